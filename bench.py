@@ -2,14 +2,17 @@
 """Benchmark of the basecalling hot path on MI355X: raw-signal samples/s through
     normalise -> conv -> GRU stack -> softmax -> prepare_post+log -> k-mer Viterbi (+backtrace) -> paths on host.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model raw_0.98_rgrgr] [--batch 1024]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--model raw_0.98_rgrgr] [--batch 1024] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic 4000-sample chunks already resident in HBM.
 N > 1: launched by torch.distributed.run, one rank per GPU; every rank processes its own batch (reads/chunks are
 independent units: no data-path collective, weak scaling); timing = max over ranks, value = whole-job samples/s.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for how `roofline` and `cpu_baseline` are defined).  Besides the
-contract's fields the line carries, all measured in the same process on the same device:
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for how `roofline` and `cpu_baseline` are defined).  A plain run sets up,
+warms up, times the K steps and prints the line (`roofline` and `cpu_baseline` null); `--dump-outputs DIR` writes what the last
+timed step returned (scores, paths, lens in float32; `loss`, `acc` in float64 with --train) as DIR/<name>.npy, from fixed seeded inputs.
+With `--full` the line also carries, all measured in the same process on the same device:
+    roofline            (and cpu_baseline, stages_ms_per_step) a separate pass with HIP events; the oracle on the host's cores
     roofline            dominant kernel of the workload: algorithmic flops / HIP-event duration against ITS pipe's peak
     exact_f32           the same workload with every product in plain fp32 MFMA
     in_flight           two / four batches in flight on streams of their own, two / four batches as one call
@@ -87,13 +90,48 @@ def parse():
                     help="tests only (tests/test_bench_launcher.py): the rank plumbing of this script -- device binding by LOCAL_RANK, "
                          "barriers, max over ranks, one line from rank 0 -- on the gloo backend with a Runner that sleeps; no GPU, "
                          "no kernel, and the line says so")
-    ap.add_argument("--quick", action="store_true", help="only the main region, the stage pass and the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed region: the stage pass (roofline), the CPU baseline and, on one GPU with one stream, "
+                         "the other legs (child processes, exact_f32, in flight, upload, host feed, whole reads, train, sustained); "
+                         "a plain run does only what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (float32 or float64; a fixed, seeded "
+                         "sample of the chunks when the arrays exceed %d MB)" % (DUMP_MAX_BYTES >> 20))
+    ap.add_argument("--quick", action="store_true", help="with --full: only the main region, the stage pass and the CPU baseline")
     ap.add_argument("--only", default=None, choices=["batch256", "model1024"],
                     help="run ONE leg and print its JSON (bench.py starts itself with this as a child process)")
     ap.add_argument("--train", action="store_true",
                     help="time the TRAINING step instead (BASELINE.json configs[4]: forward + backward + ADAMski, "
                          "gradient all-reduce over RCCL when --gpus > 1); prints the same kind of JSON line")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+#: --dump-outputs writes at most this many bytes
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, nrow=None):
+    """Write `arrays` (name -> numpy array) as out_dir/<name>.npy in float32 (float64 where float32 would lose bits: int64 or float64
+    inputs).  Arrays whose leading axis is `nrow` (one row per chunk) are cut to the same fixed, seeded sample of rows when the whole set
+    exceeds DUMP_MAX_BYTES; `rows.npy` then lists the rows kept."""
+    def as_float(a):
+        a = np.asarray(a)
+        return a.astype(np.float64 if a.dtype.itemsize > 4 else np.float32)
+    arrays = {k: as_float(v) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES and nrow:
+        per_row = sum(a.nbytes // nrow for a in arrays.values() if a.ndim and a.shape[0] == nrow)
+        fixed = total - per_row * nrow
+        keep = max(1, min(nrow, (DUMP_MAX_BYTES - fixed - 8 * nrow) // max(1, per_row)))
+        rows = np.sort(np.random.RandomState(0x5eed).choice(nrow, size=keep, replace=False))
+        arrays = {k: (a[rows] if a.ndim and a.shape[0] == nrow else a) for k, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -423,6 +461,16 @@ class Runner(object):
         # upload leg: the raw signal of the next batch comes from pinned host memory on the copy stream
         self.pinned_in = None
         self.upload_buf = None
+        self.last = None
+
+    def outputs_of_last_step(self):
+        """name -> host array of what the last step's call returned (after a synchronise)."""
+        k, scores, paths, lens = self.last
+        out = {"scores": scores.cpu().numpy(), "paths": paths.cpu().numpy(), "lens": lens.cpu().numpy()}
+        if self.with_bases:
+            out["bases"] = self.bases_dev[k].cpu().numpy()
+            out["nbases"] = self.nbases_dev[k].cpu().numpy()
+        return out
 
     def set_deterministic(self, flag):
         """Basecaller(deterministic=...): True (the default) keeps every call on the plans that compute the same bits; False lets the
@@ -449,6 +497,7 @@ class Runner(object):
             if self.copied_before[k] is not None:
                 self.copied_before[k].synchronize()                   # the host has the paths of call i - 2 of this slot
             scores, paths, lens = self.bcs[k].call_chunks(self.dev[i % self.nbuf] if src is None else src)
+            self.last = (k, scores, paths, lens)          # what the caller receives (valid until call i + 2 of the slot: --dump-outputs)
             if self.with_bases:                                                 # base sequences, still on the device
                 if self.copied[k] is not None:
                     self.streams[k].wait_event(self.copied[k])
@@ -692,11 +741,14 @@ def main_train(args, as_field=False, torch=None, dist=None):
         loss, acc = fg(x, labels, weights, 1e-3 / (1.0 + i / 5000.0))
     barrier()
     dt = time.perf_counter() - t0
-    allreduce_ms = None
+    if args.dump_outputs and not as_field and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": np.float64(float(loss)), "acc": np.float64(float(acc))})
+    allreduce_ms, flat = None, None
     if dist is not None:
         tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if dist is not None and args.full:
         # the step's one exchange by itself: the all-reduce of a flat float32 gradient of this network's size (train.allreduce_mean_),
         # back to back, max over ranks
         flat = torch.zeros(sum(int(np.prod(p.get_value().shape)) for p in net.params()), dtype=torch.float32, device="cuda")
@@ -714,7 +766,7 @@ def main_train(args, as_field=False, torch=None, dist=None):
     devices = None if as_field else devices_of_ranks(torch, dist, torch.cuda.current_device())
     # per-stage HIP events in a pass of their own
     stages = {}
-    if not args.no_stage_timing:
+    if args.full and not args.no_stage_timing:
         rec = profiler.start()
         ns = max(2, min(steps, 5))
         for i in range(ns):
@@ -769,11 +821,11 @@ def main_train(args, as_field=False, torch=None, dist=None):
                        "model": args.model, "chunk_len": L, "batch_per_gpu": B, "global_batch": B * world,
                        "parallelism": "data parallel over %d GPU(s), one all-reduce of the flat gradient per step" % world},
             "roofline": roofline, "roofline_by_stage": by_stage,
-            "cpu_baseline": cpu_baseline_train(args.model, L) if (world == 1 and args.cpu_chunks > 0) else None,
+            "cpu_baseline": cpu_baseline_train(args.model, L) if (args.full and world == 1 and args.cpu_chunks > 0) else None,
             "final_loss": float(loss),
             "devices": devices, "rccl_ranks_seen": len(devices) if dist is not None else None,
             "allreduce_ms_per_step": allreduce_ms,
-            "gradient_floats": None if dist is None else int(flat.numel()),
+            "gradient_floats": None if flat is None else int(flat.numel()),
             "stages_ms_per_step": {k: v["per_step"] for k, v in sorted(stages.items())},
             "stages_hbm_bytes_per_step": hbm_per_step,
             "hbm_bytes_per_step": sum(hbm_per_step.values()) if hbm_per_step else None})
@@ -951,7 +1003,7 @@ def main():
     rank, world, local_rank = shard.dist_info()
     stub = args.stub_device
     children = {}
-    if (world == 1 and max(1, args.streams) == 1 and not args.quick and not stub and args.small_batch_steps > 0
+    if (args.full and world == 1 and max(1, args.streams) == 1 and not args.quick and not stub and args.small_batch_steps > 0
             and args.model == "raw_0.98_rgrgr" and args.batch == 1024 and not args.with_bases):
         children = children_first(args)              # (nothing in this process has touched the device yet)
     if stub:
@@ -976,7 +1028,8 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", torch.cuda.current_device()))
     B, L = args.batch, args.chunk_len
     nstream = max(1, args.streams)
-    extras = world == 1 and nstream == 1 and not args.quick and not stub        # the single-GPU legs behind the main region
+    # the single-GPU legs behind the main region
+    extras = args.full and world == 1 and nstream == 1 and not args.quick and not stub
     nslot = max(nstream, 4 if (extras and args.overlap_steps > 0) else 1)
     if stub:
         if os.environ.get("SLOIKA_AMD_STUB_FAIL_RANK") == str(rank):      # tests: a rank that dies must fail the whole launch
@@ -1016,7 +1069,7 @@ def main():
     # a pause of 5 ms behind 100 back-to-back launches of the Gru kernel, 572 ... 602 ... 525 us over the next 40 against 520 steady -- so
     # nothing sits between the warm-up steps and the timed region but the contract's barrier: the clock probe of the region's leading
     # edge is a launch on a stream of its own beside the last warm-up step, not a synchronise - probe - synchronise of its own)
-    edge_probe = None if stub else ClockProbe(torch, nmax=4)
+    edge_probe = None if (stub or not args.full) else ClockProbe(torch, nmax=4)
     for i in range(args.warmup):
         if edge_probe is not None and i == args.warmup - 1:
             edge_probe.sample()              # the shader clock right in front of the timed region ...
@@ -1033,11 +1086,14 @@ def main():
         tl = [torch.zeros(1, dtype=torch.float64, device=dev) for _ in range(world)]
         dist.all_gather(tl, torch.tensor([per_rank_ms[0]], dtype=torch.float64, device=dev))
         per_rank_ms = [float(t.item()) for t in tl]
+    # ---- what the last timed step returned, before any other call reuses its result set ----
+    if args.dump_outputs and not stub and rank == 0:
+        dump_outputs(args.dump_outputs, run.outputs_of_last_step(), nrow=B)
 
     devices = devices_of_ranks(torch, dist, bound, stub)
     # ---- the same steps once more with HIP events around every C-ABI call: per-stage times and the roofline ----
     stages, roofline, ms_profiled, by_stage = {}, None, None, None
-    if not args.no_stage_timing and args.stage_steps > 0 and not stub:
+    if args.full and not args.no_stage_timing and args.stage_steps > 0 and not stub:
         rec = profiler.start()
         dts = timed(lambda i: run.step(i, nstream), args.stage_steps)
         profiler.stop()
@@ -1278,7 +1334,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if world == 1 and args.cpu_chunks > 0 and not stub:
+        if args.full and world == 1 and args.cpu_chunks > 0 and not stub:
             cpu = cpu_baseline(args.model, L, args.cpu_chunks)
         nst = max(1, args.stage_steps)
         gemm_flops = sum(stages[k]["flops"] for k in stages if k in MFMA_STAGES) / nst

@@ -6,7 +6,7 @@ cp $L /tmp/lib_keep.so
 for r in 1 2 3; do
  for v in old new; do
   cp tools/_build/lib_$v.so $L
-  python3 bench.py --steps 20 --warmup 3 --cpu-chunks 0 --exact-steps 0 --overlap-steps 0 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print('$v', round(d['ms_per_step'],3), {k:round(v,3) for k,v in d['stages_ms_per_step'].items()})"
+  python3 bench.py --full --steps 20 --warmup 3 --cpu-chunks 0 --exact-steps 0 --overlap-steps 0 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print('$v', round(d['ms_per_step'],3), {k:round(v,3) for k,v in d['stages_ms_per_step'].items()})"
  done
 done
 cp /tmp/lib_keep.so $L

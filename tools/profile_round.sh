@@ -10,10 +10,11 @@ tag=$1
 shift
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
 mkdir -p gpurun_out
+out=$_                 # (the folder just made: the output folder)
 if [ $# -gt 0 ]; then extra="--quick --cpu-chunks 0"; else extra=""; fi
-python3 bench.py --steps 20 --warmup 3 $extra "$@" > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
+python3 bench.py --full --steps 20 --warmup 3 $extra "$@" > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 rm -rf gpurun_out/prof_${tag}
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${tag} -- python3 bench.py --steps 10 --warmup 3 --cpu-chunks 0 --quick "$@" > gpurun_out/prof_${tag}.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag} -- python3 bench.py --full --steps 10 --warmup 3 --cpu-chunks 0 --quick "$@" > $out/prof_${tag}.log 2>&1
 rm -rf gpurun_out/pmc_fetch gpurun_out/pmc_write
 bash tools/collect_pmc.sh "$@"
 python3 tools/pmc_summary.py gpurun_out/pmc_fetch gpurun_out/pmc_write > gpurun_out/${tag}_pmc_traffic.json

@@ -11,21 +11,22 @@ tag=$1; shift
 parts=${@:-stamps util sq pmc stats bench}
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
 mkdir -p gpurun_out
+out=$_                 # (the folder just made: the output folder)
 has() { [[ " $parts " == *" $1 "* ]]; }
 Q="--steps 2 --warmup 1 --cpu-chunks 0 --quick --no-stage-timing"
 
 if has bench; then
-  timeout 600 python3 bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
-  timeout 300 python3 bench.py --train --steps 10 --warmup 3 > gpurun_out/${tag}_train_bench.json 2> gpurun_out/${tag}_train_bench.err
+  timeout 600 python3 bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+  timeout 300 python3 bench.py --full --train --steps 10 --warmup 3 > $out/${tag}_train_bench.json 2> $out/${tag}_train_bench.err
 fi
 if has stamps; then
   SLOIKA_AMD_LIB=$PWD/tools/_build/libsloika_amd_diag.so timeout 900 python3 tools/bar16_check.py 96x96 > gpurun_out/${tag}_bar16_check.txt 2>&1
 fi
 if has stats; then
   rm -rf gpurun_out/prof_${tag} gpurun_out/prof_${tag}_train
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${tag} -- python3 bench.py --steps 10 --warmup 3 --cpu-chunks 0 --quick > gpurun_out/prof_${tag}.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag} -- python3 bench.py --full --steps 10 --warmup 3 --cpu-chunks 0 --quick > $out/prof_${tag}.log 2>&1
   find gpurun_out/prof_${tag} -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} gpurun_out/${tag}_kernel_stats.csv
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${tag}_train -- python3 bench.py --train --steps 5 --warmup 2 --cpu-chunks 0 > gpurun_out/prof_${tag}_train.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag}_train -- python3 bench.py --full --train --steps 5 --warmup 2 --cpu-chunks 0 > $out/prof_${tag}_train.log 2>&1
   find gpurun_out/prof_${tag}_train -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} gpurun_out/${tag}_train_kernel_stats.csv
 fi
 if has util; then

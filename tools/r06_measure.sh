@@ -12,6 +12,7 @@ tag=$1; shift
 parts=${@:-stamps util sq pmc stats bench}
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
 mkdir -p gpurun_out
+out=$_                 # (the folder just made: the output folder)
 has() { [[ " $parts " == *" $1 "* ]]; }
 Q="--steps 2 --warmup 1 --cpu-chunks 0 --quick --no-stage-timing"
 
@@ -19,9 +20,9 @@ if has bench; then
   # the driver's own command first (a fresh process on an idle device: its 20 steps behind 5), then the default run
   timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${tag}_bench_driver_style.json 2> gpurun_out/${tag}_bench_driver_style.err
   cp bench_detail.json gpurun_out/${tag}_bench_driver_style_detail.json
-  timeout 600 python3 bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
+  timeout 600 python3 bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
   cp bench_detail.json gpurun_out/${tag}_bench_detail.json
-  timeout 300 python3 bench.py --train --steps 10 --warmup 3 > gpurun_out/${tag}_train_bench.json 2> gpurun_out/${tag}_train_bench.err
+  timeout 300 python3 bench.py --full --train --steps 10 --warmup 3 > $out/${tag}_train_bench.json 2> $out/${tag}_train_bench.err
   cp bench_detail.json gpurun_out/${tag}_train_bench_detail.json
   timeout 120 python3 tools/warmup_curve.py 60 --no-probe > gpurun_out/${tag}_warmup_curve.txt 2>&1
   timeout 120 python3 tools/warmup_kernel_only.py > gpurun_out/${tag}_warmup_kernel_only.txt 2>&1
@@ -31,12 +32,12 @@ if has stamps; then
 fi
 if has stats; then
   rm -rf gpurun_out/prof_${tag} gpurun_out/prof_${tag}_train
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${tag} -- python3 bench.py --steps 10 --warmup 3 --cpu-chunks 0 --quick > gpurun_out/prof_${tag}.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag} -- python3 bench.py --full --steps 10 --warmup 3 --cpu-chunks 0 --quick > $out/prof_${tag}.log 2>&1
   find gpurun_out/prof_${tag} -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} gpurun_out/${tag}_kernel_stats.csv
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${tag}_train -- python3 bench.py --train --steps 5 --warmup 2 --cpu-chunks 0 > gpurun_out/prof_${tag}_train.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag}_train -- python3 bench.py --full --train --steps 5 --warmup 2 --cpu-chunks 0 > $out/prof_${tag}_train.log 2>&1
   find gpurun_out/prof_${tag}_train -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} gpurun_out/${tag}_train_kernel_stats.csv
   rm -rf gpurun_out/prof_${tag}_pre
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${tag}_pre -- python3 bench.py --model pretrained --steps 10 --warmup 3 --cpu-chunks 0 --quick > gpurun_out/prof_${tag}_pre.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag}_pre -- python3 bench.py --full --model pretrained --steps 10 --warmup 3 --cpu-chunks 0 --quick > $out/prof_${tag}_pre.log 2>&1
   find gpurun_out/prof_${tag}_pre -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} gpurun_out/${tag}_pretrained_kernel_stats.csv
   rm -rf gpurun_out/prof_${tag} gpurun_out/prof_${tag}_train gpurun_out/prof_${tag}_pre
 fi
