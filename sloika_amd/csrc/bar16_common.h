@@ -33,18 +33,6 @@ __device__ __forceinline__ float sigmoid4(float x)
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
 }
 
-// Row 4g+q of a tile's accumulator for the lane (g, q, c) when only column group 0 (lanes q = 0) holds the product: lane
-// quartet q of every 16-lane row takes register q of the lanes four, eight, twelve places below it (bank-masked DPP moves
-// -- three instructions, as many as the three selects they replace).
-__device__ __forceinline__ float gather4(const f32x4 &a)
-{
-    int r = __float_as_int(a[0]);
-    r = __builtin_amdgcn_update_dpp(r, __float_as_int(a[1]), 0x114, 0xf, 0x2, false);      // row_shr:4  -> quartet 1
-    r = __builtin_amdgcn_update_dpp(r, __float_as_int(a[2]), 0x118, 0xf, 0x4, false);      // row_shr:8  -> quartet 2
-    r = __builtin_amdgcn_update_dpp(r, __float_as_int(a[3]), 0x11c, 0xf, 0x8, false);      // row_shr:12 -> quartet 3
-    return __int_as_float(r);
-}
-
 template <int V>
 using ic = std::integral_constant<int, V>;
 template <int B_, int E_, class F>
@@ -68,19 +56,6 @@ __device__ __forceinline__ void mfma3x2(const half8 &w0_hi, const half8 &w0_lo, 
     acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0_hi, h_hi, acc0, 0, 0, 0);
     acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1_hi, h_hi, acc1, 0, 0, 0);
 }
-// the same for NT tiles of the projection and K block kb of their weights
-template <int NT, int KBLK_>
-__device__ __forceinline__ void mfma3xn(const half8 (*w_hi)[KBLK_], const half8 (*w_lo)[KBLK_], int kb, const half8 &x_hi,
-                                        const half8 &x_lo, f32x4 *acc)
-{
-#pragma unroll
-    for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w_hi[t][kb], x_lo, acc[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w_lo[t][kb], x_hi, acc[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w_hi[t][kb], x_hi, acc[t], 0, 0, 0);
-}
-
 // Projection weights in ACCUMULATION registers (a wave alone on its SIMD has 256 of them next to its 256 ordinary ones), named
 // directly as the MFMA's A operand.  hipcc treats those registers as spill space and copies every operand back (four
 // v_accvgpr_read per operand and use); operands only ever used through an "a" constraint stay where they are.
@@ -151,33 +126,6 @@ __device__ __forceinline__ void z_block_mfma(f32x4 &a0, f32x4 &a1, const half8 &
     asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(a0) : "a"(w0_hi), "v"(bh));
     asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(a1) : "a"(w1_hi), "v"(bh));
 }
-// the same with hook(ic<BASE + i>) after MFMA i = 0..5: pieces of the wave's vector work that fill the issue gaps (a wave whose
-// MFMAs follow each other directly waits 16 cycles per instruction for the pipe)
-template <bool FIRST, int BASE, class F>
-__device__ __forceinline__ void z_block_mfma_hooked(f32x4 &a0, f32x4 &a1, const half8 &w0_hi, const half8 &w0_lo, const half8 &w1_hi,
-                                                    const half8 &w1_lo, const half8 &bh, const half8 &bl, F &&hook)
-{
-    if constexpr (FIRST) {
-        asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(a0) : "a"(w0_hi), "v"(bl));
-        hook(ic<BASE + 0>{});
-        asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(a1) : "a"(w1_hi), "v"(bl));
-        hook(ic<BASE + 1>{});
-    } else {
-        asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(a0) : "a"(w0_hi), "v"(bl));
-        hook(ic<BASE + 0>{});
-        asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(a1) : "a"(w1_hi), "v"(bl));
-        hook(ic<BASE + 1>{});
-    }
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(a0) : "a"(w0_lo), "v"(bh));
-    hook(ic<BASE + 2>{});
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(a1) : "a"(w1_lo), "v"(bh));
-    hook(ic<BASE + 3>{});
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(a0) : "a"(w0_hi), "v"(bh));
-    hook(ic<BASE + 4>{});
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(a1) : "a"(w1_hi), "v"(bh));
-    hook(ic<BASE + 5>{});
-}
-
 // ---- two MFMAs per product instead of three: the state's hi and lo halves in DIFFERENT column groups --------------------------
 // With four chunks per workgroup the 16 columns of the recurrent MFMAs hold four copies of every chunk (lane (g, q, c) reads
 // column 4q + c, the copies differ in q).  Let the copies q = 0, 1 carry the hi half of the state and q = 2, 3 the lo half (one

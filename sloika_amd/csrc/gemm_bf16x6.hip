@@ -16,12 +16,8 @@
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #define GB_BM 128                                        // rows per workgroup and row tile of its waves (WR row tiles: WR times as many)
-#ifndef GB_BK
-#define GB_BK 32                                         // (64: 256-byte runs per row and half the barriers, two workgroups per CU -- measured below)
-#endif
-#ifndef GB_WR
-#define GB_WR 2                                          // row tiles per wave of the wide variant
-#endif
+constexpr int GB_BK = 32;                                // K slab (64: 256-byte runs per row and half the barriers, two workgroups per CU -- not kept)
+constexpr int GB_WR = 2;                                 // row tiles per wave of the wide variant
 #define GB_XLD (GB_BK + 4)                               // floats per x row in LDS (gemm.hip)
 #define GB_WLD (GB_BK + 8)                               // bf16 per W row in LDS: the 16-byte reads of 16 rows hit 64 banks
 

@@ -19,21 +19,14 @@
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 // Row groups of 32 per workgroup.  Every workgroup streams the whole of W through LDS once, so W traffic per row falls with
-// the workgroup height.  Back-to-back launches in one process (tools/build_gemm_variants.sh): 2 groups 1.35 ms, 4 groups 1.03,
+// the workgroup height.  Back-to-back launches in one process (git history): 2 groups 1.35 ms, 4 groups 1.03,
 // 5 groups 0.97, 6 groups 0.99 (13 waves need <= 128 registers: spills) -- but inside the pipeline, between the last GRU and
 // the decoder, 4 and 5 groups both take 0.91-0.92 ms (alternating runs on one device), so the default stays at 4, which keeps
 // the patch stores for K up to 128 and fits 168 registers without scratch.
-#ifndef GH_NWM
-#define GH_NWM 4
-#endif
+constexpr int GH_NWM = 4;
 #define GH_BM (32 * GH_NWM)
 #define GH_THREADS (64 * (2 * GH_NWM + 1))
-#ifndef GH_RINGMAX
-#define GH_RINGMAX 3
-#endif
-#ifndef GH_BIASMAX
-#define GH_BIASMAX 2048
-#endif
+constexpr int GH_BIASMAX = 2048;                         // longest bias vector (N) staged in LDS
 #define GH_BN 64
 
 // power-of-two scale that brings a row whose largest magnitude is amax into [1, 2) (exponent kept inside [27, 227])
@@ -95,9 +88,6 @@ extern "C" int slk_split_f16x2_f32(const float *w, int rows, int K, void *hi, vo
 // TRSTORE: the full, aligned tiles leave through a per-wave LDS patch so that one store instruction writes 8 rows x 128
 // contiguous bytes (whole cache lines) instead of 32 rows x 32 bytes: straight from the accumulators a lane owns 16 bytes of
 // ONE row, and the store path works through 32 different lines per instruction (measured: 0.92 ms, 0.60 without stores).
-#ifndef GH_TRSTORE
-#define GH_TRSTORE true
-#endif
 // XM (the softmax layer of the training step, train_network.py:128-136, as two passes over the SAME products instead of a logits
 // tensor that is written, read, overwritten with its gradient and read again):
 //   1  statistics pass: no logits are stored.  Per row: maximum, 1 / sum of exp(l - maximum), the first column that attains the
@@ -114,7 +104,7 @@ struct XentArgs {
     int T, B, drop;
     float min_prob;
 };
-template <int KS, bool STATS, int ACT, bool TRSTORE = GH_TRSTORE, int XM = 0>
+template <int KS, bool STATS, int ACT, bool TRSTORE = true, int XM = 0>
 __global__ void __launch_bounds__(GH_THREADS) gemm_rows_f16x3_kernel(const float *__restrict__ x, long ldx,
                                                               const _Float16 *__restrict__ Whi,
                                                               const _Float16 *__restrict__ Wlo,
@@ -126,7 +116,7 @@ __global__ void __launch_bounds__(GH_THREADS) gemm_rows_f16x3_kernel(const float
     static_assert(XM == 0 || (ACT == SLK_ACT_LINEAR && (XM == 1) == STATS), "cross-entropy passes: linear logits, statistics in pass 1");
     constexpr int KP = 16 * KS;                    // padded K (halves per weight row in Whi/Wlo)
     constexpr int LD = KP + 8;                     // LDS row stride in halves: (KP+8)*2 B = odd multiple of 16 B
-    constexpr int RING = (KS <= 9 && GH_RINGMAX >= 3) ? 3 : 2;          // weight-tile slots (a tile is 64 x (KP+8) halves, twice): LDS budget
+    constexpr int RING = KS <= 9 ? 3 : 2;          // weight-tile slots (a tile is 64 x (KP+8) halves, twice): LDS budget
     constexpr int PPR = KP / 8 + 1;                // 16-byte pieces per LDS row (the last one is padding)
     constexpr int BIAS_MAX = GH_BIASMAX + GH_BN;
     __shared__ __attribute__((aligned(16))) _Float16 wsh[RING][GH_BN * LD];
@@ -137,7 +127,7 @@ __global__ void __launch_bounds__(GH_THREADS) gemm_rows_f16x3_kernel(const float
     __shared__ __attribute__((aligned(16))) float bias_lds[BIAS_MAX];   // zero padded to whole tiles
     __shared__ __attribute__((aligned(16))) float winv_lds[BIAS_MAX];   // inverse scales of the weight rows (= columns here)
     constexpr int TP = 36;                          // floats per row of a wave's 32 x 32 store patch (144 B: no bank clash)
-    constexpr bool TR = TRSTORE && XM != 1 && KS <= (GH_NWM > 4 ? 6 : 8);         // (K > 128: the weight ring leaves no room for the patches)
+    constexpr bool TR = TRSTORE && XM != 1 && KS <= 8;         // (K > 128: the weight ring leaves no room for the patches)
     __shared__ __attribute__((aligned(16))) float patch[TR ? 2 * GH_NWM * 32 * TP : 4];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -458,24 +448,19 @@ __global__ void __launch_bounds__(GH_THREADS) gemm_rows_f16x3_kernel(const float
     if (wg_fast) {
         // epilogues of full tiles 0 .. nfast-1 next to the MFMAs of tiles 1 .. nfast
         const int nfast = nfull < ntiles - 1 ? nfull : ntiles - 1;
-#ifndef GH_PHASE
-#define GH_PHASE 1               /* 0: every wave in the same order (round 1); measured 1.030 -> 1.005 ms in one process */
-#endif
         // Waves w and w+4 share a SIMD and the tile barrier keeps them in step: with the same instruction order both want the
         // matrix pipe at the same time and the vector unit at the same time.  So the upper four run a tile period the other way
         // round -- the epilogue of the previous tile FIRST, then this tile's MFMAs -- and each half's MFMAs run under the other
-        // half's epilogue.
-        if (GH_PHASE == 0 || wave < GH_NWM) {
+        // half's epilogue.  (Every wave in the same order, round 1's schedule: 1.030 against 1.005 ms in one process.)
+        if (wave < GH_NWM) {
             for (; nt + 1 <= nfast; nt += 2) {
                 accB = mma(nt);
-                if (GH_PHASE == 2) __builtin_amdgcn_sched_barrier(0);
                 epilogue_fast(nt - 1, accA);
-                if (GH_PHASE != 2) interleave_hint();
+                interleave_hint();
                 tile_barrier();
                 accA = mma(nt + 1);
-                if (GH_PHASE == 2) __builtin_amdgcn_sched_barrier(0);
                 epilogue_fast(nt, accB);
-                if (GH_PHASE != 2) interleave_hint();
+                interleave_hint();
                 tile_barrier();
             }
         } else {
@@ -625,9 +610,9 @@ static int launch_xent(const float *x, long ldx, const _Float16 *hi, const _Floa
                        long ld, long M, int K, int N, const XentArgs &xa, hipStream_t s)
 {
     dim3 grid((unsigned)((M + GH_BM - 1) / GH_BM)), block(GH_THREADS);
-    hipLaunchKernelGGL((gemm_rows_f16x3_kernel<KS, true, SLK_ACT_LINEAR, GH_TRSTORE, 1>), grid, block, 0, s, x, ldx, hi, lo, winv, bias, grad, ld,
+    hipLaunchKernelGGL((gemm_rows_f16x3_kernel<KS, true, SLK_ACT_LINEAR, true, 1>), grid, block, 0, s, x, ldx, hi, lo, winv, bias, grad, ld,
                        M, K, N, (float2 *)nullptr, xa);
-    hipLaunchKernelGGL((gemm_rows_f16x3_kernel<KS, false, SLK_ACT_LINEAR, GH_TRSTORE, 2>), grid, block, 0, s, x, ldx, hi, lo, winv, bias, grad, ld,
+    hipLaunchKernelGGL((gemm_rows_f16x3_kernel<KS, false, SLK_ACT_LINEAR, true, 2>), grid, block, 0, s, x, ldx, hi, lo, winv, bias, grad, ld,
                        M, K, N, (float2 *)nullptr, xa);
     return slk_launch_status();
 }

@@ -19,23 +19,6 @@ __device__ __forceinline__ float gru_candidate_mfma(float h_t, float z, float h)
     return omz > 0.0f ? slk_clip((h_t - z * h) * slk_rcp(omz), -1.0f, 1.0f) : 0.0f;
 }
 
-#ifdef GBM_DIAG
-__device__ unsigned long long gbm_stamps[8];
-#define GBM_STAMP(k)                                                                       \
-    {                                                                                      \
-        unsigned long long tn_;                                                            \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tn_)::"memory");        \
-        stamp_acc[k] += tn_ - tprev;                                                       \
-        tprev = tn_;                                                                       \
-    }
-extern "C" int slk_gbm_read_stamps(unsigned long long *out)
-{
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(gbm_stamps), sizeof(gbm_stamps)) == hipSuccess ? 0 : -1;
-}
-#else
-#define GBM_STAMP(k)
-#endif
-
 template <int N>
 __global__ void __launch_bounds__(320) gru_backward_mfma_kernel(const float *__restrict__ dy, long lddy,
                                                                 const float *__restrict__ hprev, long ldhp,
@@ -156,13 +139,8 @@ __global__ void __launch_bounds__(320) gru_backward_mfma_kernel(const float *__r
         }
     };
     prepare(T - 1);
-#ifdef GBM_DIAG
-    unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev)::"memory");
-#endif
     for (int it = 0; it < T; it++) {
         const int s = T - 1 - it;
-        GBM_STAMP(0)
         float *dacb = dacbuf[it & 1], *dzrb = dzrbuf[it & 1];
         float g[CPL];
         if (owner) {
@@ -178,9 +156,7 @@ __global__ void __launch_bounds__(320) gru_backward_mfma_kernel(const float *__r
                 }
             }
         }
-        GBM_STAMP(1)
         lds_barrier();                                               // 1: dac visible; ring slot s % D is free again
-        GBM_STAMP(2)
         // ---------------- product 1: drh = dac . sW2 ----------------
         float keep[CPL], rh_now[CPL];
 #pragma unroll
@@ -216,9 +192,7 @@ __global__ void __launch_bounds__(320) gru_backward_mfma_kernel(const float *__r
                 }
             }
         }
-        GBM_STAMP(3)
         lds_barrier();                                               // 2: [daz dar] visible; ring slot (s-1) % D has landed
-        GBM_STAMP(4)
         // ---------------- product 2: carry = keep + [daz dar] . sW ----------------
         if (!loader) {
             float vp[NV2];
@@ -243,7 +217,6 @@ __global__ void __launch_bounds__(320) gru_backward_mfma_kernel(const float *__r
 #pragma unroll
             for (int i = 0; i < CPL; i++) carry[i] = keep[i] + tot[c0 + i];
         }
-        GBM_STAMP(5)
 #pragma unroll
         for (int i = 0; i < CPL; i++) {
             dap[i] += tstep * (3 * N);
@@ -252,10 +225,6 @@ __global__ void __launch_bounds__(320) gru_backward_mfma_kernel(const float *__r
         // no third barrier: the next step writes the other parity's buffers, and these are rewritten two steps on, after every
         // wave has passed two more barriers
     }
-#ifdef GBM_DIAG
-    if (blockIdx.x == 0 && (tid == 0 || tid == 256))
-        for (int k = 0; k < 4; k++) gbm_stamps[(tid == 0 ? 0 : 4) + k] = k == 0 ? stamp_acc[0] + stamp_acc[1] : stamp_acc[k + 1] + (k == 3 ? stamp_acc[5] : 0);
-#endif
 }
 
 template <int N>

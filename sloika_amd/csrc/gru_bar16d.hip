@@ -20,34 +20,15 @@
 
 typedef float f32x2d __attribute__((ext_vector_type(2)));
 
-// timing experiments (tools/build_bar16d_variants.sh; results are garbage): 1 = service waves only keep the barriers, 2 = the leader
-// does not split x, 4 = chain waves skip their share of the projection, 8 = no stores to h_out
-//   16 = stamps: cycles each wave of workgroup 0 works (barrier exit -> next barrier entry) and waits per interval of a group
-#ifndef BAR16D_ABL
-#define BAR16D_ABL 0
-#endif
-// 1: the leader's split of x is cut into pieces issued between the MFMAs of a tile (measured: slower, 3320 vs 3010 cycles per step)
-#ifndef BAR16D_HOOKS
-#define BAR16D_HOOKS 0
-#endif
-#ifndef BAR16D_CT
-#define BAR16D_CT 2
-#endif
-// 1: the reset gate's epilogue in pieces between the update gate's asm MFMAs (interval A); measured: 2763 against 2697 cycles per step
-#ifndef BAR16D_ZHOOK
-#define BAR16D_ZHOOK 0
-#endif
-// which gate's weights live in accumulation registers (its MFMAs are asm, placed where the source puts them): 0 = the update gate,
-// 1 = the candidate (its MFMAs come in one run in front of its epilogue anyway; the update gate's stay the compiler's to interleave):
-// measured 2912 against 2782 cycles per step
-// 1: two MFMAs per recurrent product, the two copies of a chunk carrying the hi and the lo half of the state (bar16_common.h: mfma2x2,
-// pick_mix_d) -- the same arithmetic as gru_bar16.hip's, bit for bit; 0: round 2's three-term sequence
-#ifndef BAR16D_MIX
-#define BAR16D_MIX 1
-#endif
-#ifndef BAR16D_CACC
-#define BAR16D_CACC 0
-#endif
+// Measured and not kept (design/ notes, git history): the reset gate's epilogue in pieces between the update gate's asm MFMAs (2763 vs
+// 2697 cycles per step); the candidate's weights in accumulation registers instead of the update gate's (2912 vs 2782).
+// The leader's split of x cut into pieces issued between the MFMAs of a tile (measured: slower, 3320 vs 3010 cycles per step) is still
+// written out below, switched off: deleting its arm makes clang order the service waves' x loads and split differently, so that goes
+// in a change of its own, measured on its own.
+constexpr bool BAR16D_HOOKS = false;
+// The recurrent products take two MFMAs each, the two copies of a chunk carrying the hi and the lo half of the state (bar16_common.h:
+// mfma2x2, pick_mix_d) -- the same arithmetic as gru_bar16.hip's, bit for bit.
+// vestigial: only the removed stamp build wrote this buffer; the diagnostic build's reader below now reads zeros
 __device__ unsigned long long slk_dbg_bar16d[4][16];
 #ifdef SLK_DIAG                          /* tools/build_diag_lib.sh */
 extern "C" SLK_API int slk_debug_read_bar16d(unsigned long long *host_out)
@@ -56,25 +37,6 @@ extern "C" SLK_API int slk_debug_read_bar16d(unsigned long long *host_out)
                                                                                                                  : SLK_ERR_LAUNCH;
 }
 #endif
-// DSTAMP_IN(k): about to enter the barrier that opens interval k; DSTAMP_OUT(k): through it
-#define DSTAMP_IN(k)                                                                  \
-    if constexpr (BAR16D_ABL & 16) {                                                  \
-        unsigned long long tnow;                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                            \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tnow)::"memory");   \
-        __builtin_amdgcn_sched_barrier(0);                                            \
-        dwork[((k) + 7) & 7] += tnow - tprev;                                         \
-        tprev = tnow;                                                                 \
-    }
-#define DSTAMP_OUT(k)                                                                 \
-    if constexpr (BAR16D_ABL & 16) {                                                  \
-        unsigned long long tnow;                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                            \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tnow)::"memory");   \
-        __builtin_amdgcn_sched_barrier(0);                                            \
-        dwait[(k) & 7] += tnow - tprev;                                               \
-        tprev = tnow;                                                                 \
-    }
 
 // first tile of interval k when a service wave has st tiles per group and set (k = 8: st); the leader splits x of set 0 in
 // intervals 1..KBLK and of set 1 in intervals 4.. (or 5..), so the load is even except for interval 0 (operand fetch)
@@ -103,7 +65,7 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
     constexpr int KBLK = (I + 31) / 32;
     constexpr int GS = 4;                                // steps per projection group (16 MFMA columns = 4 steps x 4 chunks of a set)
     constexpr int R = 2 * GS;                            // vI ring: group G+1 is written while group G is consumed
-    constexpr int CT = NCW == 3 ? (KBLK == 4 ? 3 : BAR16D_CT) : 0;   // projection tiles of a chain wave (KBLK = 4: the service wave's registers hold 9 tiles, not 12) (weights in accumulation registers)
+    constexpr int CT = NCW == 3 ? (KBLK == 4 ? 3 : 2) : 0;   // projection tiles of a chain wave (KBLK = 4: the service wave's registers hold 9 tiles, not 12) (weights in accumulation registers)
     constexpr int ST = (NT16 - NCW * CT) / NSW;          // ... of a service wave
     constexpr int NACAP = 240 / (8 * KBLK);              // 256 accumulation registers, 2 * KBLK * 4 per tile
     constexpr int NA = ST < NACAP ? ST : NACAP;
@@ -118,8 +80,6 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
     __shared__ __attribute__((aligned(16))) unsigned xop_hi[2 * 2 * OPIMG], xop_lo[2 * 2 * OPIMG];      // [group & 1][set]
     __shared__ __attribute__((aligned(16))) float xinv_lds[2 * 2 * 16];
     __shared__ __attribute__((aligned(16))) float vbuf[R * 2 * VSTEP];                                   // [step % R][set]
-    constexpr bool MIX = BAR16D_MIX != 0;
-    static_assert(!MIX || (!BAR16D_ZHOOK && !BAR16D_CACC), "the two-term products are written for the default schedule only");
     // hi image [set], then lo image [set], the lo image 32 banks behind the hi image (gru_bar16.hip: on the same banks a ds_read_b128 of
     // the mixed operand, whose lane quartets read both, takes two passes -- LDSBankConflict 7.8 % of this kernel's LDS cycles in round 4)
     constexpr int IMG = 4 * N + (4 * N % 64 == 0 ? 32 : 4 * N % 64 == 32 ? 0 : 4);
@@ -236,10 +196,7 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
 #pragma unroll
         for (int p = 0; p < 2; p++) {
 #pragma unroll
-            for (int i = 0; i < KBS; i++) {
-                if constexpr (BAR16D_CACC) { wc_hi[p][i] = to_acc_regs(wc_hi[p][i]); wc_lo[p][i] = to_acc_regs(wc_lo[p][i]); }
-                else { wz_hi[p][i] = to_acc_regs(wz_hi[p][i]); wz_lo[p][i] = to_acc_regs(wz_lo[p][i]); }
-            }
+            for (int i = 0; i < KBS; i++) { wz_hi[p][i] = to_acc_regs(wz_hi[p][i]); wz_lo[p][i] = to_acc_regs(wz_lo[p][i]); }
         }
         constexpr int CTA = CT > 0 ? CT : 1;
         half8 pw_hi[CTA][KBLK], pw_lo[CTA][KBLK];
@@ -255,7 +212,7 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
         int boff[KBS];
 #pragma unroll
         for (int i = 0; i < KBS; i++) boff[i] = set * 2 * N + ((((w + i) % KBS) * 4 + g) * 4 + c) * 4;        // in dwords
-        int moff[KBS];                                   // MIX: my copy's image (q & 1 = 0: hi, 1: lo)
+        int moff[KBS];                                   // my copy's image (q & 1 = 0: hi, 1: lo)
 #pragma unroll
         for (int i = 0; i < KBS; i++) moff[i] = qh * IMG + boff[i];
         const int wd = set * 2 * N + ((w * 4 + g) * 4 + c) * 4 + 2 * qh;                         // my two packed pairs, in dwords
@@ -293,46 +250,33 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
         }
         lds_bar();                                       // vI of group 0 complete
 
-        unsigned long long dwork[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dwait[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
-        if constexpr (BAR16D_ABL & 16) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev)::"memory");
         float hold[2][2] = {{0.0f, 0.0f}, {0.0f, 0.0f}};
         [[maybe_unused]] float zkeep[2][2] = {{0.0f, 0.0f}, {0.0f, 0.0f}};      // SAVE: the update gates of the step before
         // carried from step to step: my own K block of h(s-1) as B operand (read back right after I wrote it)
         half8 oh = hzero, ol = hzero;
         settle(oh);
-        settle(ol);
+        settle(ol);                                      // (ol: unused since the three-term products went; its s_nop is in the schedule)
         // rows 4g + 2qh + j of a tile's accumulator
-        auto pick = [&](const f32x4 &a, int j) {
-            if constexpr (MIX) return pick_mix_d(a, j);
-            else return qh ? a[2 + j] : a[j];
+        auto pick = [&](const f32x4 &a, int j) { return pick_mix_d(a, j); };
+        auto mfma_z = [&](auto FIRSTC, int i, const half8 &bm, f32x4 &a0, f32x4 &a1) {
+            z_block_mfma2<decltype(FIRSTC)::value != 0>(a0, a1, wz_hi[0][i], wz_lo[0][i], wz_hi[1][i], wz_lo[1][i], bm);
         };
-        auto mfma_z = [&](auto FIRSTC, int i, const half8 &bh_, const half8 &bl_, f32x4 &a0, f32x4 &a1) {
-            if constexpr (MIX) z_block_mfma2<decltype(FIRSTC)::value != 0>(a0, a1, wz_hi[0][i], wz_lo[0][i], wz_hi[1][i], wz_lo[1][i], bh_);
-            else z_block_mfma<decltype(FIRSTC)::value != 0>(a0, a1, wz_hi[0][i], wz_lo[0][i], wz_hi[1][i], wz_lo[1][i], bh_, bl_);
-        };
-        // r / c products of one K block (MIX: bh_ = the mixed operand, bl_ unused)
-        auto mfma_rc = [&](const half8 (&wh)[2][KBS], const half8 (&wl)[2][KBS], int i, const half8 &bh_, const half8 &bl_, f32x4 &a0, f32x4 &a1) {
-            if constexpr (MIX) mfma2x2(wh[0][i], wl[0][i], wh[1][i], wl[1][i], bh_, a0, a1);
-            else mfma3x2(wh[0][i], wl[0][i], wh[1][i], wl[1][i], bh_, bl_, a0, a1);
+        // r / c products of one K block with the mixed operand bm
+        auto mfma_rc = [&](const half8 (&wh)[2][KBS], const half8 (&wl)[2][KBS], int i, const half8 &bm, f32x4 &a0, f32x4 &a1) {
+            mfma2x2(wh[0][i], wl[0][i], wh[1][i], wl[1][i], bm, a0, a1);
         };
         // One step = two intervals, each opened by a barrier (see gru_bar16.hip for the plan of a step)
         auto step = [&](auto PHC, const int s, const int G) {
             constexpr int ph = decltype(PHC)::value;
-            constexpr bool PROJ = CT > 0 && ph < KBLK && !(BAR16D_ABL & 4);
+            constexpr bool PROJ = CT > 0 && ph < KBLK;
             // ------------------------------ interval A ------------------------------
-            DSTAMP_IN(2 * ph)
-            if constexpr (BAR16D_ABL & 16) lds_bar(); else if constexpr (MIX) lds_bar_1read(); else lds_bar_2reads();
-            DSTAMP_OUT(2 * ph)
-            half8 bh[KBS], bl[KBS];                      // MIX: bh = the mixed operands, bl unused
+            lds_bar_1read();
+            half8 bh[KBS];                               // the mixed operands
             bh[0] = oh;
-            bl[0] = ol;
 #pragma unroll
-            for (int i = 1; i < KBS; i++) {
-                if constexpr (MIX) bh[i] = ldH(h_img, moff[i]);
-                else { bh[i] = ldH(h_hi, boff[i]); bl[i] = ldH(h_lo, boff[i]); }
-            }
+            for (int i = 1; i < KBS; i++) bh[i] = ldH(h_img, moff[i]);
             if (s > 0) {                                 // h(s-1), still in `hold` (gru_bar16.hip: stored behind the barrier, not in front of it)
-                if (live && s - 1 < Tc && !(BAR16D_ABL & 8)) {
+                if (live && s - 1 < Tc) {
                     *reinterpret_cast<f32x2d *>(hp) = f32x2d{hold[0][0], hold[0][1]};
                     *reinterpret_cast<f32x2d *>(hp + 16) = f32x2d{hold[1][0], hold[1][1]};
                     if constexpr (SAVE) {
@@ -354,7 +298,7 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
             }
             __builtin_amdgcn_sched_barrier(0);
             f32x4 accR[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, accZ[2];
-            mfma_rc(wr_hi, wr_lo, 0, bh[0], bl[0], accR[0], accR[1]);
+            mfma_rc(wr_hi, wr_lo, 0, bh[0], accR[0], accR[1]);
             if constexpr (PROJ) {                        // my tiles of the projection, K block ph, both sets: inside the LDS round trip
 #pragma unroll
                 for (int sset = 0; sset < 2; sset++) {
@@ -376,82 +320,41 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
             if constexpr (KBS > 1) {
                 asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");       // the six vI reads may still be on their way
 #pragma unroll
-                for (int i = 1; i < KBS; i++) { keep(bh[i]); if constexpr (!MIX) keep(bl[i]); }
+                for (int i = 1; i < KBS; i++) keep(bh[i]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int i = 1; i < KBS; i++) mfma_rc(wr_hi, wr_lo, i, bh[i], bl[i], accR[0], accR[1]);
+                for (int i = 1; i < KBS; i++) mfma_rc(wr_hi, wr_lo, i, bh[i], accR[0], accR[1]);
                 // the r products in FRONT of the update gate's asm MFMAs, which supply the wait states between them and the asm reads of
                 // pick_mix_d (instruction selection places an MFMA anywhere its operands allow, sched_barrier or not; volatile
                 // statements keep their order, and this one hands the accumulators on)
                 asm volatile("" : "+v"(accR[0]), "+v"(accR[1]));
                 __builtin_amdgcn_sched_barrier(0);
             }
-            // z products of all blocks but the last INSIDE the r epilogue: the asm MFMAs are not the compiler's to place (it put
-            // them behind the sigmoids, back to back in front of the LDS write the other waves wait for), so the epilogue is cut
-            // into pieces that follow every other MFMA: sigmoid(r) per value, r*h, the two splits, the write
+            // z products of all blocks but the last in front of the r epilogue
             float rr[2][2];
             uint2 rhi, rlo;
-            auto r_piece = [&](auto HC) {
-                constexpr int i = decltype(HC)::value;
-                constexpr int NH = 6 * (KBS - 1);                     // hooks available (0: the whole epilogue afterwards)
-                constexpr int stride = NH >= 12 ? 2 : 1;
-                if constexpr (NH >= 6) {
-                    if constexpr (i == 0 * stride) rr[0][0] = sigmoid4(fmaf(pick(accR[0], 0), inv_r[0][0], vr[0][0]));
-                    if constexpr (i == 1 * stride) rr[1][0] = sigmoid4(fmaf(pick(accR[1], 0), inv_r[1][0], vr[1][0]));
-                    if constexpr (i == 2 * stride) rr[0][1] = sigmoid4(fmaf(pick(accR[0], 1), inv_r[0][1], vr[0][1]));
-                    if constexpr (i == 3 * stride) rr[1][1] = sigmoid4(fmaf(pick(accR[1], 1), inv_r[1][1], vr[1][1]));
-                    if constexpr (i == 4 * stride) split2(rr[0][0] * hold[0][0], rr[1][0] * hold[1][0], rhi.x, rlo.x);
-                    if constexpr (i == 5 * stride) split2(rr[0][1] * hold[0][1], rr[1][1] * hold[1][1], rhi.y, rlo.y);
-                }
-            };
-            if constexpr (KBS > 1 && BAR16D_ZHOOK) {
-                static_for<0, KBS - 1>([&](auto IC) {
-                    constexpr int i = decltype(IC)::value;
-                    z_block_mfma_hooked<i == 0, 6 * i>(accZ[0], accZ[1], wz_hi[0][i], wz_lo[0][i], wz_hi[1][i], wz_lo[1][i], bh[i], bl[i], r_piece);
-                });
-            } else {
-                if constexpr (BAR16D_CACC) {
-                    accZ[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    accZ[1] = accZ[0];
+            if constexpr (KBS > 1) {
+                mfma_z(ic<1>{}, 0, bh[0], accZ[0], accZ[1]);
 #pragma unroll
-                    for (int i = 0; i < KBS - 1; i++)
-                        mfma3x2(wz_hi[0][i], wz_lo[0][i], wz_hi[1][i], wz_lo[1][i], bh[i], bl[i], accZ[0], accZ[1]);
-                } else if constexpr (KBS > 1) {
-                    mfma_z(ic<1>{}, 0, bh[0], bl[0], accZ[0], accZ[1]);
-#pragma unroll
-                    for (int i = 1; i < KBS - 1; i++) mfma_z(ic<0>{}, i, bh[i], bl[i], accZ[0], accZ[1]);
-                }
-                // pick_mix_d reads the accumulators from asm, where the compiler keeps no distance to the MFMAs that wrote them: with
-                // more than one K block the z products lie in between, otherwise let the pipe drain
-                if constexpr (MIX && KBS == 1) mfma_drain2(accR[0], accR[1]);
-#pragma unroll
-                for (int p = 0; p < 2; p++) {
-#pragma unroll
-                    for (int j = 0; j < 2; j++) rr[p][j] = sigmoid4(fmaf(pick(accR[p], j), inv_r[p][j], vr[p][j]));
-                }
-                split2(rr[0][0] * hold[0][0], rr[1][0] * hold[1][0], rhi.x, rlo.x);
-                split2(rr[0][1] * hold[0][1], rr[1][1] * hold[1][1], rhi.y, rlo.y);
-                if constexpr (BAR16D_CACC) {             // one MFMA, then up to four VALU instructions, for as long as both last
-#pragma unroll
-                    for (int i = 0; i < 6 * (KBS - 1); i++) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                    }
-                }
+                for (int i = 1; i < KBS - 1; i++) mfma_z(ic<0>{}, i, bh[i], accZ[0], accZ[1]);
             }
+            // pick_mix_d reads the accumulators from asm, where the compiler keeps no distance to the MFMAs that wrote them: with
+            // more than one K block the z products lie in between, otherwise let the pipe drain
+            if constexpr (KBS == 1) mfma_drain2(accR[0], accR[1]);
+#pragma unroll
+            for (int p = 0; p < 2; p++) {
+#pragma unroll
+                for (int j = 0; j < 2; j++) rr[p][j] = sigmoid4(fmaf(pick(accR[p], j), inv_r[p][j], vr[p][j]));
+            }
+            split2(rr[0][0] * hold[0][0], rr[1][0] * hold[1][0], rhi.x, rlo.x);
+            split2(rr[0][1] * hold[0][1], rr[1][1] * hold[1][1], rhi.y, rlo.y);
             lds_fence();
             *reinterpret_cast<uint2 *>(&rh_hi[wd]) = rhi;
             *reinterpret_cast<uint2 *>(&rh_lo[wd]) = rlo;
-            half8 ch[KBS], cl[KBS];                      // MIX: ch = the mixed operands, cl unused
-            if constexpr (MIX) {
-                ch[0] = ldH(rh_img, moff[0]);            // my own block, straight back (LDS executes a wave's operations in order)
-                cl[0] = ch[0];
-            } else {
-                ch[0] = ldH(rh_hi, boff[0]);
-                cl[0] = ldH(rh_lo, boff[0]);
-            }
+            half8 ch[KBS];                               // the mixed operands
+            ch[0] = ldH(rh_img, moff[0]);                // my own block, straight back (LDS executes a wave's operations in order)
             lds_fence();
-            const bool store = live && s < Tc && !(BAR16D_ABL & 8);
+            const bool store = live && s < Tc;
             if constexpr (SAVE) {
                 if (store) {
                     *reinterpret_cast<f32x2d *>(zp + N) = f32x2d{rr[0][0], rr[0][1]};
@@ -459,14 +362,9 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
                 }
             }
             // ------------------------------ interval B ------------------------------
-            DSTAMP_IN(2 * ph + 1)
-            if constexpr (BAR16D_ABL & 16) lds_bar(); else if constexpr (MIX) lds_bar_1read(); else lds_bar_2reads();
-            DSTAMP_OUT(2 * ph + 1)
+            lds_bar_1read();
 #pragma unroll
-            for (int i = 1; i < KBS; i++) {
-                if constexpr (MIX) ch[i] = ldH(rh_img, moff[i]);
-                else { ch[i] = ldH(rh_hi, boff[i]); cl[i] = ldH(rh_lo, boff[i]); }
-            }
+            for (int i = 1; i < KBS; i++) ch[i] = ldH(rh_img, moff[i]);
             constexpr int nph = (ph + 1) & 3;            // the next step projects K block nph of the group after ITS group
             constexpr bool NPROJ = CT > 0 && nph < KBLK;
             half8 xh[2], xl[2];
@@ -480,45 +378,31 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
             }
             __builtin_amdgcn_sched_barrier(0);
             f32x4 accC[2];
-            if constexpr (BAR16D_CACC) {
-                if constexpr (KBS == 1) { accZ[0] = f32x4{0.f, 0.f, 0.f, 0.f}; accZ[1] = accZ[0]; }
-                mfma3x2(wz_hi[0][KBS - 1], wz_lo[0][KBS - 1], wz_hi[1][KBS - 1], wz_lo[1][KBS - 1], bh[KBS - 1], bl[KBS - 1], accZ[0], accZ[1]);
-                z_block_mfma<true>(accC[0], accC[1], wc_hi[0][0], wc_lo[0][0], wc_hi[1][0], wc_lo[1][0], ch[0], cl[0]);
-            } else {
-                if constexpr (KBS > 1) mfma_z(ic<0>{}, KBS - 1, bh[KBS - 1], bl[KBS - 1], accZ[0], accZ[1]);
-                else mfma_z(ic<1>{}, 0, bh[0], bl[0], accZ[0], accZ[1]);
-                accC[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-                accC[1] = accC[0];
-                mfma_rc(wc_hi, wc_lo, 0, ch[0], cl[0], accC[0], accC[1]);
-            }
+            if constexpr (KBS > 1) mfma_z(ic<0>{}, KBS - 1, bh[KBS - 1], accZ[0], accZ[1]);
+            else mfma_z(ic<1>{}, 0, bh[0], accZ[0], accZ[1]);
+            accC[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+            accC[1] = accC[0];
+            mfma_rc(wc_hi, wc_lo, 0, ch[0], accC[0], accC[1]);
             __builtin_amdgcn_sched_barrier(0);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-            for (int i = 1; i < KBS; i++) { keep(ch[i]); if constexpr (!MIX) keep(cl[i]); }
+            for (int i = 1; i < KBS; i++) keep(ch[i]);
             if constexpr (NPROJ) {
 #pragma unroll
                 for (int sset = 0; sset < 2; sset++) { keep(xh[sset]); keep(xl[sset]); pxh[sset] = xh[sset]; pxl[sset] = xl[sset]; }
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (BAR16D_CACC) {
-                // the candidate's products with the other waves' blocks: asm, in source order, the update gate's epilogue behind the first
-                static_for<1, KBS>([&](auto IC) {
-                    constexpr int i = decltype(IC)::value;
-                    z_block_mfma<false>(accC[0], accC[1], wc_hi[0][i], wc_lo[0][i], wc_hi[1][i], wc_lo[1][i], ch[i], cl[i]);
-                });
-            } else {
-                if constexpr (KBS > 1) {
-                    mfma_rc(wc_hi, wc_lo, 1, ch[1], cl[1], accC[0], accC[1]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                // the z accumulators came from asm MFMAs the compiler does not know as such: twelve MFMAs (or the drain) have been
-                // issued since the last of them, and nothing that reads them may move above this point
-                // (... and the candidate's MFMAs issued so far lie between them and those reads: the statement hands their accumulators on too)
-                if constexpr (KBS == 1) mfma_drain2(accZ[0], accZ[1]);
-                else asm volatile("" : "+v"(accZ[0]), "+v"(accZ[1]), "+v"(accC[0]), "+v"(accC[1]));
-#pragma unroll
-                for (int i = 2; i < KBS; i++) mfma_rc(wc_hi, wc_lo, i, ch[i], cl[i], accC[0], accC[1]);
+            if constexpr (KBS > 1) {
+                mfma_rc(wc_hi, wc_lo, 1, ch[1], accC[0], accC[1]);
+                __builtin_amdgcn_sched_barrier(0);
             }
+            // the z accumulators came from asm MFMAs the compiler does not know as such: twelve MFMAs (or the drain) have been
+            // issued since the last of them, and nothing that reads them may move above this point
+            // (... and the candidate's MFMAs issued so far lie between them and those reads: the statement hands their accumulators on too)
+            if constexpr (KBS == 1) mfma_drain2(accZ[0], accZ[1]);
+            else asm volatile("" : "+v"(accZ[0]), "+v"(accZ[1]), "+v"(accC[0]), "+v"(accC[1]));
+#pragma unroll
+            for (int i = 2; i < KBS; i++) mfma_rc(wc_hi, wc_lo, i, ch[i], accC[0], accC[1]);
             float zz[2][2], omz[2][2], zh[2][2];
 #pragma unroll
             for (int p = 0; p < 2; p++) {
@@ -530,19 +414,14 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
                     asm volatile("" : "+v"(zh[p][j]), "+v"(omz[p][j]));        // pinned here: not sunk to the blend below
                 }
             }
-            if constexpr (BAR16D_CACC) {
-                __builtin_amdgcn_sched_barrier(0);
-                mfma_drain(accC[0]);
-                mfma_drain(accC[1]);
-            } else {                                     // one MFMA, then up to four VALU instructions, for as long as both last
+            // one MFMA, then up to four VALU instructions, for as long as both last
 #pragma unroll
-                for (int i = 0; i < 6 * (KBS - 2); i++) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                }
+            for (int i = 0; i < 6 * (KBS - 2); i++) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (MIX) mfma_drain2(accC[0], accC[1]);                  // the candidate's last MFMAs were issued just above
+            mfma_drain2(accC[0], accC[1]);               // the candidate's last MFMAs were issued just above
             float hn[2][2];
 #pragma unroll
             for (int p = 0; p < 2; p++) {
@@ -560,13 +439,7 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
                 *reinterpret_cast<uint2 *>(&h_hi[wd]) = hi;
                 *reinterpret_cast<uint2 *>(&h_lo[wd]) = lo;
             }
-            if constexpr (MIX) {
-                oh = ldH(h_img, moff[0]);
-                ol = oh;
-            } else {
-                oh = ldH(h_hi, boff[0]);
-                ol = ldH(h_lo, boff[0]);
-            }
+            oh = ldH(h_img, moff[0]);
             lds_fence();
             if constexpr (SAVE) {
 #pragma unroll
@@ -582,17 +455,13 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
             if (s + 2 < T) step(ic<2>{}, s + 2, G);
             if (s + 3 < T) step(ic<3>{}, s + 3, G);
         }
-        if (live && T - 1 < Tc && !(BAR16D_ABL & 8)) {   // h (and z) of the last step
+        if (live && T - 1 < Tc) {                        // h (and z) of the last step
             *reinterpret_cast<f32x2d *>(hp) = f32x2d{hold[0][0], hold[0][1]};
             *reinterpret_cast<f32x2d *>(hp + 16) = f32x2d{hold[1][0], hold[1][1]};
             if constexpr (SAVE) {
                 *reinterpret_cast<f32x2d *>(zp) = f32x2d{zkeep[0][0], zkeep[0][1]};
                 *reinterpret_cast<f32x2d *>(zp + 16) = f32x2d{zkeep[1][0], zkeep[1][1]};
             }
-        }
-        if constexpr (BAR16D_ABL & 16) {
-            if (blockIdx.x == 0 && lane == 0)
-                for (int i = 0; i < 8; i++) { slk_dbg_bar16d[wave][i] = dwork[i]; slk_dbg_bar16d[wave][8 + i] = dwait[i]; }
         }
     } else {
         // =================================================================================================
@@ -747,14 +616,14 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
             constexpr int lo = tile_first_d(ST, k), hi = tile_first_d(ST, k + 1);
             constexpr bool S0 = k >= K0 && k < K0 + KBLK, S1 = k >= 4 && k < 4 + KBLK;
             constexpr int sset = S1 ? 1 : 0, kb = S1 ? k - 4 : k - K0;
-            if constexpr ((S0 || S1) && !(BAR16D_ABL & 2) && (hi == lo || !BAR16D_HOOKS)) {   // the split on its own, then the tiles
+            if constexpr ((S0 || S1) && (hi == lo || !BAR16D_HOOKS)) {   // the split on its own, then the tiles
                 static_for<lo, hi>([&](auto TC) { project_tile(TC, G1, no_hook); });
                 if (leader && G1 > 0) {
                     if constexpr (kb == 0) split_scale(G1 + 1, ic<sset>{});
                     split_block(G1 + 1, sset, kb);
                     if constexpr (kb == KBLK - 1) load_x(G1 + 2, ic<sset>{});
                 }
-            } else if constexpr ((S0 || S1) && !(BAR16D_ABL & 2)) {
+            } else if constexpr (S0 || S1) {
                 if (leader && G1 > 0) {
                     if constexpr (kb == 0) split_scale(G1 + 1, ic<sset>{});
                     project_tile(ic<lo>{}, G1, [&](auto HC) {
@@ -782,14 +651,9 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
         lds_bar();                                       // vI of group 0 complete
 
         // interval k = 0..7 of group G (two per step, each opened by the barrier the chain waves open theirs with)
-        unsigned long long dwork[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dwait[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
-        if constexpr (BAR16D_ABL & 16) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev)::"memory");
         auto interval = [&](auto KC, const int G) {
             constexpr int k = decltype(KC)::value;
-            DSTAMP_IN(k)
             lds_bar();
-            DSTAMP_OUT(k)
-            if constexpr (BAR16D_ABL & 1) return;
             if constexpr (k == 0) load_operands(G + 1);
             project_interval(KC, G + 1);
         };
@@ -799,10 +663,6 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
             if (s + 1 < T) { interval(ic<2>{}, G); interval(ic<3>{}, G); }
             if (s + 2 < T) { interval(ic<4>{}, G); interval(ic<5>{}, G); }
             if (s + 3 < T) { interval(ic<6>{}, G); interval(ic<7>{}, G); }
-        }
-        if constexpr (BAR16D_ABL & 16) {
-            if (blockIdx.x == 0 && lane == 0)
-                for (int i = 0; i < 8; i++) { slk_dbg_bar16d[wave][i] = dwork[i]; slk_dbg_bar16d[wave][8 + i] = dwait[i]; }
         }
     }
 }

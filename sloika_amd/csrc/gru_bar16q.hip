@@ -18,19 +18,11 @@
 
 #include "bar16_common.h"
 
-// timing experiments (tools/build_bar16q_variants.sh; results are garbage): 1 = service waves only keep the barriers, 2 = chain waves
-// skip their share of the projection, 4 = no stores to h_out
-#ifndef BAR16Q_ABL
-#define BAR16Q_ABL 0
-#endif
 // first tile of interval k (of four) when a service wave has st tiles per group and set; the leader splits set 0 in interval 0 and
 // set 1 in interval 2
 __host__ __device__ constexpr int tile_first_q(int st, int k)
 {
-#ifndef BAR16Q_W
-#define BAR16Q_W 2, 2, 2, 3
-#endif
-    constexpr int w[4] = {BAR16Q_W};
+    constexpr int w[4] = {2, 2, 2, 3};
     int tot = 0, acc = 0;
     for (int i = 0; i < 4; i++) tot += w[i];
     for (int i = 0; i < k && i < 4; i++) acc += w[i];
@@ -53,10 +45,7 @@ __global__ void __launch_bounds__(256, 1) gru_bar16q_kernel(const float *__restr
     constexpr int KBLK = (I + 31) / 32;
     constexpr int GS = 2;                                // steps per projection group (16 MFMA columns = 2 steps x 8 chunks of a set)
     constexpr int R = 2 * GS;                            // vI ring: group G+1 is written while group G is consumed
-#ifndef BAR16Q_CT
-#define BAR16Q_CT 3
-#endif
-    constexpr int CT = NCW == 3 ? BAR16Q_CT : 0;         // projection tiles of a chain wave (weights in accumulation registers)
+    constexpr int CT = NCW == 3 ? 3 : 0;                 // projection tiles of a chain wave (weights in accumulation registers)
     constexpr int ST = (NT16 - NCW * CT) / NSW;          // ... of a service wave
     constexpr int NACAP = 240 / (8 * KBLK);              // 256 accumulation registers, 2 * KBLK * 4 per tile
     constexpr int NA = ST < NACAP ? ST : NACAP;
@@ -240,7 +229,7 @@ __global__ void __launch_bounds__(256, 1) gru_bar16q_kernel(const float *__restr
         // projects K block k of the NEXT group (when k < KBLK); the operands of a slot are fetched one slot earlier
         auto proj_slot = [&](auto KC) {
             constexpr int k = decltype(KC)::value;
-            if constexpr (CT > 0 && k < KBLK && !(BAR16Q_ABL & 2)) {
+            if constexpr (CT > 0 && k < KBLK) {
 #pragma unroll
                 for (int sset = 0; sset < 2; sset++) {
 #pragma unroll
@@ -268,7 +257,7 @@ __global__ void __launch_bounds__(256, 1) gru_bar16q_kernel(const float *__restr
 #pragma unroll
             for (int i = 1; i < KBS; i++) { bh[i] = ldH(h_hi, boff[i]); bl[i] = ldH(h_lo, boff[i]); }
             if (s > 0) {                                 // h(s-1), still in `hold` (gru_bar16.hip: stored behind the barrier, not in front of it)
-                if (live && s - 1 < Tc && !(BAR16Q_ABL & 4)) {
+                if (live && s - 1 < Tc) {
                     *reinterpret_cast<f32x4 *>(hp) = f32x4{hold[0][0], hold[0][1], hold[0][2], hold[0][3]};
                     *reinterpret_cast<f32x4 *>(hp + 16) = f32x4{hold[1][0], hold[1][1], hold[1][2], hold[1][3]};
                 }
@@ -348,15 +337,12 @@ __global__ void __launch_bounds__(256, 1) gru_bar16q_kernel(const float *__restr
             cl[0] = ldH(rh_lo, boff[0]);
             lds_fence();
             // one MFMA, then up to four VALU instructions, for as long as both last
-#ifndef BAR16Q_ZV
-#define BAR16Q_ZV 4
-#endif
 #pragma unroll
             for (int i = 0; i < 6 * KBS; i++) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, BAR16Q_ZV, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
             }
-            const bool store = live && s < Tc && !(BAR16Q_ABL & 4);
+            const bool store = live && s < Tc;
             if constexpr (SAVE) {
                 if (store) {
                     *reinterpret_cast<f32x4 *>(zp + N) = f32x4{rr[0][0], rr[0][1], rr[0][2], rr[0][3]};
@@ -464,7 +450,7 @@ __global__ void __launch_bounds__(256, 1) gru_bar16q_kernel(const float *__restr
             step(ic<0>{}, s, G);
             if (s + 1 < T) step(ic<1>{}, s + 1, G);
         }
-        if (live && T - 1 < Tc && !(BAR16Q_ABL & 4)) {   // h of the last step
+        if (live && T - 1 < Tc) {                        // h of the last step
             *reinterpret_cast<f32x4 *>(hp) = f32x4{hold[0][0], hold[0][1], hold[0][2], hold[0][3]};
             *reinterpret_cast<f32x4 *>(hp + 16) = f32x4{hold[1][0], hold[1][1], hold[1][2], hold[1][3]};
         }
@@ -630,7 +616,6 @@ __global__ void __launch_bounds__(256, 1) gru_bar16q_kernel(const float *__restr
         auto interval = [&](auto KC, const int G) {
             constexpr int k = decltype(KC)::value;
             lds_bar();
-            if constexpr (BAR16Q_ABL & 1) return;
             if constexpr (k == 0) load_operands(G + 1);
             project_interval(KC, G + 1);
         };

@@ -56,13 +56,6 @@ __device__ __forceinline__ float gw_chunk_max(float mx)
     return mx;
 }
 
-#ifndef GW_ABL_SKIP
-#define GW_ABL_SKIP 0                                    // timing experiments (results are garbage): waves >= this skip their dx MFMAs
-#endif
-#ifndef GW_ABL
-#define GW_ABL 0                                         // timing experiments only (results are garbage): 1 no stores, 2 no loads, 4 fixed scales
-#endif
-
 // DX: the layer's dL/dx = da . iW (rows [daz | dar | dac] of da against iW[3n][insize]) comes out of the same pass: the two operand images
 // of a step ARE da of that step as fp16 hi/lo pairs, so the product costs a wave the MFMAs of its own 16 inputs (transposed iW as A
 // operands, 2 x 9 K blocks at n = 96) and nothing else -- no second pass over da (944 MB per layer read back by a separate GEMM).
@@ -235,9 +228,6 @@ __global__ void __launch_bounds__(4 * N, 1) gru_bwd16_kernel(const float *__rest
 
     auto dx_zr = [&](f32x4 &xz, const half8 *bz) __attribute__((always_inline)) {
         if constexpr (DX) {
-#if GW_ABL_SKIP
-            if (w >= GW_ABL_SKIP) { xz = f32x4{0.f, 0.f, 0.f, 0.f}; return; }      // timing experiment: the waves that share a SIMD skip their tile
-#endif
             static_for<0, KB2>([&](auto KC) {
                 constexpr int kb = decltype(KC)::value;
                 gw_mma<kb == 0>(xz, w3l[kb], bz[kb]);
@@ -247,9 +237,6 @@ __global__ void __launch_bounds__(4 * N, 1) gru_bwd16_kernel(const float *__rest
     };
     auto dx_c = [&](f32x4 &xc, const half8 *bm) __attribute__((always_inline)) {
         if constexpr (DX) {
-#if GW_ABL_SKIP
-            if (w >= GW_ABL_SKIP) { xc = f32x4{0.f, 0.f, 0.f, 0.f}; return; }
-#endif
             static_for<0, KB1>([&](auto KC) {
                 constexpr int kb = decltype(KC)::value;
                 gw_mma<kb == 0>(xc, w4l[kb], bm[kb]);
@@ -266,16 +253,10 @@ __global__ void __launch_bounds__(4 * N, 1) gru_bwd16_kernel(const float *__rest
         half8 bz[KB2];
 #pragma unroll
         for (int kb = 0; kb < KB2; kb++) bz[kb] = ldH(z_img, moff2[kb]);
-#if GW_ABL & 4
-        const float Gb = 1.0f;
-#else
         const float Gb = __uint_as_float(s_m[par][c]);   // >= max |g| of this step over the chunk's units (see below)
         // the other parity's slot is empty again before it is filled behind this step's barrier Y (it was read last a whole barrier ago)
         if (tid < 4) s_m[par ^ 1][tid] = 0u;
-#endif
-#if !(GW_ABL & 2)
         load_v(vs[(ph + 4) % 5]);
-#endif
         f32x4 a2;                                        // (two chains over alternating K blocks: measured, 3 % slower)
         static_for<0, KB2>([&](auto KC) {
             constexpr int kb = decltype(KC)::value;
@@ -299,12 +280,10 @@ __global__ void __launch_bounds__(4 * N, 1) gru_bwd16_kernel(const float *__rest
         const float gg = uok ? cur.dy + keep + p2 : 0.0f;
         const float dac = gg * omz * (1.0f - cc * cc);
         const float daz = gg * (h - cc) * z * omz;
-#if !(GW_ABL & 1)
         if (live && uok) {
             dap[2 * n] = dac;
             dap[0] = daz;
         }
-#endif
         {
             float hv = dac * sc1;
             asm volatile("" : "+v"(hv));                 // split2's note on v_fma_mixlo_f16 applies
@@ -333,24 +312,18 @@ __global__ void __launch_bounds__(4 * N, 1) gru_bwd16_kernel(const float *__rest
         const float drh = uok ? pick_mix(a1) * inv1 * invs1 : 0.0f;
         const float dar = drh * h * r * (1.0f - r);
         keep = gg * z + drh * r;
-#if !(GW_ABL & 1)
         if (live && uok) {
             dap[n] = dar;
             rhp[0] = r * h;
         }
-#else
-        if (live && uok && T < 0) { dap[n] = dar + dac + daz; rhp[0] = r * h; }
-#endif
         dap += dstep;
         rhp += rhstep;
         {
-#if !(GW_ABL & 4)
             // |g| of the next step <= max_u |dy + keep| + C1 max_u |dzr| <= 2 max_u (|dy + keep| + C1 |dzr|): ONE number per chunk and
             // step.  (Round 3 exchanged the two maxima and the exact max |g| as well: three atomics, 2260 cycles per step; one: 1950;
             // none -- fixed scales, a timing experiment -- 1640.  Issuing it behind a barrier instead of in front of one, or from 16
-            // lanes after a reduction over the k groups, changes nothing or costs: tools/bwd16_variants.py.)
+            // lanes after a reduction over the k groups, changes nothing or costs: measured, see git history.)
             amax(&s_m[par ^ 1][c], uok ? 2.0f * fmaf(C1, fmaxf(fabsf(daz), fabsf(dar)), fabsf(nxt.dy + keep)) : 0.0f);
-#endif
             float v0 = daz * sc2, v1 = dar * sc2;
             asm volatile("" : "+v"(v0), "+v"(v1));
             const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1;
@@ -369,11 +342,7 @@ __global__ void __launch_bounds__(4 * N, 1) gru_bwd16_kernel(const float *__rest
                 dxv *= gw_dact(yb_prev, dact);
                 yb_prev = cur.yb;
             }
-#if !(GW_ABL & 1)
             if (live && xok && !first_step) dxp[-dxstep] = dxv;
-#else
-            if (live && xok && T < 0) dxp[0] = dxv;
-#endif
         }
         if constexpr (DX) {
             dx_c(xc, bm);                                  // this step's dac half, under the [daz | dar] image's way to LDS

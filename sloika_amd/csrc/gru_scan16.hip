@@ -20,20 +20,9 @@
 
 #include "bar16_common.h"
 
-// 1: the update gate's products with the wave's own K block right behind the reset gate's, inside the LDS round trip (0: behind the
-// reset gate's other blocks; measured equal)
-// timing experiments (results garbage): 1 = do not wait for the projection loads, 2 = no stores, 4 = no projection loads at all
-#ifndef SCAN16_ABL
-#define SCAN16_ABL 0
-#endif
-#ifndef SCAN16_Z0_EARLY
-#define SCAN16_Z0_EARLY 1
-#endif
-// 1: two MFMAs per recurrent product, the state's hi and lo halves in different column groups (bar16_common.h, mfma2x2 / pick_mix);
-// 0: the three-term sequence of round 2 (every column group a copy of the hi half, the lo half a second operand)
-#ifndef SCAN16_MIX
-#define SCAN16_MIX 1
-#endif
+// Two MFMAs per recurrent product, the state's hi and lo halves in different column groups (bar16_common.h, mfma2x2 / pick_mix).
+// The update gate's products with the wave's own K block come right behind the reset gate's, inside the LDS round trip (behind the
+// reset gate's other blocks measured equal).
 // one float per lane from HBM, not tracked by the compiler: the caller counts (s_waitcnt vmcnt(n), then pin_f)
 __device__ __forceinline__ void gload1(float &dst, const float *src) { asm volatile("global_load_dword %0, %1, off" : "=v"(dst) : "v"(src) : "memory"); }
 // the same with the row's base address in scalar registers and the lane's part as an unsigned 32-bit byte offset: nothing but one
@@ -54,7 +43,6 @@ __global__ void __launch_bounds__(256, 1) gru_scan16_kernel(const float *__restr
     constexpr bool T9 = N == 160;
     constexpr int NV = T9 ? 3 : 2;                       // (neuron, chunk) pairs a lane requests per step
 
-    constexpr bool MIX = SCAN16_MIX != 0;
     // hi image, then lo image 32 banks behind it (gru_bar16.hip)
     constexpr int LO = 2 * N + (2 * N % 64 == 32 ? 0 : 32);
     __shared__ __attribute__((aligned(16))) unsigned h_img[LO + 2 * N], rh_img[LO + 2 * N];
@@ -162,10 +150,10 @@ __global__ void __launch_bounds__(256, 1) gru_scan16_kernel(const float *__restr
     int boff[KBS];
 #pragma unroll
     for (int i = 0; i < KBS; i++) boff[i] = ((((w + i) % KBS) * 4 + g) * 4 + c) * 4;        // in dwords
-    int moff[KBS];                                       // MIX: my column group's image (q = 0, 1: hi; q = 2, 3: lo)
+    int moff[KBS];                                       // my column group's image (q = 0, 1: hi; q = 2, 3: lo)
 #pragma unroll
     for (int i = 0; i < KBS; i++) moff[i] = (q >> 1) * LO + boff[i];
-    auto pick = [&](const f32x4 &a) { if constexpr (MIX) return pick_mix(a); else return sel4(a, q); };
+    auto pick = [&](const f32x4 &a) { return pick_mix(a); };
     const int wd = ((w * 4 + g) * 4 + c) * 4 + q;                                           // my packed pair, in dwords
     const int n0 = 32 * w + 4 * g + q;                                                      // my neuron of tile 2w (+16: 2w+1)
     const bool nok0 = n0 < n, nok1 = n0 + 16 < n;
@@ -211,7 +199,7 @@ __global__ void __launch_bounds__(256, 1) gru_scan16_kernel(const float *__restr
     float hold[2] = {0.0f, 0.0f};
     float hold9 = 0.0f;
     // one gate of the ninth tile: sum over the K blocks of the 3-term split, A operands from LDS (slot i <-> my block order)
-    auto tile9_mfma = [&](int gate, const half8 *bhh, const half8 *bll) __attribute__((always_inline)) {
+    auto tile9_mfma = [&](int gate, const half8 *bhh) __attribute__((always_inline)) {
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         half8 ah = *w9at(gate, wu, 0), al = *w9at(gate, wu, 1);                     // my operand order starts at my own K block
 #pragma unroll
@@ -222,17 +210,8 @@ __global__ void __launch_bounds__(256, 1) gru_scan16_kernel(const float *__restr
                 nh = *w9at(gate, kb, 0);
                 nl = *w9at(gate, kb, 1);
             }
-            if constexpr (MIX) {                                                    // bhh = the mixed operands, bll unused
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bhh[i], acc, 0, 0, 0);
-                if (i == 0) asm volatile("" : "+v"(acc) : "v"(ah), "v"(al), "v"(bhh[0]));
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bhh[i], acc, 0, 0, 0);
-                ah = nh;
-                al = nl;
-                continue;
-            }
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bll[i], acc, 0, 0, 0);
-            if (i == 0) asm volatile("" : "+v"(acc) : "v"(ah), "v"(al), "v"(bll[0]), "v"(bhh[0]));     // see gemm_rows_f16x3.hip
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bhh[i], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bhh[i], acc, 0, 0, 0);       // bhh: the mixed operands
+            if (i == 0) asm volatile("" : "+v"(acc) : "v"(ah), "v"(al), "v"(bhh[0]));
             acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bhh[i], acc, 0, 0, 0);
             ah = nh;
             al = nl;
@@ -241,70 +220,46 @@ __global__ void __launch_bounds__(256, 1) gru_scan16_kernel(const float *__restr
     };
     half8 oh = {0, 0, 0, 0, 0, 0, 0, 0}, ol = {0, 0, 0, 0, 0, 0, 0, 0};      // my own K block of h(s-1) as B operand
     settle(oh);
-    settle(ol);
+    settle(ol);                                          // (ol: unused since the three-term products went; its s_nop is in the schedule)
     auto step = [&](auto PHC, const int s) {
         constexpr int ph = decltype(PHC)::value;
         VI &cur = vs[ph];
         // ------------------------------ interval A ------------------------------
-        if constexpr (MIX) lds_bar_1read(); else lds_bar_2reads();
-        half8 bh[KBS], bl[KBS];                          // MIX: bh = the mixed operands, bl unused
+        lds_bar_1read();
+        half8 bh[KBS];                                   // the mixed operands
         bh[0] = oh;
-        bl[0] = ol;
 #pragma unroll
-        for (int i = 1; i < KBS; i++) {
-            if constexpr (MIX) bh[i] = ldH(h_img, moff[i]);
-            else { bh[i] = ldH(h_hi, boff[i]); bl[i] = ldH(h_lo, boff[i]); }
-        }
-        if constexpr (!(SCAN16_ABL & 4)) load_vi(s + 3, vs[(ph + 3) & 3]);                // three steps ahead
+        for (int i = 1; i < KBS; i++) bh[i] = ldH(h_img, moff[i]);
+        load_vi(s + 3, vs[(ph + 3) & 3]);                                                // three steps ahead
         __builtin_amdgcn_sched_barrier(0);
         f32x4 accR[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, accZ[2], accC[2];
-        if constexpr (MIX) {
-            if constexpr (T9) z_block_mfma2<true>(accR[0], accR[1], wr_hi[0][0], wr_lo[0][0], wr_hi[1][0], wr_lo[1][0], bh[0]);
-            else mfma2x2(wr_hi[0][0], wr_lo[0][0], wr_hi[1][0], wr_lo[1][0], bh[0], accR[0], accR[1]);
-        } else {
-            if constexpr (T9) z_block_mfma<true>(accR[0], accR[1], wr_hi[0][0], wr_lo[0][0], wr_hi[1][0], wr_lo[1][0], bh[0], bl[0]);
-            else mfma3x2(wr_hi[0][0], wr_lo[0][0], wr_hi[1][0], wr_lo[1][0], bh[0], bl[0], accR[0], accR[1]);
-        }
-#if SCAN16_Z0_EARLY
-        if constexpr (MIX) z_block_mfma2<true>(accZ[0], accZ[1], wz_hi[0][0], wz_lo[0][0], wz_hi[1][0], wz_lo[1][0], bh[0]);
-        else z_block_mfma<true>(accZ[0], accZ[1], wz_hi[0][0], wz_lo[0][0], wz_hi[1][0], wz_lo[1][0], bh[0], bl[0]);
-#endif
+        if constexpr (T9) z_block_mfma2<true>(accR[0], accR[1], wr_hi[0][0], wr_lo[0][0], wr_hi[1][0], wr_lo[1][0], bh[0]);
+        else mfma2x2(wr_hi[0][0], wr_lo[0][0], wr_hi[1][0], wr_lo[1][0], bh[0], accR[0], accR[1]);
+        z_block_mfma2<true>(accZ[0], accZ[1], wz_hi[0][0], wz_lo[0][0], wz_hi[1][0], wz_lo[1][0], bh[0]);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-        for (int i = 1; i < KBS; i++) { keep(bh[i]); if constexpr (!MIX) keep(bl[i]); }
+        for (int i = 1; i < KBS; i++) keep(bh[i]);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 1; i < KBS; i++) {
-            if constexpr (MIX) {
-                if constexpr (T9) z_block_mfma2<false>(accR[0], accR[1], wr_hi[0][i], wr_lo[0][i], wr_hi[1][i], wr_lo[1][i], bh[i]);
-                else mfma2x2(wr_hi[0][i], wr_lo[0][i], wr_hi[1][i], wr_lo[1][i], bh[i], accR[0], accR[1]);
-            } else {
-                if constexpr (T9) z_block_mfma<false>(accR[0], accR[1], wr_hi[0][i], wr_lo[0][i], wr_hi[1][i], wr_lo[1][i], bh[i], bl[i]);
-                else mfma3x2(wr_hi[0][i], wr_lo[0][i], wr_hi[1][i], wr_lo[1][i], bh[i], bl[i], accR[0], accR[1]);
-            }
+            if constexpr (T9) z_block_mfma2<false>(accR[0], accR[1], wr_hi[0][i], wr_lo[0][i], wr_hi[1][i], wr_lo[1][i], bh[i]);
+            else mfma2x2(wr_hi[0][i], wr_lo[0][i], wr_hi[1][i], wr_lo[1][i], bh[i], accR[0], accR[1]);
         }
         f32x4 acc9 = {0.f, 0.f, 0.f, 0.f};
         float h9prev = 0.0f;
         if constexpr (T9) {
             if (duty == 0) h9prev = h9f[lane];                                     // written by wave 3 before the barrier that ended step s-1
-            if (duty == 0 || duty == 1) acc9 = tile9_mfma(duty, bh, bl);
+            if (duty == 0 || duty == 1) acc9 = tile9_mfma(duty, bh);
         }
         __builtin_amdgcn_sched_barrier(0);
         // z products of blocks 0 .. KBS-2 under the r epilogue
-#if !SCAN16_Z0_EARLY
-        if constexpr (MIX) z_block_mfma2<true>(accZ[0], accZ[1], wz_hi[0][0], wz_lo[0][0], wz_hi[1][0], wz_lo[1][0], bh[0]);
-        else z_block_mfma<true>(accZ[0], accZ[1], wz_hi[0][0], wz_lo[0][0], wz_hi[1][0], wz_lo[1][0], bh[0], bl[0]);
-#endif
         static_for<1, KBS - 1>([&](auto IC) {
             constexpr int i = decltype(IC)::value;
-            if constexpr (MIX) z_block_mfma2<false>(accZ[0], accZ[1], wz_hi[0][i], wz_lo[0][i], wz_hi[1][i], wz_lo[1][i], bh[i]);
-            else z_block_mfma<false>(accZ[0], accZ[1], wz_hi[0][i], wz_lo[0][i], wz_hi[1][i], wz_lo[1][i], bh[i], bl[i]);
+            z_block_mfma2<false>(accZ[0], accZ[1], wz_hi[0][i], wz_lo[0][i], wz_hi[1][i], wz_lo[1][i], bh[i]);
         });
-        if constexpr (!(SCAN16_ABL & 5)) {                                                                  // this step's vI (see above)
-            if constexpr (T9) asm volatile("s_waitcnt vmcnt(27)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-        }
+        if constexpr (T9) asm volatile("s_waitcnt vmcnt(27)" ::: "memory");           // this step's vI (see above)
+        else asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
         pin_f(cur.z[0]); pin_f(cur.z[1]); pin_f(cur.r[0]); pin_f(cur.r[1]); pin_f(cur.c[0]); pin_f(cur.c[1]);
         if constexpr (T9) { pin_f(cur.z[2]); pin_f(cur.r[2]); pin_f(cur.c[2]); }
         if constexpr (T9) { mfma_drain(accR[0]); mfma_drain(accR[1]); }       // asm MFMAs: the compiler keeps no distance for them
@@ -329,41 +284,24 @@ __global__ void __launch_bounds__(256, 1) gru_scan16_kernel(const float *__restr
                 z9f[lane] = sigmoid4(fmaf(pick(acc9), inv9, cur.z[2]));
             }
         }
-        half8 ch[KBS], cl[KBS];                          // MIX: ch = the mixed operands, cl unused
-        if constexpr (MIX) {
-            ch[0] = ldH(rh_img, moff[0]);                // my own block, straight back (LDS executes a wave's operations in order)
-            cl[0] = ch[0];
-        } else {
-            ch[0] = ldH(rh_hi, boff[0]);
-            cl[0] = ldH(rh_lo, boff[0]);
-        }
+        half8 ch[KBS];                                   // the mixed operands
+        ch[0] = ldH(rh_img, moff[0]);                    // my own block, straight back (LDS executes a wave's operations in order)
         lds_fence();
         // ------------------------------ interval B ------------------------------
-        if constexpr (MIX) lds_bar_1read(); else lds_bar_2reads();
+        lds_bar_1read();
 #pragma unroll
-        for (int i = 1; i < KBS; i++) {
-            if constexpr (MIX) ch[i] = ldH(rh_img, moff[i]);
-            else { ch[i] = ldH(rh_hi, boff[i]); cl[i] = ldH(rh_lo, boff[i]); }
-        }
+        for (int i = 1; i < KBS; i++) ch[i] = ldH(rh_img, moff[i]);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (MIX) {
-            z_block_mfma2<false>(accZ[0], accZ[1], wz_hi[0][KBS - 1], wz_lo[0][KBS - 1], wz_hi[1][KBS - 1], wz_lo[1][KBS - 1], bh[KBS - 1]);
-            z_block_mfma2<true>(accC[0], accC[1], wc_hi[0][0], wc_lo[0][0], wc_hi[1][0], wc_lo[1][0], ch[0]);
-            asm volatile("" ::"v"(bh[KBS - 1]));         // the fresh accumulators must not take over the operand the z MFMAs still read
-        } else {
-            z_block_mfma<false>(accZ[0], accZ[1], wz_hi[0][KBS - 1], wz_lo[0][KBS - 1], wz_hi[1][KBS - 1], wz_lo[1][KBS - 1], bh[KBS - 1],
-                                bl[KBS - 1]);
-            z_block_mfma<true>(accC[0], accC[1], wc_hi[0][0], wc_lo[0][0], wc_hi[1][0], wc_lo[1][0], ch[0], cl[0]);
-            asm volatile("" ::"v"(bh[KBS - 1]), "v"(bl[KBS - 1]));
-        }
+        z_block_mfma2<false>(accZ[0], accZ[1], wz_hi[0][KBS - 1], wz_lo[0][KBS - 1], wz_hi[1][KBS - 1], wz_lo[1][KBS - 1], bh[KBS - 1]);
+        z_block_mfma2<true>(accC[0], accC[1], wc_hi[0][0], wc_lo[0][0], wc_hi[1][0], wc_lo[1][0], ch[0]);
+        asm volatile("" ::"v"(bh[KBS - 1]));             // the fresh accumulators must not take over the operand the z MFMAs still read
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-        for (int i = 1; i < KBS; i++) { keep(ch[i]); if constexpr (!MIX) keep(cl[i]); }
+        for (int i = 1; i < KBS; i++) keep(ch[i]);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (MIX) z_block_mfma2<false>(accC[0], accC[1], wc_hi[0][1], wc_lo[0][1], wc_hi[1][1], wc_lo[1][1], ch[1]);
-        else z_block_mfma<false>(accC[0], accC[1], wc_hi[0][1], wc_lo[0][1], wc_hi[1][1], wc_lo[1][1], ch[1], cl[1]);
-        // the z accumulators: twelve (MIX: eight) MFMAs have been issued since their last one
+        z_block_mfma2<false>(accC[0], accC[1], wc_hi[0][1], wc_lo[0][1], wc_hi[1][1], wc_lo[1][1], ch[1]);
+        // the z accumulators: eight MFMAs have been issued since their last one
         asm volatile("" : "+v"(accZ[0]), "+v"(accZ[1]));
         float zz[2], omz[2], zh[2];
 #pragma unroll
@@ -375,15 +313,14 @@ __global__ void __launch_bounds__(256, 1) gru_scan16_kernel(const float *__restr
         }
         static_for<2, KBS>([&](auto IC) {
             constexpr int i = decltype(IC)::value;
-            if constexpr (MIX) z_block_mfma2<false>(accC[0], accC[1], wc_hi[0][i], wc_lo[0][i], wc_hi[1][i], wc_lo[1][i], ch[i]);
-            else z_block_mfma<false>(accC[0], accC[1], wc_hi[0][i], wc_lo[0][i], wc_hi[1][i], wc_lo[1][i], ch[i], cl[i]);
+            z_block_mfma2<false>(accC[0], accC[1], wc_hi[0][i], wc_lo[0][i], wc_hi[1][i], wc_lo[1][i], ch[i]);
         });
         f32x4 acc9c = {0.f, 0.f, 0.f, 0.f};
         float z9 = 0.0f;
         if constexpr (T9) {
             if (w3) {
                 z9 = z9f[lane];                                                     // wave 1 wrote it before the barrier that opened this interval
-                acc9c = tile9_mfma(2, ch, cl);
+                acc9c = tile9_mfma(2, ch);
             }
         }
         mfma_drain(accC[0]);
@@ -413,15 +350,9 @@ __global__ void __launch_bounds__(256, 1) gru_scan16_kernel(const float *__restr
                 h_lo[wd9] = lo;
             }
         }
-        if constexpr (MIX) {
-            oh = ldH(h_img, moff[0]);
-            ol = oh;
-        } else {
-            oh = ldH(h_hi, boff[0]);
-            ol = ldH(h_lo, boff[0]);
-        }
+        oh = ldH(h_img, moff[0]);
         lds_fence();
-        if (live && s < Tc && !(SCAN16_ABL & 2)) {
+        if (live && s < Tc) {
             if (nok0) hp[0] = hn[0];
             if (nok1) hp[16] = hn[1];
             if constexpr (T9) {

@@ -29,9 +29,7 @@ __device__ __forceinline__ void lf_gload4(f32x4 &dst, unsigned voff, const float
 
 // Two workgroups per CU (<= 256 registers): the two directions of a birnn, or two batches in flight, share the SIMDs and fill each
 // other's barrier and LDS waits.
-#ifndef LF_OCC
-#define LF_OCC 2
-#endif
+constexpr int LF_OCC = 2;
 
 template <int KBLK>
 __global__ void __launch_bounds__(256, LF_OCC) lstm_fused16_kernel(const float *__restrict__ x, long ldx, const float *__restrict__ iW,
@@ -318,21 +316,6 @@ __global__ void __launch_bounds__(256, LF_OCC) lstm_fused16_kernel(const float *
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// LF_OCC 1 only: dynamic LDS that keeps a second workgroup off the CU (a launch of <= 256 workgroups then takes one CU each)
-template <int KBLK>
-static size_t lstm_fused16_exclusive_lds()
-{
-    if (LF_OCC > 1) return 0;
-    hipFuncAttributes attr;
-    if (hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(lstm_fused16_kernel<KBLK>)) != hipSuccess) return 0;
-    const size_t half_cu = 80 * 1024 + 512;
-    const size_t dyn = attr.sharedSizeBytes >= half_cu ? 0 : half_cu - attr.sharedSizeBytes;
-    if (dyn && hipFuncSetAttribute(reinterpret_cast<const void *>(lstm_fused16_kernel<KBLK>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)dyn) != hipSuccess)
-        return 0;
-    return dyn;
-}
-
 // include/sloika_amd.h
 extern "C" int slk_lstm_fused16_f32(const float *x, long ldx, const float *iW, const float *sW, const float *bias, const float *p, float *y,
                                     long ldy, int T, int B, int insize, int n, int reverse, int act, int gate_act, const int32_t *lens,
@@ -344,12 +327,10 @@ extern "C" int slk_lstm_fused16_f32(const float *x, long ldx, const float *iW, c
     if ((unsigned long long)T * B * ldx * sizeof(float) >= (1ull << 32)) return SLK_ERR_UNSUPPORTED;          // 32-bit lane offsets
     hipStream_t s = slk_stream(stream);
     if (insize <= 32) {
-        const size_t dyn = SLK_PER_DEVICE(size_t, lstm_fused16_exclusive_lds<1>());
-        hipLaunchKernelGGL((lstm_fused16_kernel<1>), dim3((B + 3) / 4), dim3(256), dyn, s, x, ldx, iW, bias, sW, p, y, ldy, T, B, insize, n,
+        hipLaunchKernelGGL((lstm_fused16_kernel<1>), dim3((B + 3) / 4), dim3(256), 0, s, x, ldx, iW, bias, sW, p, y, ldy, T, B, insize, n,
                            reverse & 1, lens);
     } else {
-        const size_t dyn = SLK_PER_DEVICE(size_t, lstm_fused16_exclusive_lds<2>());
-        hipLaunchKernelGGL((lstm_fused16_kernel<2>), dim3((B + 3) / 4), dim3(256), dyn, s, x, ldx, iW, bias, sW, p, y, ldy, T, B, insize, n,
+        hipLaunchKernelGGL((lstm_fused16_kernel<2>), dim3((B + 3) / 4), dim3(256), 0, s, x, ldx, iW, bias, sW, p, y, ldy, T, B, insize, n,
                            reverse & 1, lens);
     }
     return slk_launch_status();

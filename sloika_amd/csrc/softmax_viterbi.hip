@@ -37,49 +37,11 @@
 #define SV_NK 1024
 #define SV_AS 320               /* floats between the four first-base blocks of a score vector (5 x 64 dwords: ds_read2st64) */
 #define SV_VP (4 * SV_AS)       /* padded score vector: element a*256 + r lives at a*SV_AS + r + 8 * (r >> 6) */
-#ifndef SV_D
-#define SV_D 3                  /* weight fragment pairs in flight per wave */
-#endif
-// diagnostic build (tools only): workgroup 0, wave 0 stamps the shader clock after every step's barrier into lp_dump (then a
-// buffer of uint64 [periods][16], not a log-posterior dump)
-#ifdef SV_DIAG
-#define SV_STAMP(K)                                                                                      \
-    do {                                                                                                 \
-        if (blockIdx.x == 0 && tid == 0 && lp_dump)                                                      \
-            reinterpret_cast<unsigned long long *>(lp_dump)[(cb + 1) * 16 + K] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-// extra stamps inside steps: slot 0..15 of a second table behind the first (offset 64 periods... see tools/sv_variants.py)
-#define SV_STAMP2(S)                                                                                     \
-    do {                                                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                               \
-        if (blockIdx.x == 0 && tid == 0 && lp_dump)                                                      \
-            reinterpret_cast<unsigned long long *>(lp_dump)[4096 + (cb + 1) * 16 + S] = __builtin_amdgcn_s_memtime(); \
-        __builtin_amdgcn_sched_barrier(0);                                                               \
-    } while (0)
-#else
-#define SV_STAMP(K) do { } while (0)
-#define SV_STAMP2(S) do { } while (0)
-#endif
-#ifndef SV_ORDER
-#define SV_ORDER 0
-#endif
-#ifndef SV_AHEAD
-#define SV_AHEAD 4              /* positions between the LDS request of a pair's A images and its first MFMA */
-#endif
-#ifndef SV_MIX
-#define SV_MIX 6                /* vector instructions the scheduler is asked to place behind every MFMA (SV_ORDER 2) */
-#endif
-#ifndef SV_MMA_STEPS
-#define SV_MMA_STEPS 10         /* steps 1 .. SV_MMA_STEPS of a period carry the MFMAs of the next block */
-#endif
+constexpr int SV_D = 3;                 /* weight fragment pairs in flight per wave */
+constexpr int SV_AHEAD = 4;             /* positions between the LDS request of a pair's A images and its first MFMA */
 #define SV_ETA 1e-10f
 #define SV_LOG2E 1.4426950408889634f
 #define SV_LN2 0.6931471805599453f
-// timing-only builds of tools/build_sv_variants.sh (results are then garbage): 1 no MFMAs, 2 no weight loads, 4 no dynamic
-// programme, 8 no exponentials / logarithms, 16 no row reductions, 32 no operand preparation
-#ifndef SV_ABL
-#define SV_ABL 0
-#endif
 
 template <int K> using ic = std::integral_constant<int, K>;
 template <int B_, int E_, class F> __device__ __forceinline__ void static_for_sv(F &&f)
@@ -287,11 +249,7 @@ __device__ __forceinline__ float sv_logpost(float p, float min_prob, float one_m
 template <int KS> struct SvSched {
     static constexpr int NP = 4 * KS;                           // weight fragment pairs per wave and block
     static constexpr int NMF = 3 * NP;                          // MFMAs per wave and block
-#ifdef SV_MMA_LAST
-    static constexpr int MMA_LAST = SV_MMA_LAST;
-#else
     static constexpr int MMA_LAST = 8;
-#endif
     static constexpr int NM = MMA_LAST + 1;
     static constexpr int MPS = (NMF + NM - 1) / NM;             // MFMAs per step
     // positions of a step that take MFMAs: two right behind the programme's LDS requests (their A images were requested at the end of the
@@ -299,18 +257,10 @@ template <int KS> struct SvSched {
     // for the barrier, and so that the two waves of a SIMD, which run the same program in lock step, do not ask the matrix pipe for
     // sixteen MFMAs within the 250 cycles of the chunks; position q takes MFMAs [q MPS / NPOS, (q + 1) MPS / NPOS) of the step
     static constexpr int NPOS = 12;
-#ifndef SV_EDGE
-#define SV_EDGE 0
-#endif
-    // first MFMA (of the step's MPS) at position q.  SV_EDGE: all of them in two bursts, right behind the programme's LDS requests and
-    // right behind its writes -- while MFMAs execute the SIMD issues one vector instruction per ~4.75 cycles for BOTH its waves instead
-    // of one per wave (tools/probes/coissue_probe.hip: a wave beside an MFMA-issuing partner runs at half rate), so the MFMAs belong
-    // where both waves only wait (LDS round trip, barrier), not between the chunks of the programme
-    static constexpr int slot_lo(int q)
-    {
-        if (SV_EDGE) return q <= 0 ? 0 : (q < NPOS - 1 ? MPS / 2 : (q == NPOS - 1 ? MPS / 2 : MPS));
-        return (q * MPS) / NPOS;
-    }
+    // first MFMA (of the step's MPS) at position q.  (Measured and not kept: all of them in two bursts, right behind the programme's LDS
+    // requests and right behind its writes -- while MFMAs execute the SIMD issues one vector instruction per ~4.75 cycles for BOTH its
+    // waves instead of one per wave (tools/probes/coissue_probe.hip: a wave beside an MFMA-issuing partner runs at half rate).)
+    static constexpr int slot_lo(int q) { return (q * MPS) / NPOS; }
     static constexpr int slot_hi(int q) { return q >= NPOS - 1 ? MPS : slot_lo(q + 1); }
     static constexpr int mf_step(int m) { return m / MPS; }
     static constexpr int fin_step(int n) { return mf_step(3 * KS * (n + 1) - 1) + 1; }
@@ -355,9 +305,6 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef SV_PRIO
-    if (wave >= 4) __builtin_amdgcn_s_setprio(SV_PRIO);
-#endif
     const int c = lane & 31, hch = lane >> 5;
     const int j = 32 * wave + c, q = j >> 2, cc = j & 3;
     const int b0 = NCH * blockIdx.x;
@@ -505,7 +452,7 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
     };
     auto wload = [&](auto pc) __attribute__((always_inline)) {
         constexpr int p = decltype(pc)::value;
-        if constexpr (p < NP && !(SV_ABL & 2)) {
+        if constexpr (p < NP) {
             wfh[p % SV_D] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane, wwave + p * 2048, 0));
             wfl[p % SV_D] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane, wwave + p * 2048 + 1024, 0));
         }
@@ -528,8 +475,7 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
     };
     auto mfma_m = [&](auto mc) __attribute__((always_inline)) {
         constexpr int m = decltype(mc)::value;
-        if constexpr (m < Sched::NMF && !(SV_ABL & 1)) {
-            if constexpr (SV_ABL & 128) { if (wave >= 4) return; }          // (timing only: the MFMAs of one wave half alone)
+        if constexpr (m < Sched::NMF) {
             constexpr int p = m / 3, term = m % 3, n = p / KS;
             constexpr bool zero = (p % KS == 0) && term == 0;
             const half8 a = term == 0 ? al[p] : ah[p];
@@ -623,7 +569,7 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
         for (int i = 0; i < 16; i++) keepf(rst[i]);
     };
     auto reduce_max = [&]() __attribute__((always_inline)) {
-        const float r = (SV_ABL & 16) ? rst[0] + rst[15] : sv_half_reduce16_asm<false>(rst, 0xCCCCCCCCCCCCCCCCull);
+        const float r = sv_half_reduce16_asm<false>(rst, 0xCCCCCCCCCCCCCCCCull);
         if (!(c & 1)) my_max[c >> 1] = r;
     };
     // tile n: exponentials in place, running row sums (the order of round 4's sum: ((t0 + t1) + t2) + t3)
@@ -635,8 +581,8 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
 #pragma unroll
         for (int i = 0; i < 16; i += 2) {
             const f32x2 d = f32x2{acc[n][i], acc[n][i + 1]} - f32x2{m[i], m[i + 1]};
-            acc[n][i] = (SV_ABL & 8) ? d.x : __builtin_amdgcn_exp2f(d.x);
-            acc[n][i + 1] = (SV_ABL & 8) ? d.y : __builtin_amdgcn_exp2f(d.y);
+            acc[n][i] = __builtin_amdgcn_exp2f(d.x);
+            acc[n][i + 1] = __builtin_amdgcn_exp2f(d.y);
         }
 #pragma unroll
         for (int i = 0; i < 16; i += 2) {
@@ -654,7 +600,7 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
         for (int i = 0; i < 16; i++) keepf(rst[i]);
     };
     auto reduce_sum = [&]() __attribute__((always_inline)) {
-        const float r = (SV_ABL & 16) ? rst[0] + rst[15] : sv_half_reduce16_asm<true>(rst, 0xCCCCCCCCCCCCCCCCull);
+        const float r = sv_half_reduce16_asm<true>(rst, 0xCCCCCCCCCCCCCCCCull);
         if (!(c & 1)) my_sum[c >> 1] = r;
     };
     auto row_stats = [&](int nb) __attribute__((always_inline)) {                             // 256 lanes: (half, row) x the eight waves' shares
@@ -683,12 +629,10 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
             if (w == 0) {
                 const float lb = dead ? 0.0f : sv_log(fmaf(e0, inv * one_m, mp_eta));
                 reinterpret_cast<float *>(smem + OFF_LP0)[(nb & 1) * 32 + row] = lb;
-#ifndef SV_DIAG
                 if constexpr (DUMP) {
                     const int t = BS * nb + ri, bb = b0 + hh;
                     if (t < T && bb < B) lp_dump[((size_t)t * B + bb) * (SV_NK + 1)] = lb;
                 }
-#endif
             }
         }
     };
@@ -711,16 +655,12 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
             reduce_sum();
         }
         if constexpr (k == Sched::WFIRST_K) wload_first(ic<0>{}, wload_first);
-        if constexpr (!(SV_ABL & 32)) {
-            if constexpr (k == Sched::ROW_K) {
-                if (wave < 4) row_stats(nb);
-                else prepare_a(nb + 1);
-            }
-            if constexpr (k == Sched::ROW_K + 1) {
-                if (wave < 4) prepare_a(nb + 1);
-            }
-        } else {
-            if constexpr (k == Sched::ROW_K) row_stats(nb);
+        if constexpr (k == Sched::ROW_K) {
+            if (wave < 4) row_stats(nb);
+            else prepare_a(nb + 1);
+        }
+        if constexpr (k == Sched::ROW_K + 1) {
+            if (wave < 4) prepare_a(nb + 1);
         }
     };
 
@@ -757,7 +697,6 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
                      "v_mul_f32 %[l3], %[ln2], %[l3]"
                      : [l0] "=&v"(ln0), [l1] "=&v"(ln1), [l2] "=&v"(ln2), [l3] "=&v"(ln3)
                      : [e0] "v"(e0), [e1] "v"(e1), [e2] "v"(e2), [e3] "v"(e3), [fac] "v"(fac), [mpe] "s"(mp_eta_s), [ln2] "s"(ln2_s));
-#ifndef SV_DIAG
         if constexpr (DUMP) {
             const int bb = b0 + hch;
             if (t < T && bb < B) {
@@ -765,12 +704,11 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
                 dst[0] = ln0; dst[1] = ln1; dst[2] = ln2; dst[3] = ln3;
             }
         }
-#endif
     };
     // one whole step: reads, the step's vector side work, the chunks with the MFMAs between them, writes
     auto step = [&](auto kc, auto dpc, auto prodc, int t0, int par, int nb) __attribute__((always_inline)) {
         constexpr int k = decltype(kc)::value;
-        constexpr bool DP = decltype(dpc)::value && !(SV_ABL & 4), PROD = decltype(prodc)::value;
+        constexpr bool DP = decltype(dpc)::value, PROD = decltype(prodc)::value;
         const int apar = nb & 1;
         [[maybe_unused]] float vs0, vs1, vs2, vs3, vk0, vk1, vk2, vk3, lp0, l0, l1, l2, l3, t0r, t1r, t2r, fac;
         [[maybe_unused]] float ls0, ls1, ls2, ls3;
@@ -796,15 +734,9 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
             l0 = ln0; l1 = ln1; l2 = ln2; l3 = ln3;             // made at the end of the step before (J)
             if constexpr (k == 0) { ls0 = l0; ls1 = l1; ls2 = l2; ls3 = l3; }
         }
-        [[maybe_unused]] const int cb = nb - 1;                 // (SV_STAMP2 names it)
-        if constexpr (k == 14) SV_STAMP2(0);
-        if constexpr (k == 15) SV_STAMP2(4);
         if constexpr (PROD) {
-            if constexpr (SV_ABL & 64) { if (wave < 4) side(kc, nb); }       // (timing only: what the side work costs one wave half alone)
-            else side(kc, nb);
+            side(kc, nb);
         }
-        if constexpr (k == 14) SV_STAMP2(1);
-        if constexpr (k == 15) SV_STAMP2(5);
         // ---- D1 ----
         if constexpr (PROD) { mfma_slot(kc, ic<2>{}, apar); aload_pos(ic<k * Sched::NPOS + 2 + SV_AHEAD>{}, apar); }
         if constexpr (DP)
@@ -910,8 +842,6 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
                          : "memory");
             tbs[((par * NCH + hch) * BS + k) * 256 + j] = (uint8_t)__float_as_uint(l0);
         }
-        if constexpr (k == 14) SV_STAMP2(2);
-        if constexpr (k == 15) SV_STAMP2(6);
         if constexpr (DP) {                                     // J for the next step's row
             if constexpr (k < 15) jit_log(ecur[0][k + 1], ecur[1][k + 1], ecur[2][k + 1], ecur[3][k + 1], fac, t0 + k + 1);
             else if constexpr (PROD) jit_log(acc[0][0], acc[1][0], acc[2][0], acc[3][0], fac, t0 + 16);    // row 0 of the block just finished
@@ -922,8 +852,6 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
             mfma_slot(kc, ic<11>{}, apar);
             aload_pos(ic<k * Sched::NPOS + 11 + SV_AHEAD>{}, apar);
         }
-        if constexpr (k == 14) SV_STAMP2(3);
-        if constexpr (k == 15) SV_STAMP2(7);
     };
     // rows of block blk (staged with parity par) -> HBM: per chunk BS rows of 256 bytes, contiguous on both sides (8 KB: 16 bytes per thread)
     auto flush_tb = [&](int blk, int par) __attribute__((always_inline)) {
@@ -943,7 +871,6 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
     do {                                                                                   \
         step(ic<K>{}, dpc, prodc, t0, par, nb);                                            \
         bar();                                                                             \
-        SV_STAMP(K);                                                                       \
         if constexpr ((K) == Sched::FLUSH_K) {                                             \
             if (DP && cb >= 1) flush_tb(cb - 1, par ^ 1);                                  \
         }                                                                                  \
@@ -1053,12 +980,7 @@ template <int KS>
 static int sv_launch(const float *x, long ldx, int T, int B, const uint8_t *pack, float skip_pen, float min_prob, uint8_t *tb,
                      int32_t *best, float *score_out, const int *lens, float *lp_dump, hipStream_t s)
 {
-#ifdef SV_DIAG
-    constexpr bool diag = true;
-#else
-    constexpr bool diag = false;
-#endif
-    if (lp_dump && !diag)
+    if (lp_dump)
         hipLaunchKernelGGL((softmax_viterbi_kernel<KS, true>), dim3((B + 1) / 2), dim3(SV_THREADS), 0, s, x, ldx, T, B, pack,
                            skip_pen, min_prob, (float)(1.0 - (double)min_prob), tb, best, score_out, lens, lp_dump);
     else
@@ -1107,9 +1029,5 @@ extern "C" int slk_softmax_viterbi_f32(const float *x, long ldx, const void *pac
     default: return SLK_ERR_UNSUPPORTED;
     }
     if (rc != SLK_OK) return rc;
-#ifdef SV_NO_BACKTRACE
-    return rc;
-#else
     return slk_backtrace_packed8(tb, best, T, B, SV_NK, path_out, len_out, lens, s);
-#endif
 }

@@ -25,9 +25,6 @@
 #include "mfma4.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-#ifndef GBWD_DIAG
-#define GBWD_DIAG 0
-#endif
 
 // ---------------------------------------------------------------------------------------------------------------
 // Packed rows for the gate recompute: xh[m] = [x[m] | h_prev[m]], h_prev(t, b) = h at the previous SCAN step (zero at
@@ -308,18 +305,15 @@ __global__ void __launch_bounds__(4 * N + 64) gru_backward_dma_kernel(const floa
             const float daz = g * (h - cc) * z * (1.0f - z);
             v_dac[par][quad][i] = dac;
             v_dzr[par][quad][i] = daz;
-            if (GBWD_DIAG != 1) {
             da[row(s, bq) * (3 * N) + 2 * N + i] = dac;
             da[row(s, bq) * (3 * N) + i] = daz;
-            }
         }
         lds_barrier();                                            // 1: dac visible; ring slot s % D is free again
         float keep = 0.0f;
         if (loader) {
             // step s-1 is read after barrier 2; the D-1 younger steps (5*CH loads each) may stay in flight -- unless
             // fewer than that were issued (the last D steps), where everything is awaited
-            if (GBWD_DIAG == 2) {
-            } else if (s - D >= 0) {
+            if (s - D >= 0) {
                 issue(s - D);
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(5 * CH * (D - 1)) : "memory");
             } else {
@@ -332,7 +326,7 @@ __global__ void __launch_bounds__(4 * N + 64) gru_backward_dma_kernel(const floa
                 const float *vp = &v_dac[par][ch][sl * KA];
                 f32x2 a01 = {0.0f, 0.0f}, a23 = {0.0f, 0.0f};
 #pragma unroll
-                for (int k = 0; k < (GBWD_DIAG == 3 ? 1 : KA); k++) {
+                for (int k = 0; k < KA; k++) {
                     const f32x2 vv = {vp[k], vp[k]};
                     a01 = __builtin_elementwise_fma(vv, wa01[k], a01);
                     a23 = __builtin_elementwise_fma(vv, wa23[k], a23);
@@ -343,10 +337,8 @@ __global__ void __launch_bounds__(4 * N + 64) gru_backward_dma_kernel(const floa
                 const float mine = quad == 0 ? drh[0] : drh[CH - 1];
                 const float dar = mine * h * r * (1.0f - r);
                 v_dzr[par][quad][N + i] = dar;
-                if (GBWD_DIAG != 1) {
-                    da[row(s, bq) * (3 * N) + N + i] = dar;
-                    rh[row(s, bq) * N + i] = r * h;
-                }
+                da[row(s, bq) * (3 * N) + N + i] = dar;
+                rh[row(s, bq) * N + i] = r * h;
                 keep = g * z + mine * r;
             }
         }
@@ -358,7 +350,7 @@ __global__ void __launch_bounds__(4 * N + 64) gru_backward_dma_kernel(const floa
                 const float *vp = &v_dzr[par][ch][sl * KB];
                 f32x2 a01 = {0.0f, 0.0f}, a23 = {0.0f, 0.0f};
 #pragma unroll
-                for (int k = 0; k < (GBWD_DIAG == 3 ? 1 : KB); k++) {
+                for (int k = 0; k < KB; k++) {
                     const f32x2 vv = {vp[k], vp[k]};
                     a01 = __builtin_elementwise_fma(vv, wb01[k], a01);
                     a23 = __builtin_elementwise_fma(vv, wb23[k], a23);
@@ -718,9 +710,6 @@ extern "C" int slk_reduce_rows_sum_f32(const float *x, int nrow, size_t n, doubl
 #define TN_WAVES 2048          /* waves wanted per launch: 256 CUs x 4 SIMDs x 2 */
 #define TN_BLK 96
 #define TN_UNROLL 4
-#ifndef TN_DEAL
-#define TN_DEAL 6              /* vector instructions asked for behind every MFMA of gemm_tn_bf16_kernel */
-#endif
 
 // Which block of C and which slice of rows this workgroup takes.  Workgroups are dealt round-robin over the 8 XCDs (blocks b and
 // b + 8 share one; observed, speed only), each with an L2 of its own, and the g1 * g2 column blocks of ONE slice read the same rows

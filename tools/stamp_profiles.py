@@ -24,6 +24,9 @@ def main():
         if not isinstance(d, dict):
             continue
         d["csrc"] = stamp
+        for ent in d.get("workloads", []):           # a merged table (unit_utilisation.json) also stamps each workload's passes
+            if isinstance(ent, dict) and ent.get("csrc"):
+                ent["csrc"] = stamp
         with open(path, "w") as fh:
             json.dump(d, fh, indent=1)
         print("stamped", path, stamp)
