@@ -737,12 +737,10 @@ extern "C" int slk_gru_bar16q_launch(const float *x, long ldx, const float *iW, 
                                      float *zr_out, hipStream_t s);
 
 // More workgroups of four chunks than CUs would run one after the other: such batches take the eight-chunk plan of
-// gru_bar16d.hip, and the sixteen-chunk plan of gru_bar16q.hip when the eight-chunk workgroups do not fit either
-// (SLOIKA_AMD_GRU_DUAL=0 / 1 / 2 forces four / eight / sixteen chunks).  Returns chunks per workgroup divided by four.
+// gru_bar16d.hip, and the sixteen-chunk plan of gru_bar16q.hip when the eight-chunk workgroups do not fit either (bits 8-9 of
+// `reverse` force a plan per call).  Returns chunks per workgroup divided by four.
 static int bar16_auto_plan(int B)
 {
-    static const int forced = getenv("SLOIKA_AMD_GRU_DUAL") ? atoi(getenv("SLOIKA_AMD_GRU_DUAL")) : -1;
-    if (forced >= 0) return forced == 0 ? 1 : (forced == 1 ? 2 : 4);
     const int ncu = SLK_PER_DEVICE(int, ([] {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;

@@ -21,7 +21,7 @@
 // lo half stays a normal number, i.e. an absolute error of 2^-25 of the BOUND on the smallest entries -- 2^-39+L relative to the
 // largest entry for a bound L bits loose: float32-grade up to L = 15.
 //
-// Per step a lane reads dy, z, r, h_t, h_prev of its unit: asm loads the kernel counts itself (gru_scan16.hip), four steps ahead.
+// Per step a lane reads dy, z, r, h_t, h_prev of its unit: asm loads the kernel counts itself (gru_scan1t.hip), four steps ahead.
 #include <limits.h>
 
 #include "bar16_common.h"

@@ -1,12 +1,14 @@
-// gru_scan1t.hip -- the scan of Gru.step (sloika/layers.py:1010-1021) for wide layers with ONE 16-neuron tile per wave: the plan
-// of gru_scan16.hip (four chunks per workgroup, two s_barrier per step, recurrent products as two fp16-split MFMAs per K block with
-// the state's hi and lo halves in different column groups, the projection vI = x.iW^T + b read from HBM) on n / 16 waves instead of
-// four.  A step is a latency chain; with two tiles per wave both tiles' activations, image writes and stores sit on it one after
-// the other, with one tile per wave two waves share a SIMD and fill each other's waits (csrc/gru_bwd16.hip measured the same
-// trade: 3350 against 2330 cycles per step).  Measured on whole layers (projection + scan, B = 1024, T' = 800): n = 112 1.11-1.19 ms
-// against 1.21-1.28 for gru_scan16.hip, n = 128 1.19-1.22 against 1.23-1.26; `pretrained` architecture 709 -> 740 M samples/s.
+// gru_scan1t.hip -- the scan of Gru.step (sloika/layers.py:1010-1021) for layers too wide for the fused kernels (n = 112 / 128 / 144:
+// models/pretrained.pkl, models/raw_1.00_rGr.py), ONE 16-neuron tile per wave on n / 16 waves: four chunks per workgroup, two
+// s_barrier per step, recurrent products as two fp16-split MFMAs per K block with the state's hi and lo halves in different column
+// groups (bar16_common.h), the projection vI = x.iW^T + b read from HBM (written by the row GEMM) by the lane that needs it.
+// A step is a latency chain; the earlier plan of two tiles on each of four waves put both tiles' activations, image writes and stores
+// on it one after the other, with one tile per wave two waves share a SIMD and fill each other's waits (csrc/gru_bwd16.hip measured
+// the same trade: 3350 against 2330 cycles per step).  Measured on whole layers (projection + scan, B = 1024, T' = 800): n = 112
+// 1.11-1.19 ms against 1.21-1.28 for two tiles per wave, n = 128 1.19-1.22 against 1.23-1.26; `pretrained` architecture 709 -> 740 M
+// samples/s.  Sizes below an instantiation (a multiple of 16) run with zero weights for the missing neurons: their state stays exactly 0.
 // n = 144 is nine waves, three of them on one SIMD: 168 registers each.  As five K blocks of 32 the weights alone are 120 of them
-// (round 3 fetched the candidate's from LDS every step instead: it spilled and ran 2.09 ms against 1.93 for gru_scan16.hip's ninth
+// (round 3 fetched the candidate's from LDS every step instead: it spilled and ran 2.09 ms against 1.93 for the two-tile plan's ninth
 // tile).  Round 5: 144 = four K blocks of 32 and ONE OF 16 -- v_mfma_f32_16x16x16_f16 for neurons 128 .. 143, whose halves the ninth
 // wave writes side by side in the image so that one 8-byte LDS read is the B operand -- 108 registers of weights, no scratch:
 // a 144-wide layer's scan 1.37 -> 0.94 ms (B = 1024, T' = 800, tools/scan_ab.py).
@@ -132,8 +134,11 @@ __global__ void __launch_bounds__(4 * N, 1) gru_scan1t_kernel(const float *__res
     const int Tc = (lens && live) ? min(max(lens[bc], 1), T) : T;
     const long hstep = (reverse ? -1L : 1L) * (long)B * ldh;
     float *hp = h_out + ((size_t)(reverse ? Tc - 1 : 0) * B + bcc) * ldh + (uok ? u0 : 0);
-    // vI of a step: z | r | c blocks of n floats per row; requests run three steps ahead in four register sets (gru_scan16.hip);
-    // steps past the chunk's end re-read its last row
+    // vI of a step: z | r | c blocks of n floats per row; steps past the chunk's end re-read its last row.  Step s uses register set
+    // s % 4 and requests step s + 3 into the set step s - 1 used.  The loads are asm (the compiler would wait for ALL outstanding memory
+    // operations at the first use -- the wave also has stores in flight); loads complete in order among themselves, so once the loads
+    // of the three younger steps are all that may be outstanding, those of the current step have arrived.  The caller refuses
+    // projections of 4 GiB and more (32-bit byte offsets).
     struct VI { float z, r, c; };
     VI vs[4];
     const float *sb_z = vI, *sb_r = vI + n, *sb_c = vI + 2 * n;
@@ -244,6 +249,7 @@ __global__ void __launch_bounds__(4 * N, 1) gru_scan1t_kernel(const float *__res
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // nothing of mine may land in registers after the wave has ended
 }
 
+// One workgroup per CU: ask for enough dynamic LDS that two cannot share a CU.
 template <int N>
 static size_t scan1t_exclusive_lds()
 {
@@ -257,9 +263,8 @@ static size_t scan1t_exclusive_lds()
     return dyn;
 }
 
-// called by slk_gru_scan16_f32 (gru_scan16.hip) for the sizes this plan is the faster one for; same contract
-extern "C" int slk_gru_scan1t_launch(const float *vI, long ldv, const float *sW, const float *sW2, float *y, long ldy, int T, int B, int n,
-                                     int reverse, const int32_t *lens, hipStream_t s)
+static int gru_scan1t_launch(const float *vI, long ldv, const float *sW, const float *sW2, float *y, long ldy, int T, int B, int n,
+                             int reverse, const int32_t *lens, hipStream_t s)
 {
     if (n % 16 || n > 144) return SLK_ERR_UNSUPPORTED;
 #define G1_LAUNCH(NN)                                                                                                        \
@@ -274,4 +279,15 @@ extern "C" int slk_gru_scan1t_launch(const float *vI, long ldv, const float *sW,
     if (n != 144) return SLK_ERR_UNSUPPORTED;              // (the block of 16 of <144> is neurons 128 .. 143)
     G1_LAUNCH(144)
 #undef G1_LAUNCH
+}
+
+// include/sloika_amd.h
+extern "C" int slk_gru_scan16_f32(const float *vI, long ldv, const float *sW, const float *sW2, float *y, long ldy, int T, int B, int n,
+                                  int reverse, int act, int gate_act, const int32_t *lens, slk_stream_t stream)
+{
+    if (!vI || !sW || !sW2 || !y || T < 1 || B < 1 || n < 1 || ldv < 3L * n || ldy < n) return SLK_ERR_INVALID_ARG;
+    if (act != SLK_ACT_TANH || gate_act != SLK_ACT_SIGMOID) return SLK_ERR_UNSUPPORTED;
+    if (n % 16 || n <= 96 || n > 144) return SLK_ERR_UNSUPPORTED;
+    if ((unsigned long long)T * B * ldv * sizeof(float) >= (1ull << 32)) return SLK_ERR_UNSUPPORTED;       // 32-bit lane offsets
+    return gru_scan1t_launch(vI, ldv, sW, sW2, y, ldy, T, B, n, reverse, lens, slk_stream(stream));
 }

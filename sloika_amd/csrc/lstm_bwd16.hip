@@ -12,7 +12,7 @@
 // scan lives in [-1, 1]; these may be 1e-9 or 1e+3), so the image of a step is scaled per chunk by the power of two that brings that
 // chunk's largest |dsum| into [1, 2) -- what the weight rows get once, the operand columns get every step: a max over the wave's
 // lanes of a chunk (two DPP steps and the k-group swap), four floats per wave through LDS and a second barrier.  Per step a lane reads dy, its four activated gates and two
-// cell states; they are requested three steps ahead with asm loads the kernel counts itself (gru_scan16.hip).
+// cell states; they are requested three steps ahead with asm loads the kernel counts itself (gru_scan1t.hip).
 #include <limits.h>
 
 #include "bar16_common.h"

@@ -1,5 +1,5 @@
 // lstm_scan16.hip -- the scan of Lstm.step (sloika/layers.py:677-691, peepholes, interleaved gate rows) on the execution plan of
-// gru_scan16.hip: four waves per workgroup, one per SIMD, four chunks per workgroup, the recurrent products as 3-term fp16 splits
+// gru_bar16.hip: four waves per workgroup, one per SIMD, four chunks per workgroup, the recurrent products as 3-term fp16 splits
 // on v_mfma_f32_16x16x32_f16 with rows scaled by powers of two, the state exchanged as packed hi / lo halves through LDS, a lane
 // owning one (unit, chunk) pair.  The Lstm step has ONE matrix product (h(s-1) against the 4n x n matrix sW) and one exchange, so
 // with the state image double buffered a step is one s_barrier:
@@ -12,7 +12,7 @@
 // in accumulation registers (their MFMAs are asm).  Sizes in between (a multiple of 16) run with zero weights for the missing units:
 // their state stays 0.  Products take two MFMAs each (the state's hi and lo halves in different column groups, bar16_common.h).  The input projection vW = x.iW^T + b comes from HBM (the row GEMM writes it): one 16-byte load per lane and step --
 // the four gate pre-activations of a unit are neighbours (row = 4*unit + gate, layers.py:682-690) -- requested three steps ahead
-// with asm loads the kernel counts itself (gru_scan16.hip).  The cell state of (unit, chunk) never leaves its lane's registers.
+// with asm loads the kernel counts itself (gru_scan1t.hip).  The cell state of (unit, chunk) never leaves its lane's registers.
 //
 // lstm_mfma.hip (float32 MFMA 4x4x1, the SLOIKA_AMD_EXACT_F32 arithmetic) remains the all-fp32 path.
 #include <limits.h>

@@ -119,33 +119,20 @@ def _stream():
     return D.stream_ptr()
 
 
-#: The package has two switches (set in the shell, read once at import):
+#: The package has one switch (set in the shell, read once at import):
 #:   SLOIKA_AMD_EXACT_F32=1    every product in plain float32 MFMA, no fp16 / bf16 splits anywhere: the correctness fallback
 #:                             (two-kernel Gru / Lstm, fp32 softmax projection + decoder on the logits)
-#:   SLOIKA_AMD_DEBUG=a,b,...  comparison runs of one plan against another, never needed for results:
-#:                             recurrent_f32    split projections, but the recurrences in float32 MFMA (csrc/recurrent.hip, lstm_mfma.hip)
-#:                             no_lstm_fused    Lstm as projection GEMM + csrc/lstm_scan16.hip instead of csrc/lstm_fused16.hip
-#:                             no_gru64_share   64-wide Gru layers never two workgroups per CU
-#:                             no_fused_decode  Softmax writes the logits, csrc/decode.hip reads them (pipeline.FUSED_DECODE)
-#:                             bf16_ff_max=N    widest FeedForward output on csrc/gemm_bf16x6.hip
-#:                             xent_in_place    training: logits written, then the loss gradient in place over them (train.hip)
-#:                                              instead of the two passes that never store logits (train.XENT_TWO_PASS)
-_DEBUG = dict((t.partition("=")[0], t.partition("=")[2]) for t in os.environ.get("SLOIKA_AMD_DEBUG", "").split(",") if t)
 #: Time-parallel projections (softmax, and the input projections of recurrent layers that have no fused kernel) run on the
 #: FP16 matrix pipe as a 3-term split of every float32 operand (csrc/gemm_rows_f16x3.hip: float32 accumulation, error a few
-#: float32 ulps, ~5x the fp32-MFMA rate) unless SLOIKA_AMD_EXACT_F32=1.
+#: float32 ulps, ~5x the fp32-MFMA rate) unless SLOIKA_AMD_EXACT_F32=1, and so do the recurrent products (csrc/gru_bar16*.hip,
+#: gru_scan1t.hip, lstm_fused16.hip, lstm_scan16.hip).
 SPLIT_F16 = os.environ.get("SLOIKA_AMD_EXACT_F32", "0") != "1"
-#: ... and so do the recurrent products (csrc/gru_bar16*.hip, gru_scan16.hip, lstm_fused16.hip, lstm_scan16.hip).
-RECURRENT_F16 = "recurrent_f32" not in _DEBUG
 #: widest FeedForward output that takes csrc/gemm_bf16x6.hip (128 -> 64: 0.78 against 1.10 ms, 192 -> 96: 0.29 against 0.39; 192 -> 128
 #: as one 128-column block: 1.69 against 1.72 ms, i.e. no gain, so it stays with the row kernel)
-BF16_FF_MAX = int(_DEBUG.get("bf16_ff_max") or 96)
-#: Gru layers up to 64 wide run their four-chunk workgroups two per CU where one per CU does not hold what is meant to run together (the
-#: directions of a birnn at B = 1024: `baseline_gru` 16.9 -> 14.9 ms per step against the eight-chunk plan on half the chip each)
-GRU64_SHARE = "no_gru64_share" not in _DEBUG
+BF16_FF_MAX = 96
 #: An Lstm layer of up to 64 units and 64 inputs runs as ONE kernel that computes its input projection inside the scan
-#: (csrc/lstm_fused16.hip)
-LSTM_FUSED = "no_lstm_fused" not in _DEBUG
+#: (csrc/lstm_fused16.hip); False: projection GEMM + csrc/lstm_scan16.hip, the plan of the other shapes (tests compare the two)
+LSTM_FUSED = True
 
 
 class _PlanHints(__import__("threading").local):
@@ -178,7 +165,9 @@ def _gru_plan_for(B, share, ncu, per_cu=1):
     (baseline_raw_gru, eight batches of 256 in flight: 520 -> 545 M samples/s).  The four-chunk kernel keeps a CU to itself."""
     if ((B + 3) // 4) * share <= ncu:
         return 0
-    if per_cu == 2 and GRU64_SHARE and ((B + 3) // 4) * share <= 2 * ncu:
+    # two four-chunk workgroups per CU where one per CU does not hold what is meant to run together (the directions of a birnn at
+    # B = 1024: `baseline_gru` 16.9 -> 14.9 ms per step against the eight-chunk plan on half the chip each)
+    if per_cu == 2 and ((B + 3) // 4) * share <= 2 * ncu:
         return 5                   # four chunks per workgroup, two workgroups per CU (bit 2 = bit 10 of `reverse`: may share a CU)
     if ((B + 7) // 8) * share <= ncu * per_cu:
         return 2
@@ -188,7 +177,7 @@ def _gru_plan_for(B, share, ncu, per_cu=1):
 #: (insize, size) of the Gru layers that run as ONE kernel, projection included (the instantiations of csrc/gru_bar16.hip,
 #: gru_bar16d.hip, gru_bar16q.hip: every Gru of models/ up to 96 wide)
 GRU_LAYER_SHAPES = frozenset([(96, 96), (64, 64), (32, 96), (128, 96), (64, 96), (48, 32), (16, 64)])
-#: sizes of the fp16-split scan behind a projection GEMM (csrc/gru_scan1t.hip: 112, 128; gru_scan16.hip: 144)
+#: sizes of the fp16-split scan behind a projection GEMM (csrc/gru_scan1t.hip)
 GRU_SCAN16_SIZES = frozenset([112, 128, 144])
 
 
@@ -201,7 +190,7 @@ def gru_plan(insize, size, fun, gatefun):
       "scan"    projection GEMM + float32-MFMA / portable scan       slk_gru_recurrent_f32, slk_gru_recurrent_ragged_f32
     """
     tanh_sigmoid = fun is activation.tanh and gatefun is activation.sigmoid
-    if SPLIT_F16 and RECURRENT_F16 and tanh_sigmoid:
+    if SPLIT_F16 and tanh_sigmoid:
         if (insize, size) in GRU_LAYER_SHAPES:
             return "layer"
         if size in GRU_SCAN16_SIZES:
@@ -216,12 +205,12 @@ def gru_pad_shape(insize, size, fun, gatefun):
     padded input columns meet zero weights, so the leading `size` outputs are those of the unpadded layer.
       * up to 96 wide with up to 128 inputs: the next shape of the one-kernel plan (GRU_LAYER_SHAPES: smallest width first, then the
         fewest inputs) -- Gru(80, 80) runs as 96 -> 96, Gru(40, 72) as 64 -> 96, Gru(20, 20) as 48 -> 32;
-      * up to 144 wide: the next multiple of 16 (csrc/gru_scan1t.hip / gru_scan16.hip: 112, 128, 144);
+      * up to 144 wide: the next multiple of 16 (csrc/gru_scan1t.hip: 112, 128, 144);
       * sizes that are not multiples of 16 otherwise: the next multiple (the MFMA scan of csrc/recurrent.hip)."""
     if activation.act_name(fun) not in ("tanh", "linear"):
         return insize, size
     tanh_sigmoid = fun is activation.tanh and gatefun is activation.sigmoid
-    if SPLIT_F16 and RECURRENT_F16 and tanh_sigmoid:
+    if SPLIT_F16 and tanh_sigmoid:
         fits = sorted((n, i) for (i, n) in GRU_LAYER_SHAPES if n >= size and i >= insize)
         if fits:
             return fits[0][1], fits[0][0]
@@ -238,7 +227,7 @@ def lstm_plan(insize, size, fun, gatefun):
     """The plan table of an Lstm layer, as gru_plan: "layer" = slk_lstm_fused16_f32 (size and insize up to 64: every Lstm of
     models/), "scan16" = projection GEMM + slk_lstm_scan16_f32, "scan" = projection GEMM + slk_lstm_recurrent*_f32."""
     tanh_sigmoid = fun is activation.tanh and gatefun is activation.sigmoid
-    if SPLIT_F16 and RECURRENT_F16 and tanh_sigmoid and size % 16 == 0:
+    if SPLIT_F16 and tanh_sigmoid and size % 16 == 0:
         if LSTM_FUSED and size <= 64 and insize <= 64 and insize % 4 == 0:
             return "layer"
         if size <= LSTM_SCAN16_MAX:
@@ -1114,7 +1103,7 @@ class Gru(RNN):
                              f16x2_flops=6.0 * rows * n * n if plan == "scan16" else 0.0):
             rc = _lib.SLK_ERR_UNSUPPORTED
             if plan == "scan16":
-                # n = 112 / 128 / 144: the barrier-stepped scan on the fp16 split (csrc/gru_scan16.hip, gru_scan1t.hip; unsupported:
+                # n = 112 / 128 / 144: the barrier-stepped scan on the fp16 split (csrc/gru_scan1t.hip; unsupported:
                 # a projection of 4 GiB or more, its lanes keep 32-bit offsets)
                 rc = L.slk_gru_scan16_f32(ws.data_ptr(), 3 * n, self.sW.dev().data_ptr(), self.sW2.dev().data_ptr(), y.data_ptr(),
                                           _row_stride(y), T, B, n, int(reverse), act, gact, lens_p, _stream())
@@ -1270,7 +1259,7 @@ class Parallel(Layer):
             # time for twice the chunks) may still let the directions share the chip: B = 1024, two directions -> 2 x 128
             grus = all(isinstance(l.layer if isinstance(l, Reverse) else l, Gru) for l in self.layers)
             plan = _gru_plan_for(B, share, ncu, 2 if grus and all(max(l.size, l.insize) <= 64 for l in inners) else 1)
-            if not (grus and SPLIT_F16 and RECURRENT_F16 and plan):
+            if not (grus and SPLIT_F16 and plan):
                 return None
             self._side_plan = plan
         # side streams belong to the stream the caller runs on: batches in flight on different streams must not meet on one

@@ -13,11 +13,6 @@ import numpy as np
 
 from . import _lib, batch, decode, layers
 
-#: decode straight from the Softmax layer's input (csrc/softmax_viterbi.hip: projection, softmax, prepare_post, log and the
-#: Viterbi forward pass in one kernel, the logits never written) where that kernel applies; SLOIKA_AMD_FUSED_DECODE=0 keeps the
-#: projection kernel + decoder pair
-FUSED_DECODE = "no_fused_decode" not in layers._DEBUG
-
 
 class Basecaller(object):
     def __init__(self, network, kmer_len=5, nbase=4, min_prob=1e-5, skip=0.0, normalisation='per-chunk', in_flight=1,
@@ -54,7 +49,10 @@ class Basecaller(object):
         if self.in_flight > 2:
             from . import device as D
             D.want_hw_queues(4 * self.in_flight)
-        self.fused_decode = FUSED_DECODE if fused_decode is None else bool(fused_decode)
+        # fused_decode (None = True): decode straight from the Softmax layer's input (csrc/softmax_viterbi.hip: projection, softmax,
+        # prepare_post, log and the Viterbi forward pass in one kernel, the logits never written) where that kernel applies; False
+        # keeps the projection kernel + decoder pair
+        self.fused_decode = True if fused_decode is None else bool(fused_decode)
         self._ws = decode.ViterbiWorkspace()
         _lib.lib()
         try:                                   # one-time host work that does not belong into the first call (layers._cu_count)

@@ -148,8 +148,9 @@ def _unwrap(layer, rev=False):
     return layer, rev
 
 
-#: the softmax layer's loss gradient from two passes over its products, no logits in memory (csrc/gemm_rows_f16x3.hip)
-XENT_TWO_PASS = "xent_in_place" not in layers._DEBUG
+#: the softmax layer's loss gradient from two passes over its products, no logits in memory (csrc/gemm_rows_f16x3.hip); False:
+#: logits written, then the loss gradient in place over them (csrc/train.hip), the plan of the other shapes (tests compare the two)
+XENT_TWO_PASS = True
 _FF_ACTS = ("linear", "tanh", "sigmoid", "relu", "elu")     # activations whose derivative is a function of the output
 
 
@@ -573,21 +574,20 @@ class TrainingStep(object):
         y = hbuf[1:T + 1]
         zr = torch.empty((T * B, 2 * n), dtype=torch.float32, device=x.device)
         M = T * B
-        rc = _lib.SLK_ERR_UNSUPPORTED
-        if layers.RECURRENT_F16:            # projection and recurrence as fp16 splits (csrc/gru_bar16.hip)
-            # (as layers.Gru.run prices it: the projection three fp16 MFMAs per product, the recurrent products two up to eight chunks
-            #  per workgroup -- training batches of up to 2048 chunks on 256 CUs -- and three on the sixteen-chunk plan)
-            two_term_fw = (B + 7) // 8 <= layers._cu_count(x.device)
-            with profiler.region("gru_fused", 6.0 * M * n * (n + layer.insize), 4.0 * M * (layer.insize + 3 * n),
-                                 f16x3_flops=6.0 * M * n * (layer.insize if two_term_fw else n + layer.insize),
-                                 f16x2_flops=6.0 * M * n * n if two_term_fw else 0.0) as reg:
-                rc = layers.gru_f16_entry()(x.data_ptr(), layers._row_stride(x), layer.iW.dev().data_ptr(),
-                                            layer.sW.dev().data_ptr(), layer.sW2.dev().data_ptr(),
-                                            layer.b.dev().data_ptr(), y.data_ptr(), n, T, B, layer.insize, n, int(rev),
-                                            activation.act_id(layer.fun), activation.act_id(layer.gatefun), None,
-                                            zr.data_ptr(), layers._stream())
-                if rc == _lib.SLK_ERR_UNSUPPORTED and reg is not None:
-                    reg.cancel()
+        # projection and recurrence as fp16 splits (csrc/gru_bar16.hip)
+        # (as layers.Gru.run prices it: the projection three fp16 MFMAs per product, the recurrent products two up to eight chunks
+        #  per workgroup -- training batches of up to 2048 chunks on 256 CUs -- and three on the sixteen-chunk plan)
+        two_term_fw = (B + 7) // 8 <= layers._cu_count(x.device)
+        with profiler.region("gru_fused", 6.0 * M * n * (n + layer.insize), 4.0 * M * (layer.insize + 3 * n),
+                             f16x3_flops=6.0 * M * n * (layer.insize if two_term_fw else n + layer.insize),
+                             f16x2_flops=6.0 * M * n * n if two_term_fw else 0.0) as reg:
+            rc = layers.gru_f16_entry()(x.data_ptr(), layers._row_stride(x), layer.iW.dev().data_ptr(),
+                                        layer.sW.dev().data_ptr(), layer.sW2.dev().data_ptr(),
+                                        layer.b.dev().data_ptr(), y.data_ptr(), n, T, B, layer.insize, n, int(rev),
+                                        activation.act_id(layer.fun), activation.act_id(layer.gatefun), None,
+                                        zr.data_ptr(), layers._stream())
+            if rc == _lib.SLK_ERR_UNSUPPORTED and reg is not None:
+                reg.cancel()
         if rc == _lib.SLK_ERR_UNSUPPORTED:
             return None
         _lib.check(rc, "gru_fused_train")
@@ -659,12 +659,12 @@ class TrainingStep(object):
         rh = torch.empty((M, n), dtype=torch.float32, device=dev)
         # gru_bwd16_kernel issues TWO fp16 MFMAs per product (v_mfma_f32_16x16x32_f16, hi and lo halves of the operand in different
         # column groups): the region says so, and bench.py prices it on the fp16 pipe at two instructions per product
-        two_term = layers.SPLIT_F16 and layers.RECURRENT_F16
+        two_term = layers.SPLIT_F16
         # dL/dx out of the scan itself (csrc/gru_bwd16.hip, DX: the operand images of a step are da of that step, so the product costs the
         # pass 18 MFMAs per wave and step and no second reading of da) -- unless the layer below hands its activation's derivative to the
         # product's epilogue (slk_gemm_dact_bf16x6), which the separate GEMM keeps
         dx = None
-        if need_dx and two_term and "no_scan_dx" not in layers._DEBUG:
+        if need_dx and two_term:
             # the layer below's activation (a Convolution / FeedForward layer whose OUTPUT is the very tensor this Gru consumed: same
             # memory, rows a uniform distance apart -- the condition of the separate product's fused form further down)
             yb_ptr, ldyb, dact = None, 0, 0
@@ -694,7 +694,7 @@ class TrainingStep(object):
             rc = _lib.SLK_OK if dx is not None else _lib.SLK_ERR_UNSUPPORTED
             if dx is not None and reg_scan is not None:
                 reg_scan.cancel()
-            if dx is None and layers.SPLIT_F16 and layers.RECURRENT_F16:     # the two products of a step as fp16 splits (csrc/gru_bwd16.hip: n <= 128)
+            if dx is None and layers.SPLIT_F16:     # the two products of a step as fp16 splits (csrc/gru_bwd16.hip: n <= 128)
                 rc = L.slk_gru_backward16_f32(dy.data_ptr(), layers._row_stride(dy), hp_ptr, ldhp, zr.data_ptr(),
                                               h.data_ptr(), layers._row_stride(h), sW.data_ptr(), sW2.data_ptr(), da.data_ptr(),
                                               rh.data_ptr(), T, B, n, int(rev), act, gact, st())
@@ -805,7 +805,7 @@ class TrainingStep(object):
         dpeep = torch.empty((B, 3 * n), dtype=torch.float32, device=dev)
         with profiler.region("train_lstm_scan", 8.0 * M * n * n, 4.0 * M * 10 * n):
             rc = _lib.SLK_ERR_UNSUPPORTED
-            if layers.SPLIT_F16 and layers.RECURRENT_F16:     # the product of a step as an fp16 split (csrc/lstm_bwd16.hip: n <= 64)
+            if layers.SPLIT_F16:     # the product of a step as an fp16 split (csrc/lstm_bwd16.hip: n <= 64)
                 rc = L.slk_lstm_backward16_f32(dy.data_ptr(), layers._row_stride(dy), gates.data_ptr(), cell.data_ptr(),
                                                sW.data_ptr(), peep, dsum.data_ptr(), dpeep.data_ptr(), T, B, n, int(rev), act, gact,
                                                st())

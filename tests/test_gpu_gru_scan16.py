@@ -1,5 +1,5 @@
-"""csrc/gru_scan16.hip -- the Gru scan for layers too wide for the fused kernels (n = 112 / 128 / 144: models/pretrained.pkl,
-raw_1.00_rGr zero-padded) on the barrier-stepped fp16-split plan -- through the C ABI, against the oracle (float32 C port,
+"""slk_gru_scan16_f32 (csrc/gru_scan1t.hip) -- the Gru scan for layers too wide for the fused kernels (n = 112 / 128 / 144:
+models/pretrained.pkl, raw_1.00_rGr zero-padded) on the barrier-stepped fp16-split plan -- through the C ABI, against the oracle (float32 C port,
 itself pinned to the reference's layers.py by tests/test_oracle_reference_layers.py)."""
 import numpy as np
 import pytest

@@ -1,5 +1,5 @@
 """Scan gfx950 ISA (hipcc --cuda-device-only -S) for registers that an asm-issued global load is still filling when another
-instruction reads them: csrc/gru_scan16.hip requests the projection of later steps with global_load_dword written as asm (the
+instruction reads them: csrc/gru_scan1t.hip requests the projection of later steps with global_load_dword written as asm (the
 compiler does not track them; the kernel counts them with s_waitcnt vmcnt(n) itself).  Under register pressure hipcc copied such
 a destination to an accumulation register right after the load was ISSUED -- before the data arrived -- and every output became
 NaN.  The loads in question use the `vaddr, s[base]` form, which the compiler's own loads in that file do not.

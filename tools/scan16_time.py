@@ -1,4 +1,4 @@
-"""Launch time of csrc/gru_scan16.hip (and of the fp32 recurrence kernel it replaces) for n = 112 / 128 at T = 800."""
+"""Launch time of slk_gru_scan16_f32 (csrc/gru_scan1t.hip) and of the fp32 recurrence kernel it replaces for n = 112 / 128 at T = 800."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

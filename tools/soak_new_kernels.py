@@ -1,5 +1,6 @@
-"""Race screen for the kernels added at the end of round 2 (csrc/gru_bar16d.hip, csrc/gru_bar16q.hip, csrc/gru_scan16.hip): many launches of the same
-inputs -- full-size batches, ragged lengths, both directions, saved gates -- must all reproduce the first one bit for bit."""
+"""Race screen for the kernels added at the end of round 2 (csrc/gru_bar16d.hip, csrc/gru_bar16q.hip) and the wide Gru scan
+(slk_gru_scan16_f32, csrc/gru_scan1t.hip): many launches of the same inputs -- full-size batches, ragged lengths, both directions,
+saved gates -- must all reproduce the first one bit for bit."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
