@@ -116,6 +116,16 @@ SLK_API int slk_pack_reads_f32(const float *src, const int64_t *start, const int
                        slk_stream_t stream);
 SLK_API int slk_reads_nonfinite_f32(const float *src, const int64_t *start, const int32_t *len, int nread, int max_len, int32_t *flags,
                             slk_stream_t stream);
+/* int16 ADC samples -> float32 picoamperes on the device, what sloika/basecall.py:105 (fast5 get_read(raw=True)) and the float32 cast of
+ * the float flows do on the host: (float)(((double)adc + offset[r]) * scale[r]), a double add, a double multiply and one round to
+ * float -- bit for bit numpy's ((adc.astype(float64) + offset) * (range / digitisation)).astype(float32) when the caller computes
+ * scale[r] = (double)range / (double)digitisation.  Read r: src[start[r] .. start[r] + len[r]) -> dst at the same indices, and
+ * dst[start[r] + len[r] .. start[r] + stride[r]) = +0.0f (len[r] <= stride[r]); nothing else is written.  flags (nullable, zeroed by the
+ * caller): flags[r] |= 1 when an output sample of read r is not finite (slk_reads_nonfinite_f32's check, in the same pass).  All arrays
+ * are device arrays of nread entries; max_stride >= every stride[r] sizes the grid.  Any nread and any start (a start that leaves the
+ * input and output offsets unequal mod 4 samples takes a scalar path).                                                              */
+SLK_API int slk_adc_to_pa_i16(const int16_t *src, const int64_t *start, const int32_t *len, const int32_t *stride, const double *offset,
+                              const double *scale, int nread, int max_stride, float *dst, int32_t *flags, slk_stream_t stream);
 /* batch.trim_open_pore(signal, max_op_fraction=0) + util.trim_array for every read of an uploaded set, without a round trip to the host
  * (sloika/batch.py:194-220 with the CLI's default fraction, bin/basecall_network.py:71: np.percentile(., 0) is the minimum; then
  * sloika/basecall.py:111-112).  spread: the per-window spreads of ALL reads (MAD or std of every `window` samples, as

@@ -165,7 +165,16 @@ def upload_reads_windowed(signals, window_size=100):
             hv[off[r]: off[r] + lens[r]] = signals[r]
             hv[off[r] + lens[r]: off[r + 1]] = 0.0
 
-    n = len(signals)
+    _pack_set(pack, off, len(signals))
+    dev = st.buf[:total].to(D.device(), non_blocking=True)
+    st.event = torch.cuda.Event()
+    st.event.record()
+    return dev, off, lens
+
+
+def _pack_set(pack, off, n):
+    """pack(lo, hi) for the reads lo .. hi of a set laid out at offsets `off` (n + 1 entries), on several host threads when it is big."""
+    total = int(off[-1])
     if total >= (1 << 24) and n >= 16:
         # a gigabyte of samples is a tenth of a second of memcpy on one core; numpy's copies release the interpreter lock
         import concurrent.futures
@@ -176,10 +185,155 @@ def upload_reads_windowed(signals, window_size=100):
             list(ex.map(lambda a: pack(*a), [(edges[k], edges[k + 1]) for k in range(nthr) if edges[k + 1] > edges[k]]))
     else:
         pack(0, n)
-    dev = st.buf[:total].to(D.device(), non_blocking=True)
+
+
+_staging16 = _Staging()              # int16 twin of _staging (upload_adc_windowed, the int16 streamed flow)
+
+
+def staging16(total):
+    """This host thread's pinned int16 staging buffer, at least `total` samples (grow-only), once the last upload out of it has left."""
+    import torch
+    st = _staging16
+    if getattr(st, "buf", None) is None or st.buf.numel() < total:
+        st.buf = torch.empty(max(total, 1 << 20), dtype=torch.int16).pin_memory()
+        st.event = None
+    if st.event is not None:
+        st.event.synchronize()
+    return st
+
+
+def upload_adc_windowed(signals, offset, scale, window_size=100, return_nonfinite=False):
+    """upload_reads_windowed for int16 ADC reads and their scaling (adc_scaling): the samples go to the device as they are (2 B each,
+    a memcpy into pinned memory, one upload) and slk_adc_to_pa_i16 writes the picoamperes into the same (dev float32, off, lengths)
+    layout -- bit for bit what upload_reads_windowed gives on the float64 reads fast5.Fast5.get_read() returns.  With return_nonfinite
+    also the reads_nonfinite answer (the kernel's flags, no second pass): -> (dev, off, lengths, bad)."""
+    import torch
+    from . import device as D
+    dev = D.device()
+    lens = [len(s) for s in signals]
+    strides = [-(-n // window_size) * window_size for n in lens]
+    off = np.concatenate([[0], np.cumsum(strides)]).astype(np.int64)
+    total, n = int(off[-1]), len(signals)
+    st = staging16(total)
+    hv = st.buf.numpy()
+
+    def pack(lo, hi):
+        for r in range(lo, hi):
+            hv[off[r]: off[r] + lens[r]] = signals[r]          # (no zero fill: the kernel writes the pad)
+
+    _pack_set(pack, off, n)
+    src = st.buf[:total].to(dev, non_blocking=True)
     st.event = torch.cuda.Event()
     st.event.record()
-    return dev, off, lens
+    out = torch.empty((total,), dtype=torch.float32, device=dev)
+    flags = torch.zeros((n,), dtype=torch.int32, device=dev)
+    if n:
+        meta = _adc_meta(off[:n], lens, strides, offset, scale, dev)
+        adc_to_pa(src, *meta, out, flags, max(strides))
+    if return_nonfinite:
+        return out, off, lens, flags.cpu().numpy() != 0
+    return out, off, lens
+
+
+def adc_chunks_to_pa(adc, scaling):
+    """[n, L] int16 ADC chunks (host array or device tensor) and one scaling per row (adc_scaling) -> [n, L] float32 picoamperes on the
+    device, out of the active arena when there is one (Basecaller(borrow=True))."""
+    import torch
+    from . import device as D
+    if isinstance(adc, torch.Tensor) and not adc.is_cuda:
+        adc = adc.numpy()
+    offset, scale = adc_scaling(adc, scaling)
+    dev = D.device()
+    n, length = (int(v) for v in adc.shape)
+    if isinstance(adc, torch.Tensor):
+        src = adc.to(dev).contiguous()
+    else:
+        src = D.scratch((n, length), torch.int16, dev)
+        src.copy_(torch.from_numpy(np.ascontiguousarray(adc)))
+    out = D.scratch((n, length), torch.float32, dev)
+    if n and length:
+        ln = np.full(n, length, dtype=np.int32)
+        adc_to_pa(src, *_adc_meta(np.arange(n, dtype=np.int64) * length, ln, ln, offset, scale, dev), out, None, length)
+    return out
+
+
+def adc_scaling(signals, scaling):
+    """The per-read (or per-row) scaling of int16 ADC samples as the float64 arrays slk_adc_to_pa_i16 takes: -> (offset [n], scale [n]),
+    scale = range / digitisation in float64, in the order of fast5.Fast5.get_read (sloika/basecall.py:105).
+
+    signals: a list of 1-D int16 numpy arrays (reads) or one [n, L] int16 numpy array or device tensor (chunks): n rows.
+    scaling: n (offset, range, digitisation) triples, an [n, 3] array in that order, or n Fast5.channel_meta dicts.
+    Raises TypeError when a signal is not int16 of the right rank, ValueError when the counts or the shape of `scaling` disagree.
+    Host only: nothing here touches a device."""
+    try:
+        import torch
+        tensor = isinstance(signals, torch.Tensor)
+    except ImportError:
+        tensor = False
+    if tensor:
+        if signals.dtype != torch.int16 or signals.dim() != 2:
+            raise TypeError("int16 ADC chunks must be a [n, L] int16 array, got %s %s" % (signals.dtype, tuple(signals.shape)))
+        n = int(signals.shape[0])
+    elif isinstance(signals, np.ndarray):
+        if signals.dtype != np.int16 or signals.ndim != 2:
+            raise TypeError("int16 ADC chunks must be a [n, L] int16 array, got %s %s" % (signals.dtype, signals.shape))
+        n = signals.shape[0]
+    else:
+        for r, s in enumerate(signals):
+            if not isinstance(s, np.ndarray) or s.dtype != np.int16 or s.ndim != 1:
+                raise TypeError("read %d: scaling= needs 1-D int16 ADC samples, got %s" %
+                                (r, "%s %s" % (s.dtype, s.shape) if isinstance(s, np.ndarray) else type(s).__name__))
+        n = len(signals)
+    if isinstance(scaling, np.ndarray):
+        trip = np.asarray(scaling, dtype=np.float64)
+        if trip.ndim != 2 or trip.shape[1] != 3:
+            raise ValueError("scaling must be [n, 3] (offset, range, digitisation), got shape %s" % (scaling.shape,))
+    else:
+        rows = []
+        for m in scaling:
+            if isinstance(m, dict):
+                rows.append((float(m["offset"]), float(m["range"]), float(m["digitisation"])))
+            else:
+                if len(m) != 3:
+                    raise ValueError("a scaling triple is (offset, range, digitisation), got %r" % (m,))
+                rows.append(tuple(float(v) for v in m))
+        trip = np.asarray(rows, dtype=np.float64).reshape(-1, 3)
+    if trip.shape[0] != n:
+        raise ValueError("%d signals but %d scaling entries" % (n, trip.shape[0]))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        scale = trip[:, 1] / trip[:, 2]              # IEEE double division: float(range) / float(digitisation); 0 -> inf (flagged)
+    return np.ascontiguousarray(trip[:, 0]), np.ascontiguousarray(scale)
+
+
+def _adc_meta(start, lens, strides, offset, scale, dev):
+    """slk_adc_to_pa_i16's per-read arrays on the device in ONE upload (through pinned memory; the device buffer comes out of the active
+    arena when there is one).  -> (start int64, len int32, stride int32, offset float64, scale float64) device tensors."""
+    import torch
+    from . import device as D
+    n = len(lens)
+    host = torch.empty((32 * n,), dtype=torch.uint8).pin_memory()
+    hv = host.numpy()
+    hv[:8 * n].view(np.int64)[:] = start
+    hv[8 * n:16 * n].view(np.float64)[:] = offset
+    hv[16 * n:24 * n].view(np.float64)[:] = scale
+    hv[24 * n:28 * n].view(np.int32)[:] = lens
+    hv[28 * n:].view(np.int32)[:] = strides
+    d = D.scratch((32 * n,), torch.uint8, dev)
+    d.copy_(host, non_blocking=True)
+    return (d[:8 * n].view(torch.int64), d[24 * n:28 * n].view(torch.int32), d[28 * n:].view(torch.int32),
+            d[8 * n:16 * n].view(torch.float64), d[16 * n:24 * n].view(torch.float64))
+
+
+def adc_to_pa(adc, start, lens, strides, offset, scale, out, flags, max_stride):
+    """slk_adc_to_pa_i16 on device tensors: int16 `adc` -> float32 `out` (int64 start, int32 lens / strides, float64 offset / scale, flags
+    int32 or None; max_stride >= every stride)."""
+    from . import device as D
+    with profiler.region("adc_to_pa", 0.0, 6.0 * out.numel()):
+        rc = _lib.lib().slk_adc_to_pa_i16(adc.data_ptr(), start.data_ptr(), lens.data_ptr(), strides.data_ptr(), offset.data_ptr(),
+                                           scale.data_ptr(), int(lens.shape[0]), int(max_stride), out.data_ptr(), D.ptr(flags),
+                                           D.stream_ptr())
+    _lib.check(rc, "adc_to_pa")
+    return out
 
 
 def open_pore_bounds_many(dev, off, lens, max_op_fraction=0.3, var_method='mad', window_size=100):

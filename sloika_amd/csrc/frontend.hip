@@ -511,6 +511,94 @@ extern "C" int slk_reads_nonfinite_f32(const float *src, const int64_t *start, c
     return slk_launch_status();
 }
 
+// ---- int16 ADC samples -> float32 picoamperes on the device (sloika/basecall.py:105, fast5 get_read(raw=True)): numpy's
+// ---- (adc.astype(float64) + offset) * (range / digitisation), then the float32 cast the float flows make.  2 B in, 4 B out per sample.
+// Samples on x, reads on y (pack_reads_kernel's layout).  A lane owns one UNIT of four consecutive samples: unit 0 is the head in front of
+// the first 16-B aligned output sample (0-3 samples), unit u >= 1 starts at head + 4 (u - 1).  A unit that lies inside the read is one
+// 8-B load and one 16-B store; the units at the read's end and every unit of a read whose input and output cannot both be aligned
+// (input and output offsets that differ mod 4 samples) go sample by sample.
+__device__ __forceinline__ float adc_to_pa(int16_t a, double off, double sc)
+{
+    return (float)(((double)a + off) * sc);       // -ffp-contract=off: a double add, a double multiply, one round to float
+}
+
+__device__ __forceinline__ bool nonfinite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+
+__global__ void __launch_bounds__(256) adc_to_pa_kernel(const int16_t *__restrict__ src, const long long *__restrict__ start,
+                                                        const int *__restrict__ len, const int *__restrict__ stride,
+                                                        const double *__restrict__ offset, const double *__restrict__ scale,
+                                                        float *__restrict__ dst, int *__restrict__ flags)
+{
+    const int r = blockIdx.y;
+    const long long s0 = start[r];
+    const int st = max(stride[r], 0);
+    const int n = min(max(len[r], 0), st);
+    const double off = offset[r], sc = scale[r];
+    const int16_t *s = src + s0;
+    float *d = dst + s0;
+    // output samples in front of the first 16-B boundary; the vector units need the input at an 8-B boundary there as well
+    int head = (int)((-(long long)(reinterpret_cast<uintptr_t>(d) >> 2)) & 3);
+    const bool vec = (reinterpret_cast<uintptr_t>(d) & 3) == 0 && (reinterpret_cast<uintptr_t>(s + head) & 7) == 0;
+    if (!vec) head = 0;
+    head = min(head, st);
+    const int nunit = 1 + (st - head + 3) / 4;
+    bool bad = false;
+    for (int u0 = blockIdx.x * 1024; u0 < nunit; u0 += gridDim.x * 1024) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int u = u0 + 256 * k + threadIdx.x;
+            if (u >= nunit) continue;
+            const int j0 = u == 0 ? 0 : head + 4 * (u - 1);
+            const int j1 = u == 0 ? head : min(j0 + 4, st);
+            if (vec && u > 0 && j0 + 4 <= n) {
+                const s16x4 a = *reinterpret_cast<const s16x4 *>(s + j0);
+                f32x4 v;
+                v.x = adc_to_pa(a.x, off, sc);
+                v.y = adc_to_pa(a.y, off, sc);
+                v.z = adc_to_pa(a.z, off, sc);
+                v.w = adc_to_pa(a.w, off, sc);
+                bad |= nonfinite_f32(v.x);
+                bad |= nonfinite_f32(v.y);
+                bad |= nonfinite_f32(v.z);
+                bad |= nonfinite_f32(v.w);
+                *reinterpret_cast<f32x4 *>(d + j0) = v;
+            } else if (vec && u > 0 && j0 >= n && j0 + 4 <= st) {
+                *reinterpret_cast<f32x4 *>(d + j0) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            } else {
+                for (int j = j0; j < j1; j++) {
+                    float v = 0.0f;                       // the pad is +0.0, as the float flows' zero fill, not (0 + offset) * scale
+                    if (j < n) {
+                        v = adc_to_pa(s[j], off, sc);
+                        bad |= nonfinite_f32(v);
+                    }
+                    d[j] = v;
+                }
+            }
+        }
+    }
+    if (flags && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(&flags[r], 1);
+}
+
+extern "C" int slk_adc_to_pa_i16(const int16_t *src, const int64_t *start, const int32_t *len, const int32_t *stride, const double *offset,
+                                 const double *scale, int nread, int max_stride, float *dst, int32_t *flags, slk_stream_t stream)
+{
+    if (!src || !start || !len || !stride || !offset || !scale || !dst || nread < 0 || max_stride < 0) return SLK_ERR_INVALID_ARG;
+    if (nread == 0) return SLK_OK;
+    // 1024 units (4096 samples) per workgroup and pass; the loop over x covers a stride beyond max_stride as well
+    const unsigned gx = (unsigned)max(1, (max_stride / 4 + 2 + 1023) / 1024);
+    for (int lo = 0; lo < nread; lo += 65535) {         // the grid's y limit
+        const int nr = min(65535, nread - lo);
+        hipLaunchKernelGGL(adc_to_pa_kernel, dim3(gx, nr), dim3(256), 0, slk_stream(stream), src,
+                           reinterpret_cast<const long long *>(start) + lo, len + lo, stride + lo, offset + lo, scale + lo, dst,
+                           flags ? flags + lo : nullptr);
+        const int rc = slk_launch_status();
+        if (rc != SLK_OK) return rc;
+    }
+    return SLK_OK;
+}
+
 // batch.trim_open_pore with max_op_fraction 0 (the CLI's default, bin/basecall_network.py:71) for every read of an uploaded set, on the
 // device: np.percentile(spread, 0) is the minimum, the read runs from its first to its last window livelier than that (batch.py:213-220),
 // then util.trim_array takes `trim0` / `trim1` samples off the ends (basecall.py:111-112).  One wave per read (a read has a few hundred to

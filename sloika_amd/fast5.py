@@ -347,6 +347,12 @@ class Fast5(object):
         m = self.channel_meta
         return (adc.astype(np.float64) + float(m["offset"])) * (float(m["range"]) / float(m["digitisation"]))
 
+    def scaling(self):
+        """(offset, range, digitisation) of the read's channel as Python floats: get_read(scale=False) with these is the int16 twin of
+        get_read() (pipeline.Basecaller's `scaling=` takes one such triple per read and scales on the device)."""
+        m = self.channel_meta
+        return float(m["offset"]), float(m["range"]), float(m["digitisation"])
+
     def read_attrs(self):
         return dict(self._read_group().attrs)
 

@@ -62,10 +62,11 @@ class Basecaller(object):
         except (ImportError, RuntimeError):
             pass
 
-    def _hidden(self, chunks, upto):
-        """Run the network on [B, chunk_len] device signal up to (not including) layer index `upto`."""
+    def _hidden(self, chunks, upto, scaling=None):
+        """Run the network on [B, chunk_len] device signal up to (not including) layer index `upto`.  With `scaling`, `chunks` are int16
+        ADC samples with one (offset, range, digitisation) per row (batch.adc_scaling), scaled to picoamperes on the device first."""
         from . import device as D
-        cd = D.to_dev(chunks)
+        cd = D.to_dev(chunks) if scaling is None else batch.adc_chunks_to_pa(chunks, scaling)
         net = self.network
         seq = net.layers if isinstance(net, layers.Serial) else [net]
         first = seq[0]
@@ -97,11 +98,11 @@ class Basecaller(object):
             layers._HINTS.in_flight, layers._HINTS.deterministic = keep
         return x
 
-    def posteriors(self, chunks):
-        """[B, chunk_len] device signal -> [T', B, nstate] posteriors (network layout)."""
+    def posteriors(self, chunks, scaling=None):
+        """[B, chunk_len] device signal -> [T', B, nstate] posteriors (network layout).  `scaling`: as in call_chunks."""
         net = self.network
         n = len(net.layers) if isinstance(net, layers.Serial) else 1
-        return self._hidden(chunks, n)
+        return self._hidden(chunks, n, scaling)
 
     #: row widths csrc/softmax_viterbi.hip is instantiated for; any narrower Softmax input is decoded from rows with zero columns up to
     #: the next of them (free when the rows come out of a zero-padded Gru twin, otherwise one padded copy of the hidden state: 0.3 ms
@@ -132,8 +133,13 @@ class Basecaller(object):
         wide[:, :, :last.insize] = hid
         return pack, wide
 
-    def call_chunks(self, chunks, lp_dump=None):
+    def call_chunks(self, chunks, lp_dump=None, scaling=None):
         """-> device tensors (scores float32 [B], paths int32 [B, T'] (-1 padded), lens int32 [B]).
+
+        scaling: None (the default) takes `chunks` as they are (picoamperes; any other dtype is cast to float32).  Otherwise `chunks` are
+        [B, L] int16 ADC samples (host array or device tensor) and `scaling` one (offset, range, digitisation) per row -- triples, an
+        [B, 3] array or fast5 channel_meta dicts (batch.adc_scaling): slk_adc_to_pa_i16 scales them on the device, bit for bit what the
+        float32 cast of fast5.Fast5.get_read()'s float64 picoamperes gives.
 
         When the network ends in a Softmax layer whose shape csrc/softmax_viterbi.hip covers, the decoder starts from that
         layer's INPUT and neither the logits nor the posterior (3.4 GB each at B=1024) are ever written; `lp_dump`, a float32
@@ -141,15 +147,15 @@ class Basecaller(object):
         (and with fused_decode=False) the decoder consumes the layer's logits + row statistics, bit-identical to decoding
         `posteriors()`."""
         if self._arena is None:
-            return self._call_chunks(chunks, lp_dump)
+            return self._call_chunks(chunks, lp_dump, scaling)
         with self._arena:
-            return self._call_chunks(chunks, lp_dump)
+            return self._call_chunks(chunks, lp_dump, scaling)
 
-    def _call_chunks(self, chunks, lp_dump):
+    def _call_chunks(self, chunks, lp_dump, scaling):
         net = self.network
         last = net.layers[-1] if isinstance(net, layers.Serial) else None
         if type(last) is layers.Softmax and len(net.layers) > 1:
-            hid = self._hidden(chunks, len(net.layers) - 1)
+            hid = self._hidden(chunks, len(net.layers) - 1, scaling)
             packed = self._fused_pack(last, hid)
             if packed is not None:
                 return decode.viterbi_fused_batch(packed[1], packed[0], self.kmer_len, skip_pen=self.skip, nbase=self.nbase,
@@ -160,7 +166,7 @@ class Basecaller(object):
             T, B = hid.shape[0], hid.shape[1]
             return decode.viterbi_logits_batch(logits, stats, self.kmer_len, T, B, ld=ld, skip_pen=self.skip,
                                                nbase=self.nbase, min_prob=self.min_prob, workspace=self._ws)
-        post = self.posteriors(chunks)
+        post = self.posteriors(chunks, scaling)
         return decode.viterbi_batch(post, self.kmer_len, skip_pen=self.skip, nbase=self.nbase,
                                     min_prob=self.min_prob, workspace=self._ws)
 
@@ -178,7 +184,8 @@ class Basecaller(object):
         """A stream of batches with `in_flight` of them on the device at a time: generator over `batches` (an iterable of [B, chunk_len]
         signal batches -- device tensors, or host arrays that are uploaded -- or [T, B, features] tensors for event models), yielding
         (scores float32 [B], paths int32 [B, T'] (-1 padded), lens int32 [B]) as numpy arrays ON THE HOST, one per batch, in the order
-        of the input.
+        of the input.  A batch may also be an (adc, scaling) pair: [B, L] int16 ADC samples (host array or device tensor) and one scaling per
+        row, as call_chunks(adc, scaling=scaling) takes them; such batches and float batches may follow each other in one stream.
 
         What the reference does with a pool of worker processes (bin/basecall_network.py:100-104, one read per call) a GPU does with
         batches side by side: at the north star's batch of 256 chunks one batch fills 64 of 256 CUs, so several must run at once.  The
@@ -216,17 +223,19 @@ class Basecaller(object):
             sc, pa, le = bufs[0][:B].numpy(), bufs[1][:B, :T].numpy(), bufs[2][:B].numpy()
             return (sc.copy(), pa.copy(), le.copy()) if copy else (sc, pa, le)
 
-        for i, chunks in enumerate(batches):
+        for i, item in enumerate(batches):
+            chunks, scaling = item if isinstance(item, tuple) and len(item) == 2 else (item, None)
             k = i % nslot
             before = pending[k]                            # batch i - in_flight: handed out once batch i is queued behind it
             cur = torch.cuda.current_stream()
             s = streams[k]
             s.wait_stream(cur)                             # (whatever produced the batch on the caller's stream)
             with torch.cuda.stream(s):
-                cd = D.to_dev(chunks)
+                # (int16 batches go to the device inside the call, out of the slot's arena)
+                cd = D.to_dev(chunks) if scaling is None else chunks
                 if isinstance(chunks, torch.Tensor) and chunks.is_cuda:
                     chunks.record_stream(s)
-                scores, paths, lens = bcs[k].call_chunks(cd)
+                scores, paths, lens = bcs[k].call_chunks(cd, scaling=scaling)
                 done = torch.cuda.Event()
                 done.record(s)
             B, T = paths.shape
@@ -326,18 +335,53 @@ class Basecaller(object):
         padded, nsamp = self._pack_reads(sigs)
         return self._call_padded(padded, nsamp)
 
-    def call_reads(self, signals, trim=(0, 0), open_pore_fraction=0.0):
+    def call_reads(self, signals, trim=(0, 0), open_pore_fraction=0.0, scaling=None):
         """Whole reads of different lengths in ONE batch (the reference calls them one at a time, basecall.py:88-121):
         `signals` is a list of 1-D float arrays (already scaled, e.g. fast5.Fast5.get_read()); each is trimmed as raw_worker does, median/MAD
         normalised over its own length, zero-padded to the longest, and the network + decoder run on the padded batch
         with per-read lengths (layers.ragged), so every read gets exactly what a batch-1 call would give.
-        -> device tensors (scores [B], paths [B, T'max] (-1 padded), lens [B]) and the per-read sample counts."""
+        -> device tensors (scores [B], paths [B, T'max] (-1 padded), lens [B]) and the per-read sample counts.
+
+        scaling: None takes `signals` as picoamperes.  Otherwise `signals` are 1-D int16 ADC reads (fast5.Fast5.get_read(scale=False)) and
+        `scaling` one (offset, range, digitisation) per read (fast5.Fast5.scaling(), batch.adc_scaling): the samples go to the device as
+        they are, are scaled there (slk_adc_to_pa_i16) and trimmed there, as prepare_read_batches does -- the same calls as on the
+        picoamperes, and the same ValueErrors for a read shorter than one window or empty after trimming."""
         net = self.network
         if not isinstance(net, layers.Serial) or type(net.layers[-1]) is not layers.Softmax:
             raise ValueError("call_reads needs a Serial network ending in a Softmax layer")
+        if scaling is not None:
+            padded, nsamp = self._adc_reads_trimmed(signals, scaling, trim, open_pore_fraction)
+            scores, paths, lens = self._call_padded(padded, nsamp)
+            return scores, paths, lens, nsamp
         sigs = self._trim_reads(signals, trim, open_pore_fraction)
         scores, paths, lens = self._call_trimmed(sigs)
         return scores, paths, lens, [len(s) for s in sigs]
+
+    @staticmethod
+    def _adc_reads_trimmed(signals, scaling, trim, open_pore_fraction, window_size=100):
+        """_trim_reads + _pack_reads for int16 reads, on the device: -> (zero-padded [B, Lmax] float32 device tensor, trimmed lengths)."""
+        import torch
+        from . import device as D
+        offset, scale = batch.adc_scaling(signals, scaling)
+        if min(len(s) for s in signals) < window_size:
+            raise ValueError("a read is shorter than one window of %d samples" % window_size)
+        assert trim[0] >= 0 and trim[1] >= 0
+        dev, off, lens, bad = batch.upload_adc_windowed(signals, offset, scale, window_size, return_nonfinite=True)
+        if bad.any():
+            raise ValueError("read %d holds samples that are not finite" % int(np.flatnonzero(bad)[0]))
+        bounds = batch.open_pore_bounds_many(dev, off, lens, open_pore_fraction, window_size=window_size)
+        if any(bd is None for bd in bounds):
+            raise ValueError("read %d has no window livelier than the open-pore threshold" % [bd is None for bd in bounds].index(True))
+        start = [int(off[r]) + bd[0] + trim[0] for r, bd in enumerate(bounds)]
+        nsamp = [bd[1] - bd[0] - trim[0] - trim[1] for bd in bounds]
+        if min(nsamp) < 1:
+            raise ValueError("empty read after trimming")
+        padded = torch.empty((len(nsamp), max(nsamp)), dtype=torch.float32, device=dev.device)
+        st = torch.as_tensor(np.asarray(start, dtype=np.int64)).to(dev.device)
+        ln = torch.as_tensor(np.asarray(nsamp, dtype=np.int32)).to(dev.device)
+        _lib.check(_lib.lib().slk_pack_reads_f32(dev.data_ptr(), st.data_ptr(), ln.data_ptr(), len(nsamp), padded.data_ptr(),
+                                                 padded.shape[1], D.stream_ptr()), "pack_reads")
+        return padded, nsamp
 
     @staticmethod
     def length_buckets(nsamp, max_batch=256, max_waste=0.08):
@@ -360,7 +404,7 @@ class Basecaller(object):
 
     @classmethod
     def prepare_read_batches(cls, network, signals, trim=(0, 0), open_pore_fraction=0.0, max_batch=256, max_waste=0.08, ids=None,
-                             **kwargs):
+                             scaling=None, **kwargs):
         """Preparation of the whole-read mode: the read set goes to the device in one upload, trimming bounds come from one launch over
         all windows (basecall.py:111-112), reads are bucketed by length and every bucket becomes a zero-padded device batch (one launch
         per bucket).  -> (batches, nsamp): batches = [(read indices, padded device tensor [B, Lmax], their sample counts)], nsamp =
@@ -369,14 +413,21 @@ class Basecaller(object):
         A read that cannot be called -- no sample left after trimming, shorter than one open-pore window, no window livelier than
         the threshold, or a sample that is not finite -- is left out of every batch and gets nsamp 0; `failed_reads(nsamp)` lists
         them.  The reference's worker does the same one read at a time: it reports the read on stderr, returns None and the pool goes
-        on (basecall.py:103-115).  The other reads of the set are unaffected."""
+        on (basecall.py:103-115).  The other reads of the set are unaffected.
+
+        scaling: as in call_reads -- int16 reads go to the device as they are and are scaled there (batch.upload_adc_windowed), the check
+        for samples that are not finite coming out of the same kernel."""
         import sys
         import torch
         from . import device as D
         # ONE upload of the whole read set; trimming bounds from the device's window spreads; the padded batches are then built on
         # the device (a launch per bucket) -- the host touches every sample once
-        dev, off, lens = batch.upload_reads_windowed(signals)
-        bad = batch.reads_nonfinite(dev, off, lens)
+        if scaling is None:
+            dev, off, lens = batch.upload_reads_windowed(signals)
+            bad = batch.reads_nonfinite(dev, off, lens)
+        else:
+            offset, scale = batch.adc_scaling(signals, scaling)
+            dev, off, lens, bad = batch.upload_adc_windowed(signals, offset, scale, return_nonfinite=True)
         bounds = batch.open_pore_bounds_many(dev, off, lens, open_pore_fraction)
         assert trim[0] >= 0 and trim[1] >= 0
         spans, nsamp = [], []
@@ -461,16 +512,20 @@ class Basecaller(object):
 
     @classmethod
     def call_reads_bucketed(cls, network, signals, trim=(0, 0), open_pore_fraction=0.0, max_batch=256, max_waste=0.08, in_flight=None,
-                            lanes=None, stream_buckets=True, **kwargs):
+                            lanes=None, stream_buckets=True, scaling=None, **kwargs):
         """Whole-read mode for MANY reads (what bin/basecall_network.py does with a pool of workers, basecall_network.py:100-104):
         reads are bucketed by length (length_buckets), every bucket is one padded ragged batch, and the buckets run side by side
         on streams of their own (one Basecaller each, sharing the network).  Each read gets bit for bit what call_reads([read])
         gives.  -> (scores [N] float32, list of N int32 path arrays, sample counts [N], stats) all on the host; stats holds the
         padded-step waste and the indices of the reads that could not be called (`failed`: score NaN, path None, sample count 0 --
-        each reported on stderr as the reference's worker reports a read it skips, basecall.py:103-115)."""
+        each reported on stderr as the reference's worker reports a read it skips, basecall.py:103-115).
+
+        scaling: as in call_reads (int16 ADC reads, one (offset, range, digitisation) per read, scaled on the device): the same results
+        as on the float64 picoamperes fast5.Fast5.get_read() returns, for half the bytes over the bus and a quarter of the host memory."""
         if open_pore_fraction == 0 and len(signals) > 2 * max_batch and stream_buckets:
-            return cls._call_reads_streamed(network, signals, trim, max_batch, max_waste, in_flight, lanes, **kwargs)
-        batches, nsamp = cls.prepare_read_batches(network, signals, trim, open_pore_fraction, max_batch, max_waste, **kwargs)
+            return cls._call_reads_streamed(network, signals, trim, max_batch, max_waste, in_flight, lanes, scaling=scaling, **kwargs)
+        batches, nsamp = cls.prepare_read_batches(network, signals, trim, open_pore_fraction, max_batch, max_waste, scaling=scaling,
+                                                  **kwargs)
         scores, paths = cls.run_read_batches(network, batches, len(nsamp), in_flight, lanes, **kwargs)
         used = sum(nsamp)
         padded = sum(ns[0] * len(idx) for idx, _, ns in batches)
@@ -481,7 +536,7 @@ class Basecaller(object):
     _UPLOAD_STREAMS = {}
 
     @classmethod
-    def _call_reads_streamed(cls, network, signals, trim, max_batch, max_waste, in_flight, lanes, window_size=100, **kwargs):
+    def _call_reads_streamed(cls, network, signals, trim, max_batch, max_waste, in_flight, lanes, window_size=100, scaling=None, **kwargs):
         """call_reads_bucketed for a big set with the CLI's open-pore fraction of 0 (bin/basecall_network.py:71), WITHOUT a round trip to
         the host between the upload of a read and its call: reads are bucketed by their RAW lengths (what the host knows without touching
         a sample; trimming takes at most a few windows off); bucket after bucket the host packs the reads into pinned memory and queues
@@ -490,7 +545,9 @@ class Basecaller(object):
         network, decoder, results and trimmed lengths to the host.  The host packs bucket k + 1 while the device runs bucket k: what is
         left in front of the network is the first bucket's upload (round 5: 85 ms of packing, upload and trimming for 4096 reads before
         the first network kernel).  A read that fails keeps its place in its bucket with length 0 (columns of a batch never mix), is
-        reported on stderr like the reference's worker does (basecall.py:103-115) and comes back with score NaN and path None."""
+        reported on stderr like the reference's worker does (basecall.py:103-115) and comes back with score NaN and path None.
+        With `scaling` (int16 reads, call_reads_bucketed) the staging area and the upload hold int16 samples, and the lane's first kernel
+        scales them (slk_adc_to_pa_i16), its flags standing in for the check for samples that are not finite."""
         import sys
         import torch
         from . import device as D
@@ -508,12 +565,16 @@ class Basecaller(object):
         strides = [-(-n // window_size) * window_size for n in raw]
         bsize = [sum(strides[i] for i in idx) for idx in buckets]
         total = sum(bsize)
-        st = batch._staging
-        if getattr(st, "buf", None) is None or st.buf.numel() < total:
-            st.buf = torch.empty(max(total, 1 << 20), dtype=torch.float32).pin_memory()
-            st.event = None
-        if st.event is not None:
-            st.event.synchronize()
+        if scaling is None:
+            st = batch._staging
+            if getattr(st, "buf", None) is None or st.buf.numel() < total:
+                st.buf = torch.empty(max(total, 1 << 20), dtype=torch.float32).pin_memory()
+                st.event = None
+            if st.event is not None:
+                st.event.synchronize()
+        else:
+            offset, scale = batch.adc_scaling(signals, scaling)
+            st = batch.staging16(total)
         hv = st.buf.numpy()
         assert trim[0] >= 0 and trim[1] >= 0
         import concurrent.futures
@@ -528,13 +589,17 @@ class Basecaller(object):
                     for j in range(lo, hi):
                         i = idx[j]
                         hv[base + off[j]: base + off[j] + raw[i]] = signals[i]
-                        hv[base + off[j] + raw[i]: base + off[j + 1]] = 0.0
+                        if scaling is None:                # (int16: slk_adc_to_pa_i16 writes the pad)
+                            hv[base + off[j] + raw[i]: base + off[j + 1]] = 0.0
                 step = max(1, -(-n // 8))
                 list(pool.map(lambda a: pack(*a), [(lo, min(n, lo + step)) for lo in range(0, n, step)]))
-                # [first sample | first window | raw length | whole windows] of every read, one small upload
-                meta = torch.empty((4, n), dtype=torch.int64).pin_memory()
+                # [first sample | first window | raw length | whole windows] of every read, one small upload (int16: + [stride | offset |
+                # scale], the float64 numbers as their bits)
+                meta = torch.empty((4 if scaling is None else 7, n), dtype=torch.int64).pin_memory()
                 mv = meta.numpy()
                 mv[0], mv[1], mv[2], mv[3] = off[:n], off[:n] // window_size, [raw[i] for i in idx], [raw[i] // window_size for i in idx]
+                if scaling is not None:
+                    mv[4], mv[5], mv[6] = np.diff(off), offset[idx].view(np.int64), scale[idx].view(np.int64)
                 with torch.cuda.stream(up):
                     sig = st.buf[base: base + bsize[k]].to(dev, non_blocking=True)
                     meta_d = meta.to(dev, non_blocking=True)
@@ -549,8 +614,14 @@ class Basecaller(object):
                     first_sample, first_win = meta_d[0], meta_d[1]
                     rawlen, nwin = meta_d[2].to(torch.int32), meta_d[3].to(torch.int32)
                     flags = torch.zeros((n,), dtype=torch.int32, device=dev)
-                    _lib.check(L.slk_reads_nonfinite_f32(sig.data_ptr(), first_sample.data_ptr(), rawlen.data_ptr(), n,
-                                                         int(max(raw[i] for i in idx)), flags.data_ptr(), lane.cuda_stream), "reads_nonfinite")
+                    if scaling is None:
+                        _lib.check(L.slk_reads_nonfinite_f32(sig.data_ptr(), first_sample.data_ptr(), rawlen.data_ptr(), n,
+                                                             int(max(raw[i] for i in idx)), flags.data_ptr(), lane.cuda_stream),
+                                   "reads_nonfinite")
+                    else:
+                        adc, sig = sig, torch.empty((bsize[k],), dtype=torch.float32, device=dev)
+                        batch.adc_to_pa(adc, first_sample, rawlen, meta_d[4].to(torch.int32), meta_d[5].view(torch.float64),
+                                        meta_d[6].view(torch.float64), sig, flags, int(np.diff(off).max()))
                     _, _, spread = batch.normalise_chunks(sig.view(-1, window_size), 'per-chunk', return_stats=True)
                     start = torch.empty((n,), dtype=torch.int64, device=dev)
                     ln = torch.empty((n,), dtype=torch.int32, device=dev)
