@@ -4,6 +4,7 @@
     normalise_chunks(chunks, 'per-chunk'|...)      median/MAD normalisation (chunkify_raw.py:178-185)
     chunks_to_network_input(chunks)                [ml, chunk_len] -> [chunk_len, ml, 1] (bin/train_network.py:304)
 """
+import contextlib
 import os
 import threading
 
@@ -84,97 +85,83 @@ def trim_open_pore(signal, max_op_fraction=0.3, var_method='mad', window_size=10
     :param var_method: 'mad' (median absolute deviation, the default) or 'std' (standard deviation) of each window
     :param window_size: size of patches used to estimate local variance
     """
-    import torch
     from . import device as D
-    assert var_method in TRIM_OPEN_PORE_LOCAL_VAR_METHODS, "var_method not understood: {}".format(var_method)
     nwin = len(signal) // window_size
     sd = D.to_dev(signal)
     if sd.dim() != 1:
         raise ValueError("trim_open_pore expects a 1D signal")
-    windows = sd[:nwin * window_size].reshape(nwin, window_size)
-    if var_method == 'mad':
-        _, _, spread = normalise_chunks(windows, 'per-chunk', return_stats=True)
-    else:
-        spread = torch.empty((nwin,), dtype=torch.float32, device=sd.device)
-        _lib.check(_lib.lib().slk_window_std_f32(windows.contiguous().data_ptr(), nwin, window_size, spread.data_ptr(),
-                                                 D.stream_ptr()), "window_std")
-    spread = spread.cpu().numpy() if isinstance(spread, torch.Tensor) else np.asarray(spread)
+    spread = _window_spread(sd[:nwin * window_size].reshape(nwin, window_size), var_method).cpu().numpy()
     # windows livelier than the max_op_fraction quantile are read; keep everything from the first to the last of them
     lively = np.flatnonzero(spread > np.percentile(spread, 100 * max_op_fraction))
     first_win, last_win = int(lively[0]), int(lively[-1])
     return signal[first_win * window_size: (last_win + 1) * window_size]
 
 
-def trim_open_pore_many(signals, max_op_fraction=0.3, var_method='mad', window_size=100):
-    """trim_open_pore for a list of reads with ONE device call: the windows of all reads are concatenated, their MADs (or
-    standard deviations) computed together, and the percentile threshold + slicing done per read on the host exactly as in
-    trim_open_pore (sloika/batch.py:194-220).  Returns a list of views of the inputs."""
+def _window_spread(windows, var_method='mad'):
+    """The 'mad' or 'std' of every row of a [nwin, window_size] float32 device matrix: -> float32 device tensor [nwin]."""
     import torch
     from . import device as D
     assert var_method in TRIM_OPEN_PORE_LOCAL_VAR_METHODS, "var_method not understood: {}".format(var_method)
-    sigs = [np.asarray(s, dtype=np.float32) for s in signals]
-    nwin = [len(s) // window_size for s in sigs]
-    if min(nwin) < 1:
-        raise ValueError("a read is shorter than one window of %d samples" % window_size)
-    allw = np.concatenate([s[:n * window_size] for s, n in zip(sigs, nwin)]).reshape(-1, window_size)
-    wd = D.to_dev(allw)
     if var_method == 'mad':
-        _, _, spread = normalise_chunks(wd, 'per-chunk', return_stats=True)
-    else:
-        spread = torch.empty((wd.shape[0],), dtype=torch.float32, device=wd.device)
-        _lib.check(_lib.lib().slk_window_std_f32(wd.data_ptr(), wd.shape[0], window_size, spread.data_ptr(), D.stream_ptr()),
-                   "window_std")
-    spread = spread.cpu().numpy()
-    out, lo = [], 0
-    for s, n in zip(sigs, nwin):
-        sp = spread[lo:lo + n]
-        lo += n
-        lively = np.flatnonzero(sp > np.percentile(sp, 100 * max_op_fraction))
-        out.append(s[int(lively[0]) * window_size: (int(lively[-1]) + 1) * window_size])
-    return out
+        return normalise_chunks(windows, 'per-chunk', return_stats=True)[2]
+    windows = windows.contiguous()
+    spread = torch.empty((windows.shape[0],), dtype=torch.float32, device=windows.device)
+    _lib.check(_lib.lib().slk_window_std_f32(windows.data_ptr(), windows.shape[0], windows.shape[1], spread.data_ptr(),
+                                             D.stream_ptr()), "window_std")
+    return spread
+
+
+def read_layout(lens, window_size=100):
+    """The layout of a read set in one buffer: read r at off[r], padded to whole windows.  -> (strides int64 [n], off int64 [n + 1])."""
+    strides = -(-np.asarray(lens, dtype=np.int64) // window_size) * window_size
+    off = np.zeros(len(strides) + 1, dtype=np.int64)
+    np.cumsum(strides, out=off[1:])
+    return strides, off
 
 
 class _Staging(threading.local):
-    """Pinned host staging buffer of upload_reads_windowed, one per host thread, kept between calls."""
-    buf = None
-    event = None
+    """Pinned host staging buffers, one per host thread and dtype, kept between calls: dtype -> (buffer, event of its last upload)."""
+
+    def __init__(self):
+        self.bufs = {}
 
 
 _staging = _Staging()
 
 
-def upload_reads_windowed(signals, window_size=100):
-    """All reads of a set in ONE upload (through pinned memory): read r occupies `dev[off[r] : off[r] + len[r]]`, every read padded
-    with zeros to whole windows, so that `dev.view(-1, window_size)` is the window matrix of all reads.  -> (dev, off, lengths)."""
+@contextlib.contextmanager
+def staging(total, dtype, stream=None):
+    """This host thread's pinned staging buffer of `dtype`, at least `total` samples (grow-only: pinning is the expensive part), once
+    the last upload out of it has left the host.  On the way out, also when the block raises, an event is recorded on `stream` (default:
+    the current stream): queue every upload out of the buffer there, inside the block."""
     import torch
-    from . import device as D
-    lens = [len(s) for s in signals]
-    strides = [-(-n // window_size) * window_size for n in lens]
-    off = np.concatenate([[0], np.cumsum(strides)]).astype(np.int64)
-    total = int(off[-1])
-    st = _staging
-    if getattr(st, "buf", None) is None or st.buf.numel() < total:
-        st.buf = torch.empty(max(total, 1 << 20), dtype=torch.float32).pin_memory()      # grow-only: pinning is the expensive part
-        st.event = None
-    if st.event is not None:
-        st.event.synchronize()                           # the previous upload out of this buffer has left the host
-    hv = st.buf.numpy()
-
-    def pack(lo, hi):
-        for r in range(lo, hi):
-            hv[off[r]: off[r] + lens[r]] = signals[r]
-            hv[off[r] + lens[r]: off[r + 1]] = 0.0
-
-    _pack_set(pack, off, len(signals))
-    dev = st.buf[:total].to(D.device(), non_blocking=True)
-    st.event = torch.cuda.Event()
-    st.event.record()
-    return dev, off, lens
+    buf, event = _staging.bufs.get(dtype, (None, None))
+    if buf is None or buf.numel() < total:
+        buf, event = torch.empty(max(total, 1 << 20), dtype=dtype).pin_memory(), None
+    if event is not None:
+        event.synchronize()
+    try:
+        yield buf
+    finally:
+        event = torch.cuda.Event()
+        event.record(stream)
+        _staging.bufs[dtype] = (buf, event)
 
 
-def _pack_set(pack, off, n):
-    """pack(lo, hi) for the reads lo .. hi of a set laid out at offsets `off` (n + 1 entries), on several host threads when it is big."""
-    total = int(off[-1])
+def fill_staging(hv, signals, off, lo, hi):
+    """Copy reads lo .. hi - 1 to hv[off[r]:] (hv: a staging buffer's numpy view), float32 zero-padded up to off[r + 1] (int16: the pad
+    is left to slk_adc_to_pa_i16, which writes it)."""
+    pad = hv.dtype == np.float32
+    for r in range(lo, hi):
+        end = off[r] + len(signals[r])
+        hv[off[r]: end] = signals[r]
+        if pad:
+            hv[end: off[r + 1]] = 0.0
+
+
+def _fill_set(hv, signals, off):
+    """fill_staging for a whole read set, on several host threads when it is big."""
+    n, total = len(signals), int(off[-1])
     if total >= (1 << 24) and n >= 16:
         # a gigabyte of samples is a tenth of a second of memcpy on one core; numpy's copies release the interpreter lock
         import concurrent.futures
@@ -182,57 +169,64 @@ def _pack_set(pack, off, n):
         cuts = np.searchsorted(off, np.linspace(0, total, nthr + 1)[1:-1]).tolist()
         edges = [0] + [min(max(c, 0), n) for c in cuts] + [n]
         with concurrent.futures.ThreadPoolExecutor(nthr) as ex:
-            list(ex.map(lambda a: pack(*a), [(edges[k], edges[k + 1]) for k in range(nthr) if edges[k + 1] > edges[k]]))
+            list(ex.map(lambda k: fill_staging(hv, signals, off, edges[k], edges[k + 1]),
+                        [k for k in range(nthr) if edges[k + 1] > edges[k]]))
     else:
-        pack(0, n)
+        fill_staging(hv, signals, off, 0, n)
 
 
-_staging16 = _Staging()              # int16 twin of _staging (upload_adc_windowed, the int16 streamed flow)
+def upload_reads_windowed(signals, window_size=100):
+    """upload_read_set for picoamperes, without the flags: -> (dev float32, off, lens)."""
+    return upload_read_set(signals, window_size)[:3]
 
 
-def staging16(total):
-    """This host thread's pinned int16 staging buffer, at least `total` samples (grow-only), once the last upload out of it has left."""
-    import torch
-    st = _staging16
-    if getattr(st, "buf", None) is None or st.buf.numel() < total:
-        st.buf = torch.empty(max(total, 1 << 20), dtype=torch.int16).pin_memory()
-        st.event = None
-    if st.event is not None:
-        st.event.synchronize()
-    return st
+def upload_read_set(signals, window_size=100, scaling=None):
+    """All reads of a set in ONE upload (through pinned memory): read r occupies `dev[off[r] : off[r] + lens[r]]`, every read padded
+    with zeros to whole windows (read_layout), so that `dev.view(-1, window_size)` is the window matrix of all reads.
+    -> (dev float32, off, lens, bad: bool [n], which reads hold a sample that is not finite).
 
-
-def upload_adc_windowed(signals, offset, scale, window_size=100, return_nonfinite=False):
-    """upload_reads_windowed for int16 ADC reads and their scaling (adc_scaling): the samples go to the device as they are (2 B each,
-    a memcpy into pinned memory, one upload) and slk_adc_to_pa_i16 writes the picoamperes into the same (dev float32, off, lengths)
-    layout -- bit for bit what upload_reads_windowed gives on the float64 reads fast5.Fast5.get_read() returns.  With return_nonfinite
-    also the reads_nonfinite answer (the kernel's flags, no second pass): -> (dev, off, lengths, bad)."""
+    scaling: None takes `signals` as picoamperes.  Otherwise `signals` are int16 ADC reads and `scaling` their (offset, range,
+    digitisation) (adc_scaling): the samples go to the device as they are (2 B each) and slk_adc_to_pa_i16 writes the picoamperes into
+    the same layout -- bit for bit what the float64 reads fast5.Fast5.get_read() returns give."""
     import torch
     from . import device as D
-    dev = D.device()
+    dtype, offset, scale = read_set_scaling(signals, scaling)
     lens = [len(s) for s in signals]
-    strides = [-(-n // window_size) * window_size for n in lens]
-    off = np.concatenate([[0], np.cumsum(strides)]).astype(np.int64)
+    strides, off = read_layout(lens, window_size)
     total, n = int(off[-1]), len(signals)
-    st = staging16(total)
-    hv = st.buf.numpy()
+    with staging(total, dtype) as buf:
+        _fill_set(buf.numpy(), signals, off)
+        src = buf[:total].to(D.device(), non_blocking=True)
+    if n == 0:
+        return torch.empty((0,), dtype=torch.float32, device=src.device), off, lens, np.zeros(0, dtype=bool)
+    dev, flags = picoamperes(src, _read_meta(off[:n], lens, strides, offset, scale, src.device), int(strides.max()))
+    return dev, off, lens, flags.cpu().numpy() != 0
 
-    def pack(lo, hi):
-        for r in range(lo, hi):
-            hv[off[r]: off[r] + lens[r]] = signals[r]          # (no zero fill: the kernel writes the pad)
 
-    _pack_set(pack, off, n)
-    src = st.buf[:total].to(dev, non_blocking=True)
-    st.event = torch.cuda.Event()
-    st.event.record()
-    out = torch.empty((total,), dtype=torch.float32, device=dev)
-    flags = torch.zeros((n,), dtype=torch.int32, device=dev)
-    if n:
-        meta = _adc_meta(off[:n], lens, strides, offset, scale, dev)
-        adc_to_pa(src, *meta, out, flags, max(strides))
-    if return_nonfinite:
-        return out, off, lens, flags.cpu().numpy() != 0
-    return out, off, lens
+def read_set_scaling(signals, scaling):
+    """How a read set crosses the bus: -> (staging dtype, per-read float64 offset and scale).  Picoamperes (scaling None) go as float32
+    with offset 0 and scale 1 (nothing scales them), int16 ADC reads as they are, with adc_scaling's numbers."""
+    import torch
+    if scaling is None:
+        return torch.float32, np.zeros(len(signals)), np.ones(len(signals))
+    return (torch.int16,) + adc_scaling(signals, scaling)
+
+
+def picoamperes(src, meta, max_stride):
+    """An uploaded read set as float32 picoamperes, on the current stream: float32 `src` as it is, int16 ADC samples scaled into a new
+    buffer (slk_adc_to_pa_i16).  meta: _read_meta's device tensors; max_stride >= every stride.  -> (set, flags int32 [n]: 1 where a
+    read holds a sample that is not finite, from the same kernel)."""
+    import torch
+    from . import device as D
+    n = int(meta[1].shape[0])
+    flags = torch.zeros((n,), dtype=torch.int32, device=src.device)
+    if src.dtype == torch.int16:
+        return adc_to_pa(src, *meta, torch.empty(src.shape, dtype=torch.float32, device=src.device), flags, max_stride), flags
+    start, lens = meta[0], meta[1]
+    for lo in range(0, n, 65535):                        # the grid's y limit
+        _lib.check(_lib.lib().slk_reads_nonfinite_f32(src.data_ptr(), start[lo:].data_ptr(), lens[lo:].data_ptr(), min(65535, n - lo),
+                                                      max_stride, flags[lo:].data_ptr(), D.stream_ptr()), "reads_nonfinite")
+    return src, flags
 
 
 def adc_chunks_to_pa(adc, scaling):
@@ -253,7 +247,7 @@ def adc_chunks_to_pa(adc, scaling):
     out = D.scratch((n, length), torch.float32, dev)
     if n and length:
         ln = np.full(n, length, dtype=np.int32)
-        adc_to_pa(src, *_adc_meta(np.arange(n, dtype=np.int64) * length, ln, ln, offset, scale, dev), out, None, length)
+        adc_to_pa(src, *_read_meta(np.arange(n, dtype=np.int64) * length, ln, ln, offset, scale, dev), out, None, length)
     return out
 
 
@@ -305,9 +299,10 @@ def adc_scaling(signals, scaling):
     return np.ascontiguousarray(trip[:, 0]), np.ascontiguousarray(scale)
 
 
-def _adc_meta(start, lens, strides, offset, scale, dev):
-    """slk_adc_to_pa_i16's per-read arrays on the device in ONE upload (through pinned memory; the device buffer comes out of the active
-    arena when there is one).  -> (start int64, len int32, stride int32, offset float64, scale float64) device tensors."""
+def _read_meta(start, lens, strides, offset, scale, dev):
+    """Per-read arrays of a read set on the device in ONE upload (through pinned memory; the device buffer comes out of the active arena
+    when there is one).  -> (start int64, len int32, stride int32, offset float64, scale float64) device tensors: picoamperes' and
+    slk_adc_to_pa_i16's arguments in their order."""
     import torch
     from . import device as D
     n = len(lens)
@@ -337,23 +332,13 @@ def adc_to_pa(adc, start, lens, strides, offset, scale, out, flags, max_stride):
 
 
 def open_pore_bounds_many(dev, off, lens, max_op_fraction=0.3, var_method='mad', window_size=100):
-    """trim_open_pore (sloika/batch.py:194-220) for reads resident on the device as upload_reads_windowed leaves them: the
+    """trim_open_pore (sloika/batch.py:194-220) for reads resident on the device as upload_read_set leaves them: the
     spreads of ALL windows in one launch, the percentile threshold per read on the host (a few hundred numbers each).
     -> list of (first sample, one past the last sample) relative to each read's start; None for a read the reference's function
     would fail on (shorter than one window, or no window livelier than the threshold)."""
-    import torch
-    from . import device as D
-    assert var_method in TRIM_OPEN_PORE_LOCAL_VAR_METHODS, "var_method not understood: {}".format(var_method)
     nwin = np.asarray([n // window_size for n in lens], dtype=np.int64)
-    wd = dev.view(-1, window_size)
-    if var_method == 'mad':
-        _, _, spread = normalise_chunks(wd, 'per-chunk', return_stats=True)
-    else:
-        spread = torch.empty((wd.shape[0],), dtype=torch.float32, device=wd.device)
-        _lib.check(_lib.lib().slk_window_std_f32(wd.data_ptr(), wd.shape[0], window_size, spread.data_ptr(), D.stream_ptr()),
-                   "window_std")
-    spread = spread.cpu().numpy()
-    w0 = np.asarray(off[:-1] if len(off) == len(lens) + 1 else off, dtype=np.int64) // window_size
+    spread = _window_spread(dev.view(-1, window_size), var_method).cpu().numpy()
+    w0 = np.asarray(off[:len(lens)], dtype=np.int64) // window_size
     out = [None] * len(lens)
     if max_op_fraction == 0 and len(lens):
         # np.percentile(., 0) is the minimum: all reads at once (whole windows only, as the reference's reshape leaves them)
@@ -380,21 +365,50 @@ def open_pore_bounds_many(dev, off, lens, max_op_fraction=0.3, var_method='mad',
     return out
 
 
-def reads_nonfinite(dev, off, lens):
-    """Which reads of an uploaded read set (upload_reads_windowed) hold a NaN or an infinity: bool array [nread]."""
+#: why a read cannot be called, by the flag bits of slk_open_pore_trim_f32 and read_spans, in the order a read is reported by:
+#: (bit, the reason on stderr (basecall.py:103-115), Basecaller.call_reads' error)
+READ_FAILURES = ((1, "samples that are not finite", "read {} holds samples that are not finite"),
+                 (2, "too short to trim the open pore", "read {} has no window livelier than the open-pore threshold"),
+                 (4, "nothing left after trimming", "empty read after trimming (read {})"))
+
+
+def read_failure(flag):
+    """The READ_FAILURES row of the first bit set in `flag`; None for 0."""
+    return next((row for row in READ_FAILURES if flag & row[0]), None)
+
+
+def read_spans(bounds, bad, trim):
+    """util.trim_array (basecall.py:111-112) on open_pore_bounds_many's bounds, as slk_open_pore_trim_f32 does it on the device:
+    -> (start, lengths, flags), lists over the reads: start relative to the read's own, flags with the kernel's bits (READ_FAILURES:
+    1 a sample is not finite (`bad`), 2 no whole window or no lively window, 4 nothing left after trimming).  A flagged read has
+    length 0."""
+    assert trim[0] >= 0 and trim[1] >= 0
+    start, lengths, flags = [], [], []
+    for bd, b in zip(bounds, bad):
+        lo, hi, f = 0, 0, 1 if b else 0
+        if bd is None:
+            f |= 2
+        else:
+            lo, hi = bd[0] + trim[0], bd[1] - trim[1]
+            f |= 4 if hi - lo < 1 else 0
+        start.append(lo if f == 0 else 0)
+        lengths.append(hi - lo if f == 0 else 0)
+        flags.append(f)
+    return start, lengths, flags
+
+
+def pack_batch(dev, start, lengths, width):
+    """slk_pack_reads_f32 on the current stream: the reads at dev[start[b] : start[b] + lengths[b]] -> [B, width] float32 device tensor,
+    zero behind every read's end.  start / lengths: host sequences, or int64 / int32 device tensors."""
     import torch
     from . import device as D
-    n = len(lens)
-    if n == 0:
-        return np.zeros(0, dtype=bool)
-    start = torch.as_tensor(np.ascontiguousarray(off[:n], dtype=np.int64)).to(dev.device)
-    ln = torch.as_tensor(np.ascontiguousarray(lens, dtype=np.int32)).to(dev.device)
-    flags = torch.zeros((n,), dtype=torch.int32, device=dev.device)
-    for lo in range(0, n, 65535):
-        hi = min(n, lo + 65535)
-        _lib.check(_lib.lib().slk_reads_nonfinite_f32(dev.data_ptr(), start[lo:].data_ptr(), ln[lo:].data_ptr(), hi - lo,
-                                                      int(max(lens[lo:hi])), flags[lo:].data_ptr(), D.stream_ptr()), "reads_nonfinite")
-    return flags.cpu().numpy() != 0
+    if not isinstance(start, torch.Tensor):
+        start = torch.as_tensor(np.asarray(start, dtype=np.int64)).to(dev.device)
+        lengths = torch.as_tensor(np.asarray(lengths, dtype=np.int32)).to(dev.device)
+    out = torch.empty((int(lengths.shape[0]), width), dtype=torch.float32, device=dev.device)
+    _lib.check(_lib.lib().slk_pack_reads_f32(dev.data_ptr(), start.data_ptr(), lengths.data_ptr(), out.shape[0], out.data_ptr(), width,
+                                             D.stream_ptr()), "pack_reads")
+    return out
 
 
 def normalise_reads_ragged(padded, lengths):

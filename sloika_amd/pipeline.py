@@ -8,6 +8,7 @@ BASELINE.json's metric is quoted on.  All arithmetic happens in the HIP kernels 
 torch only owns the buffers and the stream.
 """
 import os
+import sys
 
 import numpy as np
 
@@ -270,30 +271,6 @@ class Basecaller(object):
         scores, paths, lens = self.call_chunks(chunks)
         return scores, bio.paths_to_bases(paths, lens, self.kmer_len, alphabet, always_move=True)
 
-    def _trim_reads(self, signals, trim, open_pore_fraction):
-        """basecall.py:111-112: trim_open_pore (which also cuts the read to whole 100-sample windows), then trim_array."""
-        from . import util
-        sigs = batch.trim_open_pore_many(signals, open_pore_fraction)
-        sigs = [util.trim_array(s, *trim) for s in sigs]
-        if min(len(s) for s in sigs) < 1:
-            raise ValueError("empty read after trimming")
-        return sigs
-
-    @staticmethod
-    def _pack_reads(sigs):
-        """Trimmed reads (host float32 arrays) -> zero-padded [B, Lmax] device tensor (through pinned memory when it is big)."""
-        import torch
-        from . import device as D
-        nsamp = [len(s) for s in sigs]
-        B, lmax = len(sigs), max(nsamp)
-        host = torch.zeros((B, lmax), dtype=torch.float32)
-        if B * lmax >= (1 << 20):
-            host = host.pin_memory()
-        hv = host.numpy()
-        for b, sig in enumerate(sigs):
-            hv[b, :nsamp[b]] = sig
-        return host.to(D.device(), non_blocking=True), nsamp
-
     def _call_padded(self, padded, nsamp):
         """One padded batch of trimmed reads resident on the device ([B, Lmax], read b in its first nsamp[b] samples): per-read
         normalisation, network and decoder with per-read lengths.  -> (scores, paths, lens) on the device."""
@@ -331,57 +308,47 @@ class Basecaller(object):
         return decode.viterbi_logits_batch(logits, stats, self.kmer_len, T, B, ld=ld, skip_pen=self.skip, nbase=self.nbase,
                                            min_prob=self.min_prob, workspace=self._ws, lengths=lengths.contiguous())
 
-    def _call_trimmed(self, sigs):
-        padded, nsamp = self._pack_reads(sigs)
-        return self._call_padded(padded, nsamp)
-
     def call_reads(self, signals, trim=(0, 0), open_pore_fraction=0.0, scaling=None):
         """Whole reads of different lengths in ONE batch (the reference calls them one at a time, basecall.py:88-121):
         `signals` is a list of 1-D float arrays (already scaled, e.g. fast5.Fast5.get_read()); each is trimmed as raw_worker does, median/MAD
         normalised over its own length, zero-padded to the longest, and the network + decoder run on the padded batch
         with per-read lengths (layers.ragged), so every read gets exactly what a batch-1 call would give.
         -> device tensors (scores [B], paths [B, T'max] (-1 padded), lens [B]) and the per-read sample counts.
+        A read that cannot be called (shorter than one window, a sample that is not finite, no window livelier than the open-pore
+        threshold, nothing left after trimming) raises ValueError.
 
         scaling: None takes `signals` as picoamperes.  Otherwise `signals` are 1-D int16 ADC reads (fast5.Fast5.get_read(scale=False)) and
         `scaling` one (offset, range, digitisation) per read (fast5.Fast5.scaling(), batch.adc_scaling): the samples go to the device as
-        they are, are scaled there (slk_adc_to_pa_i16) and trimmed there, as prepare_read_batches does -- the same calls as on the
-        picoamperes, and the same ValueErrors for a read shorter than one window or empty after trimming."""
+        they are and are scaled there (slk_adc_to_pa_i16) -- the same calls as on the picoamperes."""
         net = self.network
         if not isinstance(net, layers.Serial) or type(net.layers[-1]) is not layers.Softmax:
             raise ValueError("call_reads needs a Serial network ending in a Softmax layer")
-        if scaling is not None:
-            padded, nsamp = self._adc_reads_trimmed(signals, scaling, trim, open_pore_fraction)
-            scores, paths, lens = self._call_padded(padded, nsamp)
-            return scores, paths, lens, nsamp
-        sigs = self._trim_reads(signals, trim, open_pore_fraction)
-        scores, paths, lens = self._call_trimmed(sigs)
-        return scores, paths, lens, [len(s) for s in sigs]
+        if min(len(s) for s in signals) < 100:
+            raise ValueError("a read is shorter than one window of 100 samples")
+        dev, start, nsamp, flags = self._trimmed_read_set(signals, trim, open_pore_fraction, scaling)
+        for r, f in enumerate(flags):
+            if f:
+                raise ValueError(batch.read_failure(f)[2].format(r))
+        scores, paths, lens = self._call_padded(batch.pack_batch(dev, start, nsamp, max(nsamp)), nsamp)
+        return scores, paths, lens, nsamp
 
     @staticmethod
-    def _adc_reads_trimmed(signals, scaling, trim, open_pore_fraction, window_size=100):
-        """_trim_reads + _pack_reads for int16 reads, on the device: -> (zero-padded [B, Lmax] float32 device tensor, trimmed lengths)."""
-        import torch
-        from . import device as D
-        offset, scale = batch.adc_scaling(signals, scaling)
-        if min(len(s) for s in signals) < window_size:
-            raise ValueError("a read is shorter than one window of %d samples" % window_size)
-        assert trim[0] >= 0 and trim[1] >= 0
-        dev, off, lens, bad = batch.upload_adc_windowed(signals, offset, scale, window_size, return_nonfinite=True)
-        if bad.any():
-            raise ValueError("read %d holds samples that are not finite" % int(np.flatnonzero(bad)[0]))
-        bounds = batch.open_pore_bounds_many(dev, off, lens, open_pore_fraction, window_size=window_size)
-        if any(bd is None for bd in bounds):
-            raise ValueError("read %d has no window livelier than the open-pore threshold" % [bd is None for bd in bounds].index(True))
-        start = [int(off[r]) + bd[0] + trim[0] for r, bd in enumerate(bounds)]
-        nsamp = [bd[1] - bd[0] - trim[0] - trim[1] for bd in bounds]
-        if min(nsamp) < 1:
-            raise ValueError("empty read after trimming")
-        padded = torch.empty((len(nsamp), max(nsamp)), dtype=torch.float32, device=dev.device)
-        st = torch.as_tensor(np.asarray(start, dtype=np.int64)).to(dev.device)
-        ln = torch.as_tensor(np.asarray(nsamp, dtype=np.int32)).to(dev.device)
-        _lib.check(_lib.lib().slk_pack_reads_f32(dev.data_ptr(), st.data_ptr(), ln.data_ptr(), len(nsamp), padded.data_ptr(),
-                                                 padded.shape[1], D.stream_ptr()), "pack_reads")
-        return padded, nsamp
+    def _trimmed_read_set(signals, trim, open_pore_fraction, scaling):
+        """The read set in ONE upload (batch.upload_read_set), the trimming bounds out of one launch over all windows
+        (basecall.py:111-112).  -> (device set, first sample of every read after trimming, its sample count, its flags
+        (batch.read_spans: 0 for a read that can be called))."""
+        dev, off, lens, bad = batch.upload_read_set(signals, scaling=scaling)
+        bounds = batch.open_pore_bounds_many(dev, off, lens, open_pore_fraction)
+        start, nsamp, flags = batch.read_spans(bounds, bad, trim)
+        return dev, [int(o) + s for o, s in zip(off, start)], nsamp, flags
+
+    @staticmethod
+    def _report_failures(flags, ids=None):
+        """A line on stderr for every read that cannot be called, as the reference's worker reports a read it skips (basecall.py:103-115),
+        with the reason of its first flag bit (batch.READ_FAILURES)."""
+        for r, f in enumerate(flags):
+            if f:
+                sys.stderr.write("Failure calling read {}: {}\n".format(r if ids is None else ids[r], batch.read_failure(f)[1]))
 
     @staticmethod
     def length_buckets(nsamp, max_batch=256, max_waste=0.08):
@@ -415,42 +382,17 @@ class Basecaller(object):
         them.  The reference's worker does the same one read at a time: it reports the read on stderr, returns None and the pool goes
         on (basecall.py:103-115).  The other reads of the set are unaffected.
 
-        scaling: as in call_reads -- int16 reads go to the device as they are and are scaled there (batch.upload_adc_windowed), the check
-        for samples that are not finite coming out of the same kernel."""
-        import sys
-        import torch
-        from . import device as D
-        # ONE upload of the whole read set; trimming bounds from the device's window spreads; the padded batches are then built on
-        # the device (a launch per bucket) -- the host touches every sample once
-        if scaling is None:
-            dev, off, lens = batch.upload_reads_windowed(signals)
-            bad = batch.reads_nonfinite(dev, off, lens)
-        else:
-            offset, scale = batch.adc_scaling(signals, scaling)
-            dev, off, lens, bad = batch.upload_adc_windowed(signals, offset, scale, return_nonfinite=True)
-        bounds = batch.open_pore_bounds_many(dev, off, lens, open_pore_fraction)
-        assert trim[0] >= 0 and trim[1] >= 0
-        spans, nsamp = [], []
-        for r, bd in enumerate(bounds):
-            lo, hi = (0, 0) if (bd is None or bad[r]) else (bd[0] + trim[0], bd[1] - trim[1])               # util.trim_array
-            spans.append((lo, hi))
-            nsamp.append(max(0, hi - lo))
-            if nsamp[-1] < 1:
-                why = "samples that are not finite" if bad[r] else ("too short to trim the open pore" if bd is None else
-                                                                    "nothing left after trimming")
-                sys.stderr.write("Failure calling read {}: {}\n".format(r if ids is None else ids[r], why))
+        scaling: as in call_reads -- int16 reads go to the device as they are and are scaled there (batch.upload_read_set), the
+        check for samples that are not finite coming out of the same kernel."""
+        # the host touches every sample once; the padded batches are built on the device (a launch per bucket)
+        dev, start, nsamp, flags = cls._trimmed_read_set(signals, trim, open_pore_fraction, scaling)
+        cls._report_failures(flags, ids)
         good = [r for r in range(len(nsamp)) if nsamp[r] > 0]
         batches = []
-        L = _lib.lib()
         for sub in cls.length_buckets([nsamp[r] for r in good], max_batch, max_waste):
             idx = [good[j] for j in sub]
             ns = [nsamp[i] for i in idx]
-            padded = torch.empty((len(idx), max(ns)), dtype=torch.float32, device=dev.device)
-            start = torch.as_tensor(np.asarray([int(off[i]) + spans[i][0] for i in idx], dtype=np.int64)).to(dev.device)
-            ln = torch.as_tensor(np.asarray(ns, dtype=np.int32)).to(dev.device)
-            _lib.check(L.slk_pack_reads_f32(dev.data_ptr(), start.data_ptr(), ln.data_ptr(), len(idx), padded.data_ptr(),
-                                            padded.shape[1], D.stream_ptr()), "pack_reads")
-            batches.append((idx, padded, ns))
+            batches.append((idx, batch.pack_batch(dev, [start[i] for i in idx], ns, max(ns)), ns))
         return batches, nsamp
 
     @staticmethod
@@ -466,23 +408,14 @@ class Basecaller(object):
         pairs to reuse (read_lanes(); torch's allocator caches device memory per stream, so a server that keeps its lanes does
         not pay for gigabytes of fresh allocations on every call).  -> (scores [N] float32, list of N int32 path arrays) on the
         host; a read that is in no batch (failed_reads) has score NaN and path None."""
+        import torch
         if lanes is None:
             lanes = cls.read_lanes(network, max(1, min(8, len(batches)) if in_flight is None else in_flight), **kwargs)
-        scores = np.full(nreads, np.nan, dtype=np.float32)
-        paths = [None] * nreads
-        cls._collect_read_batches(cls._launch_read_batches(lanes, batches), scores, paths)
-        return scores, paths
-
-    @staticmethod
-    def _launch_read_batches(lanes, batches, first_lane=0):
-        """Queue every prepared batch on its lane (batch k on lane (first_lane + k) % lanes) and its results' way to the host behind it;
-        nothing here waits for the device.  -> pending [(read indices, host tensors, event, device tensors)]."""
-        import torch
-        nfl = len(lanes)
+        # every batch queued on its lane (batch k on lane k % lanes) with its results' way to the host behind it, then collected
         cur = torch.cuda.current_stream()
         pending = []
         for k, (idx, padded, ns) in enumerate(batches):
-            bc, s = lanes[(first_lane + k) % nfl]
+            bc, s = lanes[k % len(lanes)]
             s.wait_stream(cur)
             with torch.cuda.stream(s):
                 padded.record_stream(s)
@@ -491,18 +424,15 @@ class Basecaller(object):
                 ev = torch.cuda.Event()
                 ev.record(s)
             pending.append((idx, host, ev, res))
-        return pending
-
-    @staticmethod
-    def _collect_read_batches(pending, scores, paths, ids=None):
-        """Wait for the queued batches and file their results under the reads' indices (`ids`: slice-local index -> index in the set)."""
+        scores = np.full(nreads, np.nan, dtype=np.float32)
+        paths = [None] * nreads
         for idx, host, ev, res in pending:
             ev.synchronize()
             sc, pa, le = (h.numpy() for h in host)
             for j, i in enumerate(idx):
-                g = i if ids is None else ids[i]
-                scores[g] = sc[j]
-                paths[g] = pa[j, :le[j]].copy()
+                scores[i] = sc[j]
+                paths[i] = pa[j, :le[j]].copy()
+        return scores, paths
 
     @classmethod
     def read_lanes(cls, network, n, **kwargs):
@@ -522,15 +452,20 @@ class Basecaller(object):
 
         scaling: as in call_reads (int16 ADC reads, one (offset, range, digitisation) per read, scaled on the device): the same results
         as on the float64 picoamperes fast5.Fast5.get_read() returns, for half the bytes over the bus and a quarter of the host memory."""
-        if open_pore_fraction == 0 and len(signals) > 2 * max_batch and stream_buckets:
-            return cls._call_reads_streamed(network, signals, trim, max_batch, max_waste, in_flight, lanes, scaling=scaling, **kwargs)
-        batches, nsamp = cls.prepare_read_batches(network, signals, trim, open_pore_fraction, max_batch, max_waste, scaling=scaling,
-                                                  **kwargs)
-        scores, paths = cls.run_read_batches(network, batches, len(nsamp), in_flight, lanes, **kwargs)
+        streamed = open_pore_fraction == 0 and len(signals) > 2 * max_batch and stream_buckets
+        if streamed:
+            scores, paths, nsamp, nbatch, padded = cls._call_reads_streamed(network, signals, trim, max_batch, max_waste, in_flight, lanes,
+                                                                            scaling=scaling, **kwargs)
+        else:
+            batches, nsamp = cls.prepare_read_batches(network, signals, trim, open_pore_fraction, max_batch, max_waste, scaling=scaling,
+                                                      **kwargs)
+            scores, paths = cls.run_read_batches(network, batches, len(nsamp), in_flight, lanes, **kwargs)
+            nbatch, padded = len(batches), sum(ns[0] * len(idx) for idx, _, ns in batches)
         used = sum(nsamp)
-        padded = sum(ns[0] * len(idx) for idx, _, ns in batches)
-        stats = {"reads": len(nsamp), "batches": len(batches), "samples": used, "padded_samples": padded,
+        stats = {"reads": len(nsamp), "batches": nbatch, "samples": used, "padded_samples": padded,
                  "padded_step_waste": 1.0 - used / float(max(padded, 1)), "failed": cls.failed_reads(nsamp)}
+        if streamed:
+            stats["streamed"] = True
         return scores, paths, nsamp, stats
 
     _UPLOAD_STREAMS = {}
@@ -544,125 +479,91 @@ class Basecaller(object):
         the window spreads, trim_open_pore + trim_array on the device (slk_open_pore_trim_f32), the zero-padded batch, normalisation,
         network, decoder, results and trimmed lengths to the host.  The host packs bucket k + 1 while the device runs bucket k: what is
         left in front of the network is the first bucket's upload (round 5: 85 ms of packing, upload and trimming for 4096 reads before
-        the first network kernel).  A read that fails keeps its place in its bucket with length 0 (columns of a batch never mix), is
-        reported on stderr like the reference's worker does (basecall.py:103-115) and comes back with score NaN and path None.
+        the first network kernel).  A read that fails on the device keeps its place in its bucket with length 0 (columns of a batch never
+        mix); a read shorter than one window goes into no bucket.  Every failed read is reported on stderr like the reference's worker
+        does (basecall.py:103-115) and comes back with score NaN and path None.
         With `scaling` (int16 reads, call_reads_bucketed) the staging area and the upload hold int16 samples, and the lane's first kernel
-        scales them (slk_adc_to_pa_i16), its flags standing in for the check for samples that are not finite."""
-        import sys
+        scales them (slk_adc_to_pa_i16), its flags standing in for the check for samples that are not finite.
+        -> (scores, paths, nsamp, number of batches, padded samples)."""
+        import concurrent.futures
         import torch
         from . import device as D
-        L = _lib.lib()
         dev = D.device()
         nread = len(signals)
         raw = [len(s) for s in signals]
-        buckets = cls.length_buckets(raw, max_batch, max_waste)
+        dtype, offset, scale = batch.read_set_scaling(signals, scaling)
+        # a read shorter than one window has no window to trim by: the reference's function fails on it (flag 2), after the check for
+        # samples that are not finite (flag 1), taken here on the host for these few samples as the device would take it
+        flags = [0] * nread
+        with np.errstate(all="ignore"):
+            for i in (i for i in range(nread) if raw[i] < window_size):
+                pa = ((np.asarray(signals[i], dtype=np.float64) + offset[i]) * scale[i]).astype(np.float32)
+                flags[i] = 2 | int(not np.isfinite(pa).all())
+        live = [i for i in range(nread) if not flags[i]]
+        buckets = [[live[j] for j in sub] for sub in cls.length_buckets([raw[i] for i in live], max_batch, max_waste)]
         if lanes is None:
             lanes = cls.read_lanes(network, max(1, min(8, len(buckets))) if in_flight is None else in_flight, **kwargs)
         up = cls._UPLOAD_STREAMS.get(dev.index)
         if up is None:
             up = cls._UPLOAD_STREAMS[dev.index] = torch.cuda.Stream()
-        # one pinned staging area for the whole set (grow-only, kept per host thread: batch._staging), bucket after bucket
-        strides = [-(-n // window_size) * window_size for n in raw]
-        bsize = [sum(strides[i] for i in idx) for idx in buckets]
-        total = sum(bsize)
-        if scaling is None:
-            st = batch._staging
-            if getattr(st, "buf", None) is None or st.buf.numel() < total:
-                st.buf = torch.empty(max(total, 1 << 20), dtype=torch.float32).pin_memory()
-                st.event = None
-            if st.event is not None:
-                st.event.synchronize()
-        else:
-            offset, scale = batch.adc_scaling(signals, scaling)
-            st = batch.staging16(total)
-        hv = st.buf.numpy()
+        # the whole set in one pinned staging area, laid out bucket after bucket
+        order = [i for idx in buckets for i in idx]
+        sigs = [signals[i] for i in order]
+        strides, off = batch.read_layout([raw[i] for i in order], window_size)
         assert trim[0] >= 0 and trim[1] >= 0
-        import concurrent.futures
-        pool = concurrent.futures.ThreadPoolExecutor(min(8, os.cpu_count() or 1))
-        pending, base = [], 0
-        try:
+        pending, lo = [], 0
+        with concurrent.futures.ThreadPoolExecutor(min(8, os.cpu_count() or 1)) as pool, \
+                batch.staging(int(off[-1]), dtype, up) as buf:
+            hv = buf.numpy()
             for k, idx in enumerate(buckets):
-                n = len(idx)
-                off = np.concatenate([[0], np.cumsum([strides[i] for i in idx])]).astype(np.int64)
-
-                def pack(lo, hi, idx=idx, off=off, base=base):
-                    for j in range(lo, hi):
-                        i = idx[j]
-                        hv[base + off[j]: base + off[j] + raw[i]] = signals[i]
-                        if scaling is None:                # (int16: slk_adc_to_pa_i16 writes the pad)
-                            hv[base + off[j] + raw[i]: base + off[j + 1]] = 0.0
+                n, hi = len(idx), lo + len(idx)
                 step = max(1, -(-n // 8))
-                list(pool.map(lambda a: pack(*a), [(lo, min(n, lo + step)) for lo in range(0, n, step)]))
-                # [first sample | first window | raw length | whole windows] of every read, one small upload (int16: + [stride | offset |
-                # scale], the float64 numbers as their bits)
-                meta = torch.empty((4 if scaling is None else 7, n), dtype=torch.int64).pin_memory()
-                mv = meta.numpy()
-                mv[0], mv[1], mv[2], mv[3] = off[:n], off[:n] // window_size, [raw[i] for i in idx], [raw[i] // window_size for i in idx]
-                if scaling is not None:
-                    mv[4], mv[5], mv[6] = np.diff(off), offset[idx].view(np.int64), scale[idx].view(np.int64)
+                list(pool.map(lambda a: batch.fill_staging(hv, sigs, off, a, min(hi, a + step)), range(lo, hi, step)))
+                base, max_stride = int(off[lo]), int(strides[lo:hi].max())
                 with torch.cuda.stream(up):
-                    sig = st.buf[base: base + bsize[k]].to(dev, non_blocking=True)
-                    meta_d = meta.to(dev, non_blocking=True)
+                    # (`upload` lives until the next bucket's replaces it: int16 samples released right after their conversion made
+                    #  about one call in three 60 ms slower)
+                    upload = buf[base: int(off[hi])].to(dev, non_blocking=True)
+                    meta = batch._read_meta(off[lo:hi] - base, [raw[i] for i in idx], strides[lo:hi], offset[idx], scale[idx], dev)
                     uploaded = torch.cuda.Event()
                     uploaded.record(up)
-                base += bsize[k]
                 bc, lane = lanes[k % len(lanes)]
                 with torch.cuda.stream(lane):
                     lane.wait_event(uploaded)
-                    sig.record_stream(lane)
-                    meta_d.record_stream(lane)
-                    first_sample, first_win = meta_d[0], meta_d[1]
-                    rawlen, nwin = meta_d[2].to(torch.int32), meta_d[3].to(torch.int32)
-                    flags = torch.zeros((n,), dtype=torch.int32, device=dev)
-                    if scaling is None:
-                        _lib.check(L.slk_reads_nonfinite_f32(sig.data_ptr(), first_sample.data_ptr(), rawlen.data_ptr(), n,
-                                                             int(max(raw[i] for i in idx)), flags.data_ptr(), lane.cuda_stream),
-                                   "reads_nonfinite")
-                    else:
-                        adc, sig = sig, torch.empty((bsize[k],), dtype=torch.float32, device=dev)
-                        batch.adc_to_pa(adc, first_sample, rawlen, meta_d[4].to(torch.int32), meta_d[5].view(torch.float64),
-                                        meta_d[6].view(torch.float64), sig, flags, int(np.diff(off).max()))
-                    _, _, spread = batch.normalise_chunks(sig.view(-1, window_size), 'per-chunk', return_stats=True)
+                    upload.record_stream(lane)
+                    meta[0].record_stream(lane)
+                    sig, fl = batch.picoamperes(upload, meta, max_stride)
+                    first_sample, rawlen = meta[0], meta[1]
+                    spread = batch._window_spread(sig.view(-1, window_size))
+                    first_win, nwin = first_sample // window_size, rawlen // window_size
                     start = torch.empty((n,), dtype=torch.int64, device=dev)
                     ln = torch.empty((n,), dtype=torch.int32, device=dev)
-                    _lib.check(L.slk_open_pore_trim_f32(spread.data_ptr(), first_win.data_ptr(), nwin.data_ptr(), first_sample.data_ptr(),
-                                                        n, window_size, int(trim[0]), int(trim[1]), start.data_ptr(), ln.data_ptr(),
-                                                        flags.data_ptr(), lane.cuda_stream), "open_pore_trim")
+                    _lib.check(_lib.lib().slk_open_pore_trim_f32(spread.data_ptr(), first_win.data_ptr(), nwin.data_ptr(),
+                                                                 first_sample.data_ptr(), n, window_size, int(trim[0]), int(trim[1]),
+                                                                 start.data_ptr(), ln.data_ptr(), fl.data_ptr(), D.stream_ptr()),
+                               "open_pore_trim")
                     lmax = max(raw[i] for i in idx)                    # (an upper bound of the trimmed lengths: the batch's row width)
-                    padded = torch.empty((n, lmax), dtype=torch.float32, device=dev)
-                    _lib.check(L.slk_pack_reads_f32(sig.data_ptr(), start.data_ptr(), ln.data_ptr(), n, padded.data_ptr(), lmax,
-                                                    lane.cuda_stream), "pack_reads")
                     # a failed read (length 0) runs as one zero sample: its column is garbage nobody reads
-                    res = bc._call_padded(padded, ln.clamp(min=1))
-                    host = tuple(t.to("cpu", non_blocking=True) for t in res + (ln, flags))
+                    res = bc._call_padded(batch.pack_batch(sig, start, ln, lmax), ln.clamp(min=1))
+                    host = tuple(t.to("cpu", non_blocking=True) for t in res + (ln, fl))
                     ev = torch.cuda.Event()
                     ev.record(lane)
                 pending.append((idx, host, ev, res, lmax))
-            st.event = torch.cuda.Event()
-            st.event.record(up)
-        finally:
-            pool.shutdown(wait=True)
+                lo = hi
         scores = np.full(nread, np.nan, dtype=np.float32)
         paths = [None] * nread
         nsamp = [0] * nread
-        padded_total = 0
         for idx, host, ev, res, lmax in pending:
             ev.synchronize()
-            sc, pa, le, ns, fl = (h.numpy() for h in host)
-            padded_total += lmax * len(idx)
+            sc, pa, le, ns, fb = (h.numpy() for h in host)
             for j, i in enumerate(idx):
-                if fl[j]:
-                    why = "samples that are not finite" if fl[j] & 1 else ("too short to trim the open pore" if fl[j] & 2 else
-                                                                            "nothing left after trimming")
-                    sys.stderr.write("Failure calling read {}: {}\n".format(i, why))
-                    continue
-                nsamp[i] = int(ns[j])
-                scores[i] = sc[j]
-                paths[i] = pa[j, :le[j]].copy()
-        used = sum(nsamp)
-        stats = {"reads": nread, "batches": len(buckets), "samples": used, "padded_samples": padded_total,
-                 "padded_step_waste": 1.0 - used / float(max(padded_total, 1)), "failed": cls.failed_reads(nsamp), "streamed": True}
-        return scores, paths, nsamp, stats
+                flags[i] = int(fb[j])
+                if not flags[i]:
+                    nsamp[i] = int(ns[j])
+                    scores[i] = sc[j]
+                    paths[i] = pa[j, :le[j]].copy()
+        cls._report_failures(flags)
+        return scores, paths, nsamp, len(buckets), sum(lmax * len(idx) for idx, _, _, _, lmax in pending)
 
     def call_chunks_host(self, chunks):
         scores, paths, lens = self.call_chunks(chunks)

@@ -14,7 +14,8 @@ def geometric_prior(n, m, rev=False):
 
 
 def trim_array(x, from_start, from_end):
-    """`x` without its first `from_start` and last `from_end` entries (a view); negative counts are refused."""
+    """`x` without its first `from_start` and last `from_end` entries (a view; empty when they overlap, as the reference's
+    `x[from_start:-from_end]`); negative counts are refused."""
     if from_start < 0 or from_end < 0:
         raise AssertionError("trim counts must not be negative")
-    return x[from_start:len(x) - from_end]
+    return x[from_start:max(from_start, len(x) - from_end)]

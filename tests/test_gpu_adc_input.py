@@ -152,6 +152,15 @@ def test_call_reads_real_reads_equal_picoampere_path(fraction):
         bc.call_reads([adc[0], adc[0][:300]], trim=(200, 100), scaling=trip[:2])
     with pytest.raises(ValueError, match="empty read after trimming"):
         bc.call_reads([pa[0], pa[0][:300]], trim=(200, 100))
+    # more taken off the end than the read holds: nothing left (the reference's x[a:-b]), not samples from the wrong end
+    with pytest.raises(ValueError, match="empty read after trimming"):
+        bc.call_reads([adc[0], adc[0][:300]], trim=(0, 400), scaling=trip[:2])
+    with pytest.raises(ValueError, match="empty read after trimming"):
+        bc.call_reads([pa[0], pa[0][:300]], trim=(0, 400))
+    nan_read = pa[0].copy()
+    nan_read[1234] = np.nan
+    with pytest.raises(ValueError, match="read 1 holds samples that are not finite"):
+        bc.call_reads([pa[0], nan_read])
     with pytest.raises(TypeError):
         bc.call_reads([pa[0]], scaling=trip[:1])                                        # float64 samples with a scaling
 

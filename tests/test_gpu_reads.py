@@ -193,8 +193,8 @@ def test_bucketed_whole_read_mode_equals_single_reads():
 @pytest.mark.parametrize("fraction", [0.0, 0.3])
 def test_a_read_that_fails_is_skipped_and_the_others_are_unaffected(fraction, stream_buckets, capsys):
     """sloika/basecall.py:103-115: the reference's worker reports a read it cannot call and returns None; the pool goes on.  Here
-    such a read (a NaN or an infinity among its samples, fewer samples than one open-pore window) must not poison the ragged batch it
-    would have shared: it is left out, reported, and every other read gets bit for bit what it gets without it."""
+    such a read (a NaN or an infinity among its samples, fewer samples than one open-pore window, no sample at all) must not poison the
+    ragged batch it would have shared: it is left out, reported, and every other read gets bit for bit what it gets without it."""
     need_gpu()
     from sloika_amd import batch, models, pipeline
     net = models.randomise_zero_layers(models.build_model("raw_0.98_rgrgr", klen=5, sd=0.5, seed=17))
@@ -205,8 +205,9 @@ def test_a_read_that_fails_is_skipped_and_the_others_are_unaffected(fraction, st
     nan_read[1234] = np.nan
     inf_read = good[5].copy()
     inf_read[7] = np.inf
-    reads = good[:3] + [nan_read] + good[3:6] + [good[0][:60]] + good[6:] + [inf_read]
-    bad_idx = [3, 7, len(reads) - 1]
+    # (the two empty reads and the 60-sample one would be the last bucket of the streamed flow, which buckets by raw length)
+    reads = good[:3] + [nan_read] + good[3:6] + [good[0][:60], good[4][:0]] + good[6:] + [inf_read, good[1][:0]]
+    bad_idx = [3, 7, 8, 12, 13]
     kw = dict(max_batch=4, max_waste=0.2, in_flight=2, kmer_len=5, skip=0.0, open_pore_fraction=fraction, stream_buckets=stream_buckets)
     scores, paths, nsamp, stats = pipeline.Basecaller.call_reads_bucketed(net, reads, **kw)
     assert bool(stats.get("streamed")) == (stream_buckets and fraction == 0.0)
@@ -215,6 +216,7 @@ def test_a_read_that_fails_is_skipped_and_the_others_are_unaffected(fraction, st
     for i in bad_idx:
         assert paths[i] is None and np.isnan(scores[i]) and nsamp[i] == 0
         assert "Failure calling read %d" % i in err
+    assert "Failure calling read 8: too short to trim the open pore" in err and "Failure calling read 13: too short" in err
     s2, p2, n2, st2 = pipeline.Basecaller.call_reads_bucketed(net, good, **kw)
     assert st2["failed"] == []
     keep = [i for i in range(len(reads)) if i not in bad_idx]

@@ -121,6 +121,41 @@ def test_util(golden_transducer):
     assert np.array_equal(util.geometric_prior(30, 2.0, rev=True), golden_transducer["geometric_prior_30_2_rev"])
     x = np.arange(20)
     assert np.array_equal(util.trim_array(x, 2, 3), x[2:-3]) and np.array_equal(util.trim_array(x, 0, 0), x)
+    assert len(util.trim_array(x, 0, 25)) == 0 and len(util.trim_array(x, 5, 15)) == 0 and len(util.trim_array(x, 30, 0)) == 0
+
+
+def test_read_spans_layout_and_buckets():
+    """The host rules of the whole-read flows: read_spans trims as util.trim_array does and flags a read as slk_open_pore_trim_f32
+    does; read_layout / fill_staging lay a read set out in whole windows; length_buckets takes every read once."""
+    from sloika_amd import batch, pipeline, util
+    trim = (50, 60)
+    bounds = [(0, 300), None, (100, 500), None, (200, 300), (0, 110), (0, 111), (0, 100)]
+    bad = [False, False, True, True, False, False, False, False]
+    start, lengths, flags = batch.read_spans(bounds, bad, trim)
+    assert flags == [0, 2, 1, 3, 4, 4, 0, 4]
+    assert start == [50, 0, 0, 0, 0, 0, 50, 0] and lengths == [190, 0, 0, 0, 0, 0, 1, 0]
+    for bd, n, f in zip(bounds, lengths, flags):
+        if bd is not None and not f & 1:
+            assert len(util.trim_array(np.arange(bd[1] - bd[0]), *trim)) == n
+    assert batch.read_spans([(0, 100)], [False], (0, 400))[2] == [4]
+    assert [batch.read_failure(f)[1] if f else None for f in flags] == [
+        None, "too short to trim the open pore", "samples that are not finite", "samples that are not finite",
+        "nothing left after trimming", "nothing left after trimming", None, "nothing left after trimming"]
+    with pytest.raises(AssertionError):
+        batch.read_spans(bounds, bad, (0, -1))
+    sigs = [np.zeros(0), np.arange(1, 2), np.arange(1, 101), np.arange(1, 102)]
+    strides, off = batch.read_layout([len(s) for s in sigs], 100)
+    assert strides.tolist() == [0, 100, 100, 200] and off.tolist() == [0, 0, 100, 200, 400]
+    for dtype in (np.float32, np.int16):
+        hv = np.full(int(off[-1]), 7, dtype=dtype)
+        batch.fill_staging(hv, sigs, off, 0, len(sigs))
+        for r, s in enumerate(sigs):
+            assert np.array_equal(hv[off[r]: off[r] + len(s)], s)
+            assert (hv[off[r] + len(s): off[r + 1]] == (0 if dtype == np.float32 else 7)).all()     # int16: the device writes the pad
+    nsamp = [5000, 4000, 4990, 300, 4995, 4000]
+    buckets = pipeline.Basecaller.length_buckets(nsamp, 2, 0.08)
+    assert sorted(i for b in buckets for i in b) == list(range(len(nsamp))) and max(len(b) for b in buckets) <= 2
+    assert buckets[0] == [0, 4] and buckets[-1] == [3]
 
 
 def test_synthetic_chunks_deterministic():

@@ -20,7 +20,7 @@ def main():
     for rep in range(3):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        dev, off, lens = batch.upload_reads_windowed(reads)
+        dev, off, lens, _ = batch.upload_read_set(reads)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         bounds = batch.open_pore_bounds_many(dev, off, lens, 0.0)
@@ -31,7 +31,7 @@ def main():
         batches, nsamp2 = pipeline.Basecaller.prepare_read_batches(net, reads, max_batch=256, max_waste=0.08, kmer_len=5, skip=0.0)
         torch.cuda.synchronize()
         t4 = time.perf_counter()
-        print("reads %d (%.0f M samples): pack + upload %.3f s, bounds %.3f s, bucketing %.3f s | whole prepare_read_batches %.3f s (%d batches)"
+        print("reads %d (%.0f M samples): pack + upload + non-finite check %.3f s, bounds %.3f s, bucketing %.3f s | whole prepare_read_batches %.3f s (%d batches)"
               % (n, sum(lens) / 1e6, t1 - t0, t2 - t1, t3 - t2, t4 - t3, len(batches)), flush=True)
 
 

@@ -53,10 +53,8 @@ def tick(label, t0):
 for rep in range(3):
     print("pass %d" % rep)
     t0 = t = time.perf_counter()
-    dev, off, lens = batch.upload_reads_windowed(reads)
-    t = tick("upload_reads_windowed", t)
-    bad = batch.reads_nonfinite(dev, off, lens)
-    t = tick("reads_nonfinite", t)
+    dev, off, lens, bad = batch.upload_read_set(reads)
+    t = tick("upload + non-finite check", t)
     bounds = batch.open_pore_bounds_many(dev, off, lens, 0.0)
     t = tick("open_pore_bounds_many", t)
     del dev
