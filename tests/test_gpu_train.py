@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+from tests import ref_reverse_scans
 from tests.gpu_util import need_gpu, dev, stream
 
 pytestmark = pytest.mark.gpu
@@ -303,9 +304,9 @@ def test_argument_validation():
 
 @pytest.mark.parametrize("n,reverse", [(96, 0), (32, 1), (144, 1)])
 def test_gru_backward_kernels_agree(n, reverse):
-    """The reverse scan has two kernels: operands through an LDS-DMA loader wave (16-byte aligned rows) and a plain one
-    (any alignment).  Same inputs, dy once aligned and once shifted by one float: the same pre-activation gradients, and
-    both equal the float64 recursion of oracle_train._backward's GRU step (the candidate c is handed over implicitly,
+    """The reverse scan has three kernels: for 16-byte aligned rows the MFMA one (n <= 112: 96 and 32 here) or the one with an
+    LDS-DMA loader wave (144 here), and a plain one (any alignment).  Same inputs, dy once aligned and once shifted by one
+    float: the same pre-activation gradients, and both equal the float64 recursion of oracle_train._backward's GRU step (the candidate c is handed over implicitly,
     through the layer output h_t = z h + (1-z) c)."""
     torch = need_gpu()
     from sloika_amd import _lib
@@ -319,20 +320,8 @@ def test_gru_backward_kernels_agree(n, reverse):
     c = rs.uniform(-0.95, 0.95, size=(M, n)).astype(np.float32)
     sW = (rs.normal(size=(2 * n, n)) / np.sqrt(n)).astype(np.float32)
     sW2 = (rs.normal(size=(n, n)) / np.sqrt(n)).astype(np.float32)
-    # float64 recursion
-    want = np.zeros((M, 3 * n))
-    carry = np.zeros((B, n))
-    for s in range(T - 1, -1, -1):
-        t = T - 1 - s if reverse else s
-        rows = slice(t * B, (t + 1) * B)
-        g = dy[rows] + carry
-        z, r, h, cc = zr[rows, :n].astype(np.float64), zr[rows, n:].astype(np.float64), xh[rows, I:].astype(np.float64), c[rows].astype(np.float64)
-        dac = g * (1 - z) * (1 - cc * cc)
-        daz = g * (h - cc) * z * (1 - z)
-        drh = dac @ sW2
-        dar = drh * h * r * (1 - r)
-        carry = g * z + drh * r + np.concatenate([daz, dar], 1) @ sW
-        want[rows] = np.concatenate([daz, dar, dac], 1)
+    # float64 recursion (tests/ref_reverse_scans.py), on the TRUE candidate
+    want, _ = ref_reverse_scans.gru_reverse_scan(dy, zr[:, :n], zr[:, n:], c, xh[:, I:], sW, sW2, T, B, reverse)
     # the kernels take the layer's forward output h_t = z h + (1-z) c and recover the candidate from it
     hout = (zr[:, :n] * xh[:, I:] + (1.0 - zr[:, :n]) * c).astype(np.float32)
     d = {k: dev(v) for k, v in dict(xh=xh, zr=zr, hout=hout, sW=sW, sW2=sW2).items()}
