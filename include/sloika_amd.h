@@ -140,6 +140,22 @@ SLK_API int slk_open_pore_trim_f32(const float *spread, const int64_t *first_win
 /* Standard deviation of each of nwin consecutive windows of `win` samples (population form, numpy's .std()):
  * batch.trim_open_pore(var_method='std'), sloika/batch.py:210-211.  out:[nwin].                                    */
 SLK_API int slk_window_std_f32(const float *signal, int nwin, int win, float *out, slk_stream_t stream);
+/* a1 for the event models: features.from_events (sloika/features.py:6-32) with maths.studentise (sloika/maths.py:48-58) for a ragged
+ * set of `nseg` segments in one launch.  mean, stdv, length: the event table's columns, all three float32 (columns_f64 == 0) or all
+ * three float64 (columns_f64 != 0).  Segment s is the events seg_start[s] .. seg_start[s] + seg_len[s] - 1: a whole read, or one
+ * chunk's window of a read (batch.chunkify 'per-chunk', sloika/batch.py:37-49).  Its rows are
+ *     [mean, stdv, length, |mean[e+1] - mean[e]|]   as float32, the last row's fourth column 0 (features.py:17-22);
+ * with `normalise` every column is studentised over the WHOLE segment (population standard deviation, one that is not > 0 replaced
+ * by 1); with `nanonet` the fourth column is the signed delta over its own standard deviation instead (features.py:27-30).  Only the
+ * first seg_keep[s] rows are written (seg_keep[s] > seg_len[s] counts as seg_len[s]): row i, column c of segment s goes to
+ *     out[4 * out_row[s] + i * ld_out + c]
+ * (ld_out = 4 and out_row = the segment's first row for a dense [rows][4] matrix; ld_out = 4 * B and out_row = b for column b of a
+ * [T][B][4] network input).  ld_out is a multiple of 4 and `out` 16-byte aligned: a row is one 16-byte store.  Nothing else is
+ * written.  Moments are accumulated in float64 in an order that depends on the segment alone, the result is rounded to float32 once:
+ * a segment gets the same bits whatever shares the launch.  Any seg_len >= 1 (a segment of length 0 writes nothing), nseg < 2^31. */
+SLK_API int slk_event_features_f32(const void *mean, const void *stdv, const void *length, int columns_f64, const int64_t *seg_start,
+                                   const int64_t *seg_len, const int64_t *seg_keep, int64_t nseg, int normalise, int nanonet,
+                                   float *out, const int64_t *out_row, int64_t ld_out, slk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * a3. Convolution.run  (sloika/layers.py:417-419 -> sloika/conv.py:66-77,90-111)

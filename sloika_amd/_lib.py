@@ -31,6 +31,7 @@ PROTOTYPES = {
     "slk_med_mad_normalise_f32": (_i, [_vp, _i, _i, _vp, _l, _l, _vp, _vp, _vp]),
     "slk_med_mad_normalise_ragged_f32": (_i, [_vp, _i, _l, _vp, _vp, _l, _l, _vp, _vp, _vp]),
     "slk_window_std_f32": (_i, [_vp, _i, _i, _vp, _vp]),
+    "slk_event_features_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, C.c_int64, _i, _i, _vp, _vp, C.c_int64, _vp]),
     "slk_conv1d_out_len": (_i, [_i, _i, _i, _i, _i]),
     "slk_conv1d_f32": (_i, [_vp, _l, _l, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "slk_window_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),

@@ -2,6 +2,7 @@
 
     decode_post(post, kmer_len, transducer, bad, min_prob, skip, ...)   basecall.py:26-51
     raw_chunk_worker(calc_post, chunks, ...)                            batched counterpart of raw_worker :88-121
+    events_read_worker / events_worker                                  basecall.py:54-85 (features made on the device)
     SeqPrinter                                                          basecall.py:124-163
 """
 import sys
@@ -89,6 +90,51 @@ def raw_worker(fast5_file_name, trim, open_pore_fraction, kmer_len, transducer, 
         return None
     return raw_read_worker(calc_post, signal, trim=trim, open_pore_fraction=open_pore_fraction, kmer_len=kmer_len,
                            min_prob=min_prob, skip=skip, nbase=len(alphabet), name=sn)
+
+
+def _trim_table(ev, from_start, from_end):
+    """util.trim_array on an event table: a structured array, or a dict of equally long columns."""
+    from . import util
+    if isinstance(ev, dict):
+        return {k: util.trim_array(np.asarray(v), from_start, from_end) for k, v in ev.items()}
+    return util.trim_array(ev, from_start, from_end)
+
+
+def events_read_worker(calc_post, ev, trim=(0, 0), kmer_len=5, min_prob=1e-5, skip=5.0, nbase=4, name="read"):
+    """The array part of events_worker (basecall.py:77-85) for ONE event table held in memory (the reference reads it from a fast5
+    file first): trim_array, features.from_events(tag='') made on the device, calc_post on [nev, 1, 4], decode_post.
+    Returns (name, score, call, n_events) or None for a table with nothing left, like the reference."""
+    from . import features
+    ev = _trim_table(ev, *trim)                                             # basecall.py:77
+    if len(features.event_columns(ev, '')[0]) == 0:
+        sys.stderr.write("Read too short in {}\n".format(name))
+        return None
+    inmat = features.from_events(ev, tag='', device=True)[:, None, :]       # basecall.py:82
+    post = calc_post(inmat)
+    score, call = decode_post(post, kmer_len, True, True, min_prob, skip=skip, nbase=nbase)
+    return name, score, call, int(inmat.shape[0])
+
+
+def events_worker(fast5_file_name, section, segmentation, trim, kmer_len, transducer, bad, min_prob, alphabet=DEFAULT_ALPHABET,
+                  skip=5.0, trans=None, calc_post=None):
+    """Worker for basecalling one single-read fast5 file from its event table (basecall.py:54-85), same arguments and return value
+    `(name, score, call, n_events)` / `None`.  The file is read with sloika_amd.fast5 (no h5py/libhdf5 needed); `calc_post` is the
+    compiled model (the reference keeps it in a process global set by init_worker, :12-23)."""
+    import os
+    from . import fast5
+    if calc_post is None:
+        calc_post = globals().get("calc_post")
+    if calc_post is None:
+        raise ValueError("events_worker needs a compiled model: pass calc_post= or call init_worker first")
+    if trans is not None or not transducer or not bad:
+        raise NotImplementedError("only the transducer decode with a bad-state column is on the GPU path")
+    try:
+        ev = fast5.Fast5(fast5_file_name).get_section_events(section, analysis=segmentation)
+        sn = os.path.splitext(os.path.basename(fast5_file_name))[0]
+    except Exception as e:                                           # basecall.py:73-75
+        sys.stderr.write("Error getting events for section {!r} in file {}\n{!r}\n".format(section, fast5_file_name, e))
+        return None
+    return events_read_worker(calc_post, ev, trim=trim, kmer_len=kmer_len, min_prob=min_prob, skip=skip, nbase=len(alphabet), name=sn)
 
 
 def init_worker(model):

@@ -3,6 +3,7 @@
     chunkify_signal(signal, chunk_len)             cut a read into [ml, chunk_len] chunks (chunkify_raw.py:172-176)
     normalise_chunks(chunks, 'per-chunk'|...)      median/MAD normalisation (chunkify_raw.py:178-185)
     chunks_to_network_input(chunks)                [ml, chunk_len] -> [chunk_len, ml, 1] (bin/train_network.py:304)
+    trim_ends_and_filter, chunkify, chunkify_many  chunks of event tables with their labels (batch.py:23-87)
 """
 import contextlib
 import os
@@ -457,3 +458,103 @@ def init_chunk_remap_worker(model, kmer_len, alphabet):
     init_chunk_identity_worker(kmer_len, alphabet)
     net = model if isinstance(model, layers.Layer) else helpers.load_model(model)
     calc_post = net.compile()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# chunks of event tables (sloika/batch.py:23-87): features by csrc/event_features.hip, labels by csrc/chunk_labels.hip
+# ---------------------------------------------------------------------------------------------------------------------------
+
+def trim_ends_and_filter(ev, trim, min_length, chunk_len):
+    """sloika/batch.py:23-27: `ev` without its first trim[0] and last trim[1] events, or None when it is shorter than `min_length` or
+    would not fill one chunk."""
+    from . import util
+    if len(ev) < sum(trim) + chunk_len or len(ev) < min_length:
+        return None
+    return util.trim_array(ev, *trim)
+
+
+def event_segments(nev, chunk_len, normalisation, first_event=0, first_row=0):
+    """The segments slk_event_features_f32 takes for chunkify's features of ONE read of `nev` events (sloika/batch.py:37-60):
+    -> (start, length, keep, out_row) int64 arrays, `normalise`.  'per-chunk': one segment per chunk, chunk_len + 1 events long
+    where the read has one more (the delta of the chunk's last event, and that event in the chunk's moments: batch.py:43-48), chunk_len
+    rows kept.  'none' / 'per-read': the whole read as one segment (moments over ALL its events), the first ml * chunk_len rows kept.
+    first_event / first_row: where the read's events and its rows start in a set of reads (chunkify_many)."""
+    if normalisation not in AVAILABLE_NORMALISATIONS:
+        raise ValueError("normalisation must be one of %s" % sorted(AVAILABLE_NORMALISATIONS))
+    if chunk_len < 1 or nev < chunk_len:
+        raise ValueError("a read of %d events does not fill a chunk of %d" % (nev, chunk_len))
+    ml = nev // chunk_len
+    if normalisation == 'per-chunk':
+        start = np.arange(ml, dtype=np.int64) * chunk_len
+        length = np.minimum(start + chunk_len + 1, nev) - start
+        keep = np.full(ml, chunk_len, dtype=np.int64)
+        return start + first_event, length, keep, start + first_row, True
+    one = np.ones(1, dtype=np.int64)
+    return one * first_event, one * nev, one * (ml * chunk_len), one * first_row, normalisation == 'per-read'
+
+
+def _kmer_text(ev, n):
+    """The first n entries of the table's 'kmer' column as bytes: -> (contiguous 'S<k>' array, k)."""
+    kmers = np.asarray(ev['kmer'][:n])
+    if kmers.dtype.kind == 'U':
+        kmers = kmers.astype('S')
+    if kmers.dtype.kind != 'S':
+        raise TypeError("the 'kmer' column must hold fixed-length strings")
+    return np.ascontiguousarray(kmers), kmers.dtype.itemsize
+
+
+def chunkify_many(evs, chunk_len, kmer_len, use_scaled, normalisation, on_device=False):
+    """chunkify for a list of event tables: the features of ALL reads are one launch of slk_event_features_f32, the labels one launch
+    of slk_kmer_labels_i32 (compare chunkify_raw.raw_chunkify_many).  -> a list of (chunks, labels, bad) per read, each what
+    chunkify gives for that read alone, bit for bit -- numpy arrays, or device tensors with on_device=True."""
+    import torch
+    from . import chunkify_raw, device as D, features
+    if len(evs) == 0:
+        raise ValueError("chunkify_many needs at least one event table")
+    tag = 'scaled_' if use_scaled else ''
+    nev = [len(ev['length']) for ev in evs]                    # (a structured array or a dict of columns)
+    for n in nev:
+        assert n >= chunk_len                                                         # batch.py:31
+    ml = [n // chunk_len for n in nev]
+    row_off = np.concatenate([[0], np.cumsum([m * chunk_len for m in ml])]).astype(np.int64)
+    cols, off = features.upload_tables(evs, tag)
+    segs = [event_segments(n, chunk_len, normalisation, int(off[r]), int(row_off[r])) for r, n in enumerate(nev)]
+    total = int(row_off[-1])
+    feats = torch.empty((total, 4), dtype=torch.float32, device=cols.device)
+    features.launch(cols, *(np.concatenate([s[k] for s in segs]) for k in range(4)), feats, 4, normalise=segs[0][4])
+    # labels: the rightmost middle k-mer's state + 1 (batch.py:69-73), 0 where the position did not change inside a chunk (:75-78)
+    texts = [_kmer_text(ev, m * chunk_len) for ev, m in zip(evs, ml)]
+    old_len = texts[0][1]
+    if any(k != old_len for _, k in texts):
+        raise ValueError("the event tables hold k-mers of different lengths")
+    assert kmer_len <= old_len
+    alphabet = chunkify_raw._alphabet(kmer_len)
+    text = torch.from_numpy(np.frombuffer(b''.join(t.tobytes() for t, _ in texts), dtype=np.uint8).copy()).to(cols.device)
+    labels = torch.empty(total, dtype=torch.int32, device=cols.device)
+    status = torch.zeros(1, dtype=torch.int32, device=cols.device)
+    _lib.check(_lib.lib().slk_kmer_labels_i32(text.data_ptr(), total, old_len, kmer_len, alphabet, len(alphabet), 1,
+                                              labels.data_ptr(), status.data_ptr(), D.stream_ptr()), "chunkify.kmer_labels")
+    seq_pos = torch.from_numpy(np.concatenate([np.asarray(ev['seq_pos'][:m * chunk_len], dtype=np.int64)
+                                               for ev, m in zip(evs, ml)])).to(cols.device)
+    stay = torch.zeros(total, dtype=torch.bool, device=cols.device)
+    stay[1:] = seq_pos[1:] == seq_pos[:-1]
+    stay[::chunk_len] = False                          # (ediff1d(..., to_begin=1): a chunk's first event always keeps its label)
+    labels[stay] = 0
+    chunkify_raw._status(status, "chunkify")
+    out = []
+    for r, ev in enumerate(evs):
+        lo, hi = int(row_off[r]), int(row_off[r + 1])
+        bad = np.logical_not(np.asarray(ev['good_emission'][:hi - lo])).reshape(ml[r], chunk_len)      # batch.py:80-81
+        c, lab = feats[lo:hi].reshape(ml[r], chunk_len, 4), labels[lo:hi].reshape(ml[r], chunk_len)
+        if on_device:
+            out.append((c, lab, torch.from_numpy(bad).to(cols.device)))
+        else:
+            out.append((c.cpu().numpy(), lab.cpu().numpy(), bad))
+    return out
+
+
+def chunkify(ev, chunk_len, kmer_len, use_scaled, normalisation):
+    """sloika/batch.py:30-87: the first ml * chunk_len events of the table `ev` (columns 'mean' / 'stdv' or their 'scaled_' twins,
+    'length', 'kmer', 'seq_pos', 'good_emission') as training chunks: -> (chunks [ml, chunk_len, 4] float32, labels [ml, chunk_len]
+    int32, bad [ml, chunk_len] bool).  The k-mer -> state mapping is the one init_chunk_identity_worker set (b'ACGT' otherwise)."""
+    return chunkify_many([ev], chunk_len, kmer_len, use_scaled, normalisation)[0]

@@ -167,7 +167,39 @@ class HDF5File(object):
             kind = "vlen_string" if (bits0 & 0x0F) == 1 else "vlen"
             _k, _d, _s, used = self._datatype(body, pos + 8)
             return kind, None, size, 8 + used
+        if cls == 6:                                         # compound: a record of named members (an event table's row)
+            return self._compound(body, pos, cv >> 4, size)
         raise Fast5Error("datatype class %d is not supported" % cls)
+
+    def _compound(self, body, pos, version, size):
+        """Compound datatype (IV.A.2.d, class 6) -> ("compound", numpy structured dtype, size, bytes consumed).  Members may be fixed
+        point, floating point or fixed-length strings (numpy 'S'); anything else (arrays, nested records, variable length) is refused."""
+        if version not in (1, 2, 3):
+            raise Fast5Error("compound datatype version %d is not supported" % version)
+        nmemb, = struct.unpack_from("<H", body, pos + 1)
+        offbytes = 4 if version < 3 else max(1, (max(size, 1).bit_length() + 7) // 8)
+        p = pos + 8
+        names, formats, offsets = [], [], []
+        for _ in range(nmemb):
+            end = body.index(b"\0", p)
+            name = body[p:end].decode("utf-8")
+            p = p + ((end - p) // 8 + 1) * 8 if version < 3 else end + 1          # (versions 1 and 2 pad the name to 8 bytes)
+            offset = int.from_bytes(body[p:p + offbytes], "little")
+            p += offbytes
+            if version == 1:
+                if body[p] != 0:
+                    raise Fast5Error("array members of a compound datatype are not supported (%s)" % name)
+                p += 28                                       # dimensionality, reserved, permutation, reserved, four sizes
+            kind, dtype, msize, used = self._datatype(body, p)
+            p += used
+            if kind == "string":
+                dtype = np.dtype("S%d" % msize)
+            elif kind not in ("int", "float"):
+                raise Fast5Error("compound member %s of kind %s is not supported" % (name, kind))
+            names.append(name)
+            formats.append(dtype)
+            offsets.append(offset)
+        return "compound", np.dtype({"names": names, "formats": formats, "offsets": offsets, "itemsize": size}), size, p - pos
 
     @staticmethod
     def _dataspace(body):
@@ -200,7 +232,7 @@ class HDF5File(object):
 
     def _decode(self, kind, dtype, size, dims, raw):
         n = int(np.prod(dims)) if dims else 1
-        if kind in ("int", "float"):
+        if kind in ("int", "float", "compound"):
             arr = np.frombuffer(raw, dtype=dtype, count=n)
             return arr.reshape(dims) if dims else arr[0]
         if kind == "string":
@@ -371,3 +403,54 @@ class Fast5(object):
                 if len(lines) >= 4:
                     return lines[0][1:], lines[1], lines[3]
         return None
+
+    # ---- event tables (the `events` sub-commands: sloika/basecall.py:69-75, sloika/batch.py:166-171) ----
+    def _latest(self, analysis):
+        """The group Analyses/<analysis>_NNN with the highest number."""
+        analyses = self.h5.root["Analyses"] if "Analyses" in self.h5.root else None
+        names = [] if analyses is None else sorted(k for k in analyses.keys() if k.startswith(analysis + "_") and k[len(analysis) + 1:].isdigit())
+        if not names:
+            raise Fast5Error("%s holds no %s analysis" % (self.path, analysis))
+        return "Analyses/" + names[-1]
+
+    def get_events(self, group=None):
+        """The event table the event detection stored for the (single) read (`group`: e.g. 'Analyses/EventDetection_000', default: the
+        latest), as a numpy structured array.  'start' and 'length' stored as whole samples are returned in seconds (float64, divided by
+        the sampling rate), as the event models were trained on them; the other columns are left as they are."""
+        reads = self.h5.root[(group or self._latest("EventDetection")) + "/Reads"]
+        names = reads.keys()
+        if not names:
+            raise Fast5Error("%s holds no detected events" % self.path)
+        ev = self.h5.read(reads[names[0]]["Events"])
+        if not isinstance(ev, np.ndarray) or ev.dtype.names is None:
+            raise Fast5Error("the event table of %s is not a table" % self.path)
+        timed = [n for n in ("start", "length") if n in ev.dtype.names and ev.dtype[n].kind in "iu"]
+        out = np.empty(ev.shape, dtype=[(n, "<f8" if n in timed else ev.dtype[n]) for n in ev.dtype.names])
+        for n in ev.dtype.names:
+            out[n] = ev[n] / self.sample_rate if n in timed else ev[n]
+        return out
+
+    def get_section_events(self, section, analysis="Segment_Linear"):
+        """The events of one section of the read ('template' or 'complement') as the segmentation analysis `analysis` split them:
+        rows start_index_<temp|comp> .. end_index_<temp|comp> - 1 of the event table the analysis worked on (its 'event_detection'
+        attribute), from the attributes under Analyses/<analysis>_NNN/Summary/split_adapter.  ValueError when the analysis found no
+        such section (the reference's callers fall back on ValueError, sloika/batch.py:168-171)."""
+        if section not in ("template", "complement"):
+            raise ValueError("section must be 'template' or 'complement', got %r" % (section,))
+        grp = self._latest(analysis)
+        node = self.h5.root[grp]
+        if "Summary/split_adapter" not in node:
+            raise ValueError("%s has no split_adapter summary under %s" % (self.path, grp))
+        summary = node["Summary/split_adapter"].attrs
+        tag = "temp" if section == "template" else "comp"
+        try:
+            first, last, count = (int(summary[k + tag]) for k in ("start_index_", "end_index_", "num_"))
+        except KeyError as e:
+            raise ValueError("%s: the split_adapter summary lacks %s" % (self.path, e))
+        if count < 1 or last <= first:
+            raise ValueError("%s holds no %s section" % (self.path, section))
+        ev = self.get_events(node.attrs.get("event_detection"))
+        if last > len(ev) or last - first != count:
+            raise Fast5Error("%s: the %s section (%d .. %d, %d events) does not fit its event table of %d" %
+                             (self.path, section, first, last, count, len(ev)))
+        return ev[first:last]

@@ -332,6 +332,77 @@ class Basecaller(object):
         scores, paths, lens = self._call_padded(batch.pack_batch(dev, start, nsamp, max(nsamp)), nsamp)
         return scores, paths, lens, nsamp
 
+    def call_events(self, tables, trim=(0, 0), tag=''):
+        """Event tables of different lengths in ONE batch, for the models that take event features (the reference calls them one at a
+        time, basecall.py:54-85): `tables` is a list of event tables (numpy structured arrays or dicts of columns tag + 'mean',
+        tag + 'stdv', 'length'); each is trimmed as events_worker does (basecall.py:77) and its features, studentised over its own
+        events, are written by slk_event_features_f32 straight into the zero-padded [T, B, 4] network input -- all tables in one launch.
+        Network and decoder run with per-read lengths (layers.ragged); the decoder is the one that reads the Softmax layer's logits,
+        which is bit for bit basecall.decode_post on the posterior, so every read gets exactly what basecall.events_read_worker gives
+        for it alone.
+        -> device tensors (scores [B], paths [B, Tmax] (-1 padded), lens [B]) and the per-read event counts after trimming.
+        A table with no event left after trimming, or one that holds a value that is not finite, is left out of the batch and reported
+        on stderr as the reference's worker reports a read it skips (basecall.py:78-80): score NaN, no path, event count 0; the other
+        reads are unaffected."""
+        import torch
+        from . import device as D, features
+        net = self.network
+        if not isinstance(net, layers.Serial) or type(net.layers[-1]) is not layers.Softmax:
+            raise ValueError("call_events needs a Serial network ending in a Softmax layer")
+        if net.layers[0].insize != 4:
+            raise ValueError("call_events needs a network that takes the 4 event features, this one takes %d" % net.layers[0].insize)
+        assert trim[0] >= 0 and trim[1] >= 0
+        cols = [features.event_columns(ev, tag) for ev in tables]
+        nev = [max(0, c.shape[1] - trim[0] - trim[1]) for c in cols]
+        flags = [(0 if np.isfinite(c).all() else 1) | (0 if n > 0 else 4) for c, n in zip(cols, nev)]
+        self._report_failures(flags)
+        nev = [0 if f else n for f, n in zip(flags, nev)]
+        good = [r for r, f in enumerate(flags) if not f]
+        ntab = len(tables)
+        if not good:
+            dev = D.device()
+            return (torch.full((ntab,), float("nan"), device=dev), torch.full((ntab, 0), -1, dtype=torch.int32, device=dev),
+                    torch.zeros((ntab,), dtype=torch.int32, device=dev), nev)
+        scores, paths, lens = self._call_event_batch([{"mean": cols[r][0], "stdv": cols[r][1], "length": cols[r][2]} for r in good],
+                                                     [nev[r] for r in good], int(trim[0]))
+        if len(good) == ntab:
+            return scores, paths, lens, nev
+        idx = torch.as_tensor(good, device=scores.device)
+        all_scores = torch.full((ntab,), float("nan"), dtype=scores.dtype, device=scores.device)
+        all_paths = torch.full((ntab, paths.shape[1]), -1, dtype=paths.dtype, device=scores.device)
+        all_lens = torch.zeros((ntab,), dtype=lens.dtype, device=scores.device)
+        all_scores[idx], all_paths[idx], all_lens[idx] = scores, paths, lens
+        return all_scores, all_paths, all_lens, nev
+
+    def _call_event_batch(self, tables, nev, skip_events):
+        if self._arena is None:
+            return self._call_event_pass(tables, nev, skip_events)
+        with self._arena:
+            return self._call_event_pass(tables, nev, skip_events)
+
+    def _call_event_pass(self, tables, nev, skip_events):
+        """call_events on tables that can be called: table b's events skip_events .. skip_events + nev[b] - 1 become column b."""
+        import torch
+        from . import device as D, features
+        net = self.network
+        B, tmax = len(tables), max(nev)
+        cols, off = features.upload_tables(tables, '')
+        x = D.scratch((tmax, B, 4), torch.float32, cols.device).zero_()
+        features.launch(cols, off[:-1] + skip_events, nev, nev, np.arange(B), x, 4 * B, normalise=True)
+        keep = layers._HINTS.in_flight, layers._HINTS.deterministic
+        layers._HINTS.in_flight, layers._HINTS.deterministic = 1, self.deterministic
+        try:
+            with layers.ragged(nev):
+                hid = x
+                for layer in net.layers[:-1]:
+                    hid = layer._forward(hid, None, False)
+                lengths = layers.ragged.current
+                logits, stats, ld = net.layers[-1].logits_and_stats(hid)
+        finally:
+            layers._HINTS.in_flight, layers._HINTS.deterministic = keep
+        return decode.viterbi_logits_batch(logits, stats, self.kmer_len, hid.shape[0], B, ld=ld, skip_pen=self.skip, nbase=self.nbase,
+                                           min_prob=self.min_prob, workspace=self._ws, lengths=lengths.contiguous())
+
     @staticmethod
     def _trimmed_read_set(signals, trim, open_pore_fraction, scaling):
         """The read set in ONE upload (batch.upload_read_set), the trimming bounds out of one launch over all windows
