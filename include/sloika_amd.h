@@ -390,6 +390,41 @@ SLK_API int slk_argmax_decode_f32(const float *post, int T, int B, int nstate, i
                           int32_t *len_out, slk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * a10. The decoder of NON-transducer models: what basecall.decode_post(transducer=False) runs (sloika/basecall.py:44, 47-50),
+ * batched over reads: decode.prepare_post(drop_bad=True) (sloika/decode.py:31-36), olddecode.estimate_transitions
+ * (sloika/olddecode.py:93-117), olddecode.decode_profile (:13-73) and, without weights, olddecode.decode_simple (:85-90).
+ * olddecode.decode_transition (:76-82) raises in the reference and has no entry point.
+ *   nbase 4 only (basecall.py:48), 3 <= klen <= 6; anything else: SLK_ERR_INVALID_ARG (workspace_bytes: 0).  N = 4^klen.
+ *   lens : NULL, or [B] int32 rows per read (0 <= lens[b] <= T) -- a ragged batch; read b then gets what a call on its first
+ *          lens[b] rows alone gives.  One workgroup per read: a read's bits do not depend on what shares the launch.
+ * slk_prepare_post_drop_bad_f32: post [T][B][N + 1] -> out [T][B][N]: of read b the rows whose FIRST maximum is not column 0,
+ *   left aligned, without column 0, divided by their float32 sum (taken in numpy's summation order) and floored with min_prob:
+ *   bit for bit what numpy writes.  kept[b] = rows written (rows behind them are not touched); kept_rows: NULL or [B][T], the
+ *   indices of the rows kept, -1 padded.  kept is the `lens` of the two calls below.
+ * slk_estimate_transitions_f64: post [T][B][N] float32, 16-byte aligned -> trans_out [B][T][3] float64 (stay, step, skip; rows
+ *   sum to 1; rows >= lens[b] are 0), sums in float64 where the reference sums in float32.  have_trans = 0: the prior is the read's own
+ *   normalised column sums (trans=None), else (t_stay, t_step, t_skip).  log_trans_out: NULL or [B][T][3], log(eta + trans) of the
+ *   same pass (basecall.py:50).
+ * slk_decode_profile_f64: post [T][B][N] float32, 16-byte aligned; input_mode SLK_POST_PLAIN (lp = log(post + 1e-10) in float32) or
+ *   SLK_POST_LOG; trans: NULL (decode_simple: no weights and then no log 4 / log 16 either, olddecode.py:27-32) or [B][T][3]
+ *   float64 LOG weights, row t - 1 used by step t; log_slip = log(1e-10 + slip).  The recurrence runs in float64 as numpy's does;
+ *   ties as the reference resolves them: of stay, slip, step, skip the last that reaches the maximum (np.where(score > new, ...)),
+ *   first maximum among the 4 step / 16 skip predecessors and for the slip source and the final state (np.argmax).  Path and
+ *   score are bit-exact functions of the log-posteriors and the weights.
+ *   score_out [B] float64 (NaN for an empty read); path_out [B][T] int32, one state per row, -1 padded; len_out [B] = lens.
+ *   workspace >= slk_decode_profile_workspace_bytes(T, B, nbase, klen), 16-byte aligned (a traceback byte per state and step).
+ * ------------------------------------------------------------------------------------------------------- */
+SLK_API int slk_prepare_post_drop_bad_f32(const float *post, int T, int B, int nbase, int klen, float min_prob, const int32_t *lens,
+                                  float *out, int32_t *kept, int32_t *kept_rows, slk_stream_t stream);
+SLK_API int slk_estimate_transitions_f64(const float *post, int T, int B, int nbase, int klen, int have_trans, double t_stay,
+                                 double t_step, double t_skip, double eta, const int32_t *lens, double *trans_out,
+                                 double *log_trans_out, slk_stream_t stream);
+SLK_API size_t slk_decode_profile_workspace_bytes(int T, int B, int nbase, int klen);
+SLK_API int slk_decode_profile_f64(const float *post, int T, int B, int nbase, int klen, int input_mode, const double *trans,
+                           double log_slip, const int32_t *lens, void *workspace, size_t workspace_bytes, double *score_out,
+                           int32_t *path_out, int32_t *len_out, slk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * f1. States -> bases (sloika/bio.py:160-179 max_overlap, :206-225 reduce_kmers, :228-237 kmers_to_sequence; what
  *   basecall.SeqPrinter.write does with a call, basecall.py:157-163), for a whole batch of decoded paths on the device.
  *   A state is the base-`nbase` number of its k-mer (first letter most significant, bio.py:12-24), so the overlap test

@@ -19,7 +19,7 @@ SLK_ERR_NO_DEVICE = -5
 
 POST_RAW, POST_PLAIN, POST_LOG, POST_LN = 0, 1, 2, 3
 
-_vp, _i, _l, _f, _sz = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
+_vp, _i, _l, _f, _sz, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t, C.c_double
 
 # name -> (restype, argtypes); mirrors include/sloika_amd.h one to one
 PROTOTYPES = {
@@ -76,6 +76,10 @@ PROTOTYPES = {
     "slk_log_post_f32": (_i, [_vp, _vp, _sz, _i, _f, _vp]),
     "slk_prepare_post_f32": (_i, [_vp, _vp, _sz, _f, _vp]),
     "slk_argmax_decode_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "slk_prepare_post_drop_bad_f32": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "slk_estimate_transitions_f64": (_i, [_vp, _i, _i, _i, _i, _i, _d, _d, _d, _d, _vp, _vp, _vp, _vp]),
+    "slk_decode_profile_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "slk_decode_profile_f64": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _d, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "slk_slip_update_f32": (_i, [_vp, _i, _f, _vp, _vp, _vp]),
     "slk_map_to_sequence_workspace_bytes": (_sz, [_i, _i]),
     "slk_map_to_sequence_f32": (_i, [_vp, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),

@@ -1,6 +1,6 @@
 """Worker-level API of the basecalling path (sloika/basecall.py), batched over chunks.
 
-    decode_post(post, kmer_len, transducer, bad, min_prob, skip, ...)   basecall.py:26-51
+    decode_post(post, kmer_len, transducer, bad, min_prob, skip, ...)   basecall.py:26-51 (transducer=False: olddecode's profile Viterbi)
     raw_chunk_worker(calc_post, chunks, ...)                            batched counterpart of raw_worker :88-121
     events_read_worker / events_worker                                  basecall.py:54-85 (features made on the device)
     SeqPrinter                                                          basecall.py:124-163
@@ -16,13 +16,18 @@ from .variables import DEFAULT_ALPHABET, nstate
 def decode_post(post, kmer_len, transducer=True, bad=True, min_prob=1e-5, skip=5.0, trans=None, nbase=4,
                 eta=1e-10):
     """Decode Viterbi state sequence from a [T,1,nstate] posterior (basecall.py:26-51): (score, path)."""
-    if not transducer:
-        raise NotImplementedError("the non-transducer decoder (sloika/olddecode.py) is outside the accelerated "
-                                  "path; bin/basecall_network.py defaults to --transducer")
     if post.shape[2] != nstate(kmer_len, transducer=transducer, bad_state=bad, nbase=nbase):
         raise ValueError("posterior does not have nstate(kmer_len) states")        # basecall.py:43
     if post.shape[1] != 1:
         raise ValueError("decode_post takes one read: [time, 1, state] (np.squeeze(axis=1), decode.py:30)")
+    if not transducer:
+        # basecall.py:44, 47-50: prepare_post(drop_bad=bad), olddecode.estimate_transitions, olddecode.decode_profile
+        from . import olddecode
+        scores, paths, lens = olddecode.decode_post_batch(post, kmer_len, bad=bad, min_prob=min_prob, trans=trans, nbase=nbase, eta=eta)
+        n = int(lens[0].item())
+        if n == 0:
+            raise ValueError("decode_post: every row of the read is called bad, nothing to decode (the reference fails with IndexError)")
+        return np.float64(scores[0].item()), paths[0, :n].cpu().numpy().astype(np.int64)
     scores, paths, lens = decode.viterbi_batch(post, kmer_len, skip_pen=skip, nbase=nbase, min_prob=min_prob)
     n = int(lens[0].item())
     return np.float32(scores[0].item()), [int(v) for v in paths[0, :n].cpu().numpy()]
@@ -53,7 +58,7 @@ def raw_chunk_worker(calc_post, chunks, kmer_len, min_prob=1e-5, skip=5.0, nbase
 
 
 def raw_read_worker(calc_post, signal, trim=(200, 10), open_pore_fraction=0.0, kmer_len=5, min_prob=1e-5, skip=5.0,
-                    nbase=4, name="read"):
+                    nbase=4, name="read", transducer=True, bad=True, trans=None):
     """The array part of raw_worker (basecall.py:110-121) for ONE whole read held in memory (the reference reads it
     from a fast5 file first): trim_open_pore, trim_array, per-read median/MAD normalisation, calc_post on [T,1,1],
     decode_post.  Returns (name, score, call, n_samples) or None for an empty read, like the reference."""
@@ -65,7 +70,7 @@ def raw_read_worker(calc_post, signal, trim=(200, 10), open_pore_fraction=0.0, k
         return None
     inmat = batch.normalise_chunks(signal.reshape(1, -1), 'per-chunk', out_layout='network')   # basecall.py:117-118
     post = calc_post(inmat)
-    score, call = decode_post(post, kmer_len, True, True, min_prob, skip=skip, nbase=nbase)
+    score, call = decode_post(post, kmer_len, transducer, bad, min_prob, skip=skip, trans=trans, nbase=nbase)
     return name, score, call, int(inmat.shape[0])
 
 
@@ -100,7 +105,8 @@ def _trim_table(ev, from_start, from_end):
     return util.trim_array(ev, from_start, from_end)
 
 
-def events_read_worker(calc_post, ev, trim=(0, 0), kmer_len=5, min_prob=1e-5, skip=5.0, nbase=4, name="read"):
+def events_read_worker(calc_post, ev, trim=(0, 0), kmer_len=5, min_prob=1e-5, skip=5.0, nbase=4, name="read", transducer=True,
+                       bad=True, trans=None):
     """The array part of events_worker (basecall.py:77-85) for ONE event table held in memory (the reference reads it from a fast5
     file first): trim_array, features.from_events(tag='') made on the device, calc_post on [nev, 1, 4], decode_post.
     Returns (name, score, call, n_events) or None for a table with nothing left, like the reference."""
@@ -111,7 +117,7 @@ def events_read_worker(calc_post, ev, trim=(0, 0), kmer_len=5, min_prob=1e-5, sk
         return None
     inmat = features.from_events(ev, tag='', device=True)[:, None, :]       # basecall.py:82
     post = calc_post(inmat)
-    score, call = decode_post(post, kmer_len, True, True, min_prob, skip=skip, nbase=nbase)
+    score, call = decode_post(post, kmer_len, transducer, bad, min_prob, skip=skip, trans=trans, nbase=nbase)
     return name, score, call, int(inmat.shape[0])
 
 

@@ -10,7 +10,7 @@ import sys
 import types
 
 _SUBMODULES = ["module_tools", "layers", "activation", "variables", "config", "conv", "decode", "transducer",
-               "viterbi_helpers", "bio", "util", "basecall", "batch", "helpers"]
+               "viterbi_helpers", "bio", "util", "basecall", "batch", "helpers", "olddecode"]
 
 
 def install(force=False):

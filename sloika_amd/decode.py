@@ -38,8 +38,12 @@ def prepare_post(post, min_prob=1e-5, drop_bad=False):
     import torch
     from . import device as D
     if drop_bad:
-        raise NotImplementedError("drop_bad=True belongs to the non-transducer decoder (sloika/olddecode.py), "
-                                  "which is outside the accelerated path")
+        # decode.py:31-35: the rows called bad (first arg-max in column 0) and the bad column leave, the rest is renormalised
+        from . import olddecode
+        if len(post.shape) != 3 or post.shape[1] != 1:
+            raise ValueError("prepare_post expects a [time, 1, state] posterior (np.squeeze(axis=1), decode.py:30)")
+        out, kept, _ = olddecode.prepare_post_drop_bad_batch(post, olddecode.klen_of(post.shape[2] - 1), min_prob=min_prob)
+        return D.like_input(out[: int(kept[0].item()), 0, :], post)
     pd = _dev(post)
     if pd.dim() != 3 or pd.shape[1] != 1:
         raise ValueError("prepare_post expects a [time, 1, state] posterior (np.squeeze(axis=1), decode.py:30)")

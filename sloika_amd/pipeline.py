@@ -17,8 +17,15 @@ from . import _lib, batch, decode, layers
 
 class Basecaller(object):
     def __init__(self, network, kmer_len=5, nbase=4, min_prob=1e-5, skip=0.0, normalisation='per-chunk', in_flight=1,
-                 fused_decode=None, deterministic=True, borrow=False):
+                 fused_decode=None, deterministic=True, borrow=False, transducer=True, bad=True, trans=None):
         """skip default 0.0 is the CLI default (bin/basecall_network.py:38).
+
+        transducer=False (bin/basecall_network.py --no-transducer): the network is a k-mer model without a blank state, decoded as
+        basecall.decode_post(transducer=False, bad=bad, trans=trans) does (basecall.py:44, 47-50) -- call_chunks, call_events and
+        call_reads materialise the posterior (Softmax.run) and hand it to olddecode.decode_post_batch (csrc/olddecode.hip): float64
+        scores, one state per row that is not called bad, each read bit for bit what the single-read worker gives.  `bad`: the
+        model has a bad state in column 0; `trans`: None or the [stay, step, skip] prior (--trans).  The throughput flows
+        (call_batches, the bucketed / streamed read flows), call_bases and fused_decode=True raise NotImplementedError then.
 
         in_flight: how many batches the caller keeps in flight at a time, each on a HIP stream of its own (one Basecaller
         per stream).  With two or more, a Gru layer runs eight chunks per workgroup (csrc/gru_bar16d.hip) whenever that lets
@@ -32,6 +39,13 @@ class Basecaller(object):
         With deterministic=True they run eight chunks per workgroup instead; deterministic=False lets the faster plan in (the
         price of the switch is in the bench line: `in_flight.deterministic`)."""
         self.deterministic = bool(deterministic)
+        self.transducer, self.bad, self.trans = bool(transducer), bool(bad), (None if trans is None else [float(v) for v in trans])
+        if not self.transducer:
+            if fused_decode:
+                raise NotImplementedError("fused_decode=True is the transducer decoder (csrc/softmax_viterbi.hip)")
+            if self.trans is not None and len(self.trans) != 3:
+                raise ValueError("Incorrect number of transitions")                  # olddecode.py:98
+            fused_decode = False
         # borrow: the reference compiles its networks with In(borrow=True) / Out(borrow=True) (layers.py:34-36): what a call returns
         # may be overwritten by a later call, the caller consumes or copies it first.  Here: every buffer of a call (layer outputs,
         # workspaces, results) comes out of an arena this Basecaller keeps, so a call whose shapes repeat allocates nothing, and what a
@@ -152,7 +166,32 @@ class Basecaller(object):
         with self._arena:
             return self._call_chunks(chunks, lp_dump, scaling)
 
+    def _decode_profile(self, post, lengths):
+        """basecall.decode_post(transducer=False) over the batch axis of a materialised posterior [T, B, nstate]."""
+        from . import olddecode
+        return olddecode.decode_post_batch(post, self.kmer_len, bad=self.bad, min_prob=self.min_prob, trans=self.trans, lengths=lengths,
+                                           nbase=self.nbase, workspace=self._ws)
+
+    def _ragged_posterior(self, first, lengths):
+        """The whole network, Softmax.run included, on the zero-padded [T, B, features] input `first(ragged context)` returns, with
+        per-read step counts (layers.ragged): -> (posterior [T', B, nstate], int32 device tensor of the reads' output steps)."""
+        keep = layers._HINTS.in_flight, layers._HINTS.deterministic
+        layers._HINTS.in_flight, layers._HINTS.deterministic = 1, self.deterministic
+        try:
+            with layers.ragged(lengths) as ctx:
+                x = first(ctx)
+                for layer in self.network.layers:
+                    x = layer._forward(x, None, False)
+                out_lengths = layers.ragged.current.contiguous()
+        finally:
+            layers._HINTS.in_flight, layers._HINTS.deterministic = keep
+        return x, out_lengths
+
     def _call_chunks(self, chunks, lp_dump, scaling):
+        if not self.transducer:
+            if lp_dump is not None:
+                raise ValueError("lp_dump belongs to the fused transducer decoder")
+            return self._decode_profile(self.posteriors(chunks, scaling), None)
         net = self.network
         last = net.layers[-1] if isinstance(net, layers.Serial) else None
         if type(last) is layers.Softmax and len(net.layers) > 1:
@@ -177,6 +216,7 @@ class Basecaller(object):
     def batch_slots(cls, network, in_flight=8, **kwargs):
         """The slots of call_batches, for reuse over several streams of batches: (Basecallers with arenas of their own, their pinned
         result buffers -- two sets per slot, like the arena's two device sets)."""
+        cls._transducer_only(kwargs, "call_batches")
         nslot = max(1, int(in_flight))
         return [cls(network, in_flight=nslot, borrow=True, **kwargs) for _ in range(nslot)], [[None, None] for _ in range(nslot)]
 
@@ -203,6 +243,7 @@ class Basecaller(object):
         Basecallers keep their arenas and the pinned buffers between the streams, so a later stream allocates nothing at all."""
         import torch
         from . import device as D
+        cls._transducer_only(kwargs, "call_batches")
         if slots is None:
             slots = cls.batch_slots(network, in_flight, **kwargs)
         bcs, host = slots
@@ -268,6 +309,8 @@ class Basecaller(object):
         """call_chunks + states -> bases on the device (what basecall.SeqPrinter.write does per read, basecall.py:157-163,
         with always_move as for a transducer model): -> (scores device [B], list of B base strings)."""
         from . import bio
+        if not self.transducer:
+            raise NotImplementedError("call_bases is built on the transducer decoder")
         scores, paths, lens = self.call_chunks(chunks)
         return scores, bio.paths_to_bases(paths, lens, self.kmer_len, alphabet, always_move=True)
 
@@ -280,6 +323,9 @@ class Basecaller(object):
             return self._call_padded_pass(padded, nsamp)
 
     def _call_padded_pass(self, padded, nsamp):
+        if not self.transducer:
+            # per-read normalisation (basecall.py:117-118), network, decoder with per-read lengths
+            return self._decode_profile(*self._ragged_posterior(lambda ctx: batch.normalise_reads_ragged(padded, ctx.lengths), nsamp))
         net = self.network
         B = padded.shape[0]
         keep = layers._HINTS.in_flight, layers._HINTS.deterministic
@@ -389,6 +435,8 @@ class Basecaller(object):
         cols, off = features.upload_tables(tables, '')
         x = D.scratch((tmax, B, 4), torch.float32, cols.device).zero_()
         features.launch(cols, off[:-1] + skip_events, nev, nev, np.arange(B), x, 4 * B, normalise=True)
+        if not self.transducer:
+            return self._decode_profile(*self._ragged_posterior(lambda ctx: x, nev))
         keep = layers._HINTS.in_flight, layers._HINTS.deterministic
         layers._HINTS.in_flight, layers._HINTS.deterministic = 1, self.deterministic
         try:
@@ -402,6 +450,13 @@ class Basecaller(object):
             layers._HINTS.in_flight, layers._HINTS.deterministic = keep
         return decode.viterbi_logits_batch(logits, stats, self.kmer_len, hid.shape[0], B, ld=ld, skip_pen=self.skip, nbase=self.nbase,
                                            min_prob=self.min_prob, workspace=self._ws, lengths=lengths.contiguous())
+
+    @staticmethod
+    def _transducer_only(kwargs, what):
+        """The throughput flows are built on the transducer decoders; a non-transducer model goes through call_chunks / call_events /
+        call_reads."""
+        if not kwargs.get("transducer", True):
+            raise NotImplementedError("%s is not available with transducer=False: use call_chunks, call_events or call_reads" % what)
 
     @staticmethod
     def _trimmed_read_set(signals, trim, open_pore_fraction, scaling):
@@ -480,6 +535,7 @@ class Basecaller(object):
         not pay for gigabytes of fresh allocations on every call).  -> (scores [N] float32, list of N int32 path arrays) on the
         host; a read that is in no batch (failed_reads) has score NaN and path None."""
         import torch
+        cls._transducer_only(kwargs, "run_read_batches")
         if lanes is None:
             lanes = cls.read_lanes(network, max(1, min(8, len(batches)) if in_flight is None else in_flight), **kwargs)
         # every batch queued on its lane (batch k on lane k % lanes) with its results' way to the host behind it, then collected
@@ -509,6 +565,7 @@ class Basecaller(object):
     def read_lanes(cls, network, n, **kwargs):
         """n (Basecaller, stream) pairs sharing one network, for run_read_batches / call_reads_bucketed."""
         import torch
+        cls._transducer_only(kwargs, "read_lanes")
         return [(cls(network, in_flight=n, **kwargs), torch.cuda.Stream()) for _ in range(max(1, n))]
 
     @classmethod
@@ -523,6 +580,7 @@ class Basecaller(object):
 
         scaling: as in call_reads (int16 ADC reads, one (offset, range, digitisation) per read, scaled on the device): the same results
         as on the float64 picoamperes fast5.Fast5.get_read() returns, for half the bytes over the bus and a quarter of the host memory."""
+        cls._transducer_only(kwargs, "call_reads_bucketed")
         streamed = open_pore_fraction == 0 and len(signals) > 2 * max_batch and stream_buckets
         if streamed:
             scores, paths, nsamp, nbatch, padded = cls._call_reads_streamed(network, signals, trim, max_batch, max_waste, in_flight, lanes,
