@@ -588,6 +588,22 @@ SLK_API int slk_reduce_sum_f32(const float *x, size_t n, int square, double *out
 /* out[r] = sum of x[r][0..n) for r < nrow (<= 16) contiguous arrays, float64, fixed order, 256 workgroups per array (the loss and
  * accuracy terms of a step: two launches of ~5 us where two slk_reduce_sum_f32 take 2 x 74 us).  scratch: nrow * 256 doubles. */
 SLK_API int slk_reduce_rows_sum_f32(const float *x, int nrow, size_t n, double *out, double *scratch, slk_stream_t stream);
+/* The Softmax layer of a VALIDATION batch (bin/validate_network.py:46-54), forward only.  Per row m of the M = T * B rows:
+ * loss_rows[m] = -log p[m, labels[m]] (float32, undivided; no min_prob, drop or weights) and correct_rows[m] = 1 (int32) where the
+ * FIRST column that attains the row maximum is the label (T.argmax's rule), else 0.
+ *   slk_linear_xent_eval_f16x3: from the layer's input, the statistics pass of slk_linear_xent_grad_f16x3 alone -- no logits, no
+ *     gradient, no scratch; at min_prob = 0, drop = 0 and unit weights the training entry point's loss term is this one divided by M,
+ *     same bits.  Shapes as there (K in 49..64 or 81..128, N <= 2048), SLK_ERR_UNSUPPORTED otherwise (-> the next one).  A label
+ *     outside [0, N) matches no column: garbage loss for that row, no access out of bounds.
+ *   slk_softmax_xent_eval_f32: from logits and row statistics written by slk_linear_rowstats_* (read only).  The caller checks that
+ *     labels lie in [0, nstate); the kernel clamps the index it reads with.
+ *   slk_reduce_rows_sum_i32: out[0] = sum of x[0..n) as a 64-bit integer (the count of correct positions). */
+SLK_API int slk_linear_xent_eval_f16x3(const float *x, long ldx, const void *W_hi, const void *W_lo, const float *W_inv_scale,
+                               const float *bias, int K, int N, const int32_t *labels, int T, int B, float *loss_rows,
+                               int32_t *correct_rows, slk_stream_t stream);
+SLK_API int slk_softmax_xent_eval_f32(const float *logits, long ld, const float *stats, const int32_t *labels, int T, int B, int nstate,
+                              float *loss_rows, int32_t *correct_rows, slk_stream_t stream);
+SLK_API int slk_reduce_rows_sum_i32(const int32_t *x, size_t n, long long *out, slk_stream_t stream);
 SLK_API size_t slk_gemm_tn_workspace_bytes(long M, int N1, int N2);
 /* 1..4 contractions over the same M rows in ONE launch (the weight gradients of a recurrent layer all contract the same dL/d(pre-
  * activation) matrix: launched together its rows cross the memory bus once): C[q] = A[q]^T B[q], colsum[q] (the array or an entry may be

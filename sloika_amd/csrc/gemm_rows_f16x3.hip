@@ -96,11 +96,17 @@ extern "C" int slk_split_f16x2_f32(const float *w, int rows, int K, void *hi, vo
 //      leaving xrow[row] = {maximum, 1 / sum, coefficient, label}
 //   2  gradient pass: the element stored is coefficient * (p - [column == label]), p = exp(l - maximum) / sum, with l the
 //      same product bit for bit; columns N .. ldy - 1 are written as zeros (the gradient is contracted with a padded row length)
+//   3  validation (bin/validate_network.py:46-54): pass 1 alone with the formulas of a held-out evaluation -- the row's loss is
+//      -log p[label], undivided and without min_prob, drop or weights, its accuracy term an int32 flag; nothing else is written.
+//      Everything up to the label's posterior is pass 1's own code (XS below), so the two agree bit for bit at min_prob = 0.
+// posterior of a row's label from its logit and the row's (maximum, 1 / sum): one expression for the training and validation passes
+__device__ __forceinline__ float xent_label_posterior(float logit, float mx, float inv_sum) { return __expf(logit - mx) * inv_sum; }
 struct XentArgs {
     float4 *xrow;                  // [M] pass 1 writes, pass 2 reads
     const int32_t *labels;         // [M] = [T][B]
     const float *weights;          // [M]
-    float *loss_rows, *correct_rows;
+    float *loss_rows;
+    void *correct_rows;            // [M] float (XM 1: 1 / count where correct) or int32_t (XM 3: 1 where correct)
     int T, B, drop;
     float min_prob;
 };
@@ -113,7 +119,8 @@ __global__ void __launch_bounds__(GH_THREADS) gemm_rows_f16x3_kernel(const float
                                                               long ldy, long M, int K, int N,
                                                               float2 *__restrict__ stats, XentArgs xa)
 {
-    static_assert(XM == 0 || (ACT == SLK_ACT_LINEAR && (XM == 1) == STATS), "cross-entropy passes: linear logits, statistics in pass 1");
+    constexpr bool XS = XM == 1 || XM == 3;        // a statistics pass of the cross-entropy: argmax and label logit, no stores
+    static_assert(XM == 0 || (ACT == SLK_ACT_LINEAR && XS == STATS), "cross-entropy passes: linear logits, statistics in pass 1");
     constexpr int KP = 16 * KS;                    // padded K (halves per weight row in Whi/Wlo)
     constexpr int LD = KP + 8;                     // LDS row stride in halves: (KP+8)*2 B = odd multiple of 16 B
     constexpr int RING = KS <= 9 ? 3 : 2;          // weight-tile slots (a tile is 64 x (KP+8) halves, twice): LDS budget
@@ -122,12 +129,12 @@ __global__ void __launch_bounds__(GH_THREADS) gemm_rows_f16x3_kernel(const float
     __shared__ __attribute__((aligned(16))) _Float16 wsh[RING][GH_BN * LD];
     __shared__ __attribute__((aligned(16))) _Float16 wsl[RING][GH_BN * LD];
     __shared__ float2 red[2][GH_BM];
-    __shared__ int redarg[XM == 1 ? 2 : 1][XM == 1 ? GH_BM : 1];
-    __shared__ float redlab[XM == 1 ? GH_BM : 1];
+    __shared__ int redarg[XS ? 2 : 1][XS ? GH_BM : 1];
+    __shared__ float redlab[XS ? GH_BM : 1];
     __shared__ __attribute__((aligned(16))) float bias_lds[BIAS_MAX];   // zero padded to whole tiles
     __shared__ __attribute__((aligned(16))) float winv_lds[BIAS_MAX];   // inverse scales of the weight rows (= columns here)
     constexpr int TP = 36;                          // floats per row of a wave's 32 x 32 store patch (144 B: no bank clash)
-    constexpr bool TR = TRSTORE && XM != 1 && KS <= 8;         // (K > 128: the weight ring leaves no room for the patches)
+    constexpr bool TR = TRSTORE && !XS && KS <= 8;         // (K > 128: the weight ring leaves no room for the patches)
     __shared__ __attribute__((aligned(16))) float patch[TR ? 2 * GH_NWM * 32 * TP : 4];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -238,7 +245,7 @@ __global__ void __launch_bounds__(GH_THREADS) gemm_rows_f16x3_kernel(const float
     int xlabel = -1;
     float llab = 0.0f;                             // XM 1: the label's logit, in the one lane of the row's four that meets it
     bool lfound = false;
-    if constexpr (XM == 1) xlabel = xa.labels[rowok ? row : M - 1];
+    if constexpr (XS) xlabel = xa.labels[rowok ? row : M - 1];
     if constexpr (XM == 2) {
         const float4 rc = xa.xrow[rowok ? row : M - 1];
         xmx = rc.x; xinvs = rc.y; xcoef = rc.z; xlabel = __float_as_int(rc.w);
@@ -312,7 +319,7 @@ __global__ void __launch_bounds__(GH_THREADS) gemm_rows_f16x3_kernel(const float
 #pragma unroll
             for (int reg = 0; reg < 16; reg++) o[reg] = xgrad(acc[reg], cbase + 8 * (reg >> 2) + (reg & 3));
         }
-        if constexpr (XM == 1) {
+        if constexpr (XS) {
             // nothing is stored
         } else if (tile_full && vec_ok) {
             if (rowok) {
@@ -349,7 +356,7 @@ __global__ void __launch_bounds__(GH_THREADS) gemm_rows_f16x3_kernel(const float
                 tm = fmaxf(tm, ok ? acc[reg] : -INFINITY);
             }
             const float mn = fmaxf(rmax, tm);
-            if constexpr (XM == 1) {
+            if constexpr (XS) {
                 // first column of the tile that attains its maximum (columns rise with reg; scanned downwards, the smallest wins);
                 // a tile only takes over from the earlier ones -- whose columns are all smaller -- when it is strictly larger
                 int ti = 0x7fffffff;
@@ -388,7 +395,7 @@ __global__ void __launch_bounds__(GH_THREADS) gemm_rows_f16x3_kernel(const float
 #pragma unroll
             for (int reg = 0; reg < 16; reg++) o[reg] = xgrad(acc[reg], cbase + 8 * (reg >> 2) + (reg & 3));
         }
-        if constexpr (XM == 1) {
+        if constexpr (XS) {
             // nothing is stored
         } else if constexpr (TR) {
             // my 16 values -> patch[row r][column 8q + 4h + i]; then lane l takes 16 bytes of row 8i + (l >> 3), so that
@@ -413,7 +420,7 @@ __global__ void __launch_bounds__(GH_THREADS) gemm_rows_f16x3_kernel(const float
             float tm = acc[0];
 #pragma unroll
             for (int reg = 1; reg < 16; reg++) tm = fmaxf(tm, acc[reg]);
-            if constexpr (XM == 1) {
+            if constexpr (XS) {
                 const int cbase = nt * GH_BN + 32 * wn + 4 * h;
                 int ti = 0x7fffffff;
 #pragma unroll
@@ -504,9 +511,9 @@ __global__ void __launch_bounds__(GH_THREADS) gemm_rows_f16x3_kernel(const float
         }
         if (h == 0) {
             red[wn][32 * wm + r] = make_float2(rmax, rsum);
-            if constexpr (XM == 1) redarg[wn][32 * wm + r] = rarg;
+            if constexpr (XS) redarg[wn][32 * wm + r] = rarg;
         }
-        if constexpr (XM == 1) {
+        if constexpr (XS) {
             if (lfound) redlab[32 * wm + r] = llab;
         }
         tile_barrier();
@@ -515,7 +522,15 @@ __global__ void __launch_bounds__(GH_THREADS) gemm_rows_f16x3_kernel(const float
             const float mn = fmaxf(p0.x, p1.x);
             const float s = ((p0.x == -INFINITY) ? 0.0f : p0.y * __expf(p0.x - mn)) +
                             ((p1.x == -INFINITY) ? 0.0f : p1.y * __expf(p1.x - mn));
-            if constexpr (XM == 1) {
+            if constexpr (XM == 3) {
+                // validate_network.py:50-51: the label's posterior exactly as pass 1 below forms it, -log of it, first maximum == label
+                const int a0 = redarg[0][tid], a1 = redarg[1][tid];
+                const int arg = p1.x > p0.x ? a1 : (p1.x == p0.x ? min(a0, a1) : a0);
+                const long m = m0 + tid;
+                const float p_lab = xent_label_posterior(redlab[tid], mn, 1.0f / s);
+                xa.loss_rows[m] = -logf(p_lab);
+                static_cast<int32_t *>(xa.correct_rows)[m] = arg == xa.labels[m] ? 1 : 0;
+            } else if constexpr (XM == 1) {
                 const int a0 = redarg[0][tid], a1 = redarg[1][tid];
                 const int arg = p1.x > p0.x ? a1 : (p1.x == p0.x ? min(a0, a1) : a0);
                 // the row's terms of train_network.py:128-136 (as softmax_xent_grad_kernel computes them)
@@ -523,12 +538,12 @@ __global__ void __launch_bounds__(GH_THREADS) gemm_rows_f16x3_kernel(const float
                 const int t = (int)(m / xa.B), label = xa.labels[m];
                 const bool counted = t >= xa.drop && t < xa.T - xa.drop;
                 const float count = (float)(xa.T - 2 * xa.drop) * (float)xa.B, inv = 1.0f / s;
-                const float p_lab = __expf(redlab[tid] - mn) * inv;
+                const float p_lab = xent_label_posterior(redlab[tid], mn, inv);
                 const float post_lab = xa.min_prob + (1.0f - xa.min_prob) * p_lab;
                 const float w = counted ? xa.weights[m] / count : 0.0f;
                 const float coef = w * (1.0f - xa.min_prob) * p_lab / post_lab;
                 xa.loss_rows[m] = counted ? -w * logf(post_lab) : 0.0f;
-                xa.correct_rows[m] = (counted && arg == label) ? 1.0f / count : 0.0f;
+                static_cast<float *>(xa.correct_rows)[m] = (counted && arg == label) ? 1.0f / count : 0.0f;
                 xa.xrow[m] = make_float4(mn, inv, coef, __int_as_float(label));
             } else {
                 stats[m0 + tid] = make_float2(mn, 1.0f / s);
@@ -636,6 +651,40 @@ extern "C" int slk_linear_xent_grad_f16x3(const float *x, long ldx, const void *
     case 6: return launch_xent<6>(x, ldx, hi, lo, W_inv_scale, bias, grad, ld, M, K, N, xa, s);
     case 7: return launch_xent<7>(x, ldx, hi, lo, W_inv_scale, bias, grad, ld, M, K, N, xa, s);
     case 8: return launch_xent<8>(x, ldx, hi, lo, W_inv_scale, bias, grad, ld, M, K, N, xa, s);
+    default: return SLK_ERR_UNSUPPORTED;
+    }
+}
+
+// The softmax layer of a VALIDATION batch (bin/validate_network.py:46-54): the statistics pass alone.  loss_rows[m] = -log p[m, label[m]]
+// (float32, undivided), correct_rows[m] = 1 (int32) where the first column that attains the row's maximum is the label, else 0; no
+// logits, no gradient, no scratch.  Labels outside [0, N) match no column: such a row's loss is garbage (checked by the caller), nothing
+// is read or written out of bounds.  Shapes as slk_linear_xent_grad_f16x3.
+template <int KS>
+static int launch_xent_eval(const float *x, long ldx, const _Float16 *hi, const _Float16 *lo, const float *winv, const float *bias, long M,
+                            int K, int N, const XentArgs &xa, hipStream_t s)
+{
+    dim3 grid((unsigned)((M + GH_BM - 1) / GH_BM)), block(GH_THREADS);
+    hipLaunchKernelGGL((gemm_rows_f16x3_kernel<KS, true, SLK_ACT_LINEAR, true, 3>), grid, block, 0, s, x, ldx, hi, lo, winv, bias,
+                       (float *)nullptr, 0L, M, K, N, (float2 *)nullptr, xa);   // (no output rows: stride 0 keeps the aligned-row plan)
+    return slk_launch_status();
+}
+
+extern "C" int slk_linear_xent_eval_f16x3(const float *x, long ldx, const void *W_hi, const void *W_lo, const float *W_inv_scale,
+                                          const float *bias, int K, int N, const int32_t *labels, int T, int B, float *loss_rows,
+                                          int32_t *correct_rows, slk_stream_t stream)
+{
+    if (!x || !W_hi || !W_lo || !W_inv_scale || !labels || !loss_rows || !correct_rows || T < 1 || B < 1 || K < 1 || N < 1 || ldx < K)
+        return SLK_ERR_INVALID_ARG;
+    const long M = (long)T * B;
+    if ((M + GH_BM - 1) / GH_BM > 0x7fffffffL || N > GH_BIASMAX) return SLK_ERR_UNSUPPORTED;
+    const _Float16 *hi = static_cast<const _Float16 *>(W_hi), *lo = static_cast<const _Float16 *>(W_lo);
+    XentArgs xa{nullptr, labels, nullptr, loss_rows, correct_rows, T, B, 0, 0.0f};
+    hipStream_t s = slk_stream(stream);
+    switch ((K + 15) / 16) {
+    case 4: return launch_xent_eval<4>(x, ldx, hi, lo, W_inv_scale, bias, M, K, N, xa, s);
+    case 6: return launch_xent_eval<6>(x, ldx, hi, lo, W_inv_scale, bias, M, K, N, xa, s);
+    case 7: return launch_xent_eval<7>(x, ldx, hi, lo, W_inv_scale, bias, M, K, N, xa, s);
+    case 8: return launch_xent_eval<8>(x, ldx, hi, lo, W_inv_scale, bias, M, K, N, xa, s);
     default: return SLK_ERR_UNSUPPORTED;
     }
 }

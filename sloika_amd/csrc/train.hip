@@ -613,6 +613,43 @@ extern "C" int slk_softmax_xent_grad_f32(float *logits, long ld, const float *st
     return slk_launch_status();
 }
 
+// The forward half of softmax_xent_grad_kernel with the formulas of a held-out evaluation (bin/validate_network.py:50-51): per row
+// loss = -log p[label] (undivided; no min_prob, drop or weights) and correct = 1 when the first maximum of the row is the label.  The
+// logits are only read.  The row is indexed with the label clamped into [0, nstate): a label outside it gives a meaningless loss (the
+// caller checks the labels) but no access outside the row.
+__global__ void __launch_bounds__(256) softmax_xent_eval_kernel(const float *__restrict__ logits, long ld, const float *__restrict__ stats,
+                                                                const int32_t *__restrict__ labels, size_t M, int nstate,
+                                                                float *__restrict__ loss_rows, int32_t *__restrict__ correct_rows)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t m = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;
+    const float *row = logits + m * ld;
+    const float mx = stats[2 * m], inv = stats[2 * m + 1];
+    const int label = labels[m];
+    int first = 0x7fffffff;
+    for (int j = lane; j < nstate; j += 64) first = (row[j] == mx && j < first) ? j : first;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) first = min(first, __shfl_xor(first, off));
+    if (lane == 0) {
+        const float p_lab = __expf(row[min(max(label, 0), nstate - 1)] - mx) * inv;
+        loss_rows[m] = -logf(p_lab);
+        correct_rows[m] = first == label ? 1 : 0;
+    }
+}
+
+extern "C" int slk_softmax_xent_eval_f32(const float *logits, long ld, const float *stats, const int32_t *labels, int T, int B,
+                                         int nstate, float *loss_rows, int32_t *correct_rows, slk_stream_t stream)
+{
+    if (!logits || !stats || !labels || !loss_rows || !correct_rows || T < 1 || B < 1 || nstate < 1 || ld < nstate)
+        return SLK_ERR_INVALID_ARG;
+    const size_t M = (size_t)T * B;
+    if ((M + 3) / 4 > 0x7fffffffUL) return SLK_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(softmax_xent_eval_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, slk_stream(stream), logits, ld, stats,
+                       labels, M, nstate, loss_rows, correct_rows);
+    return slk_launch_status();
+}
+
 // sum of x[0..n) (square = 0) or of x^2 (square = 1: updates.param_sqr, updates.py:92-103), accumulated in float64 in a
 // fixed order: one workgroup, result in out[0]
 __global__ void __launch_bounds__(1024) reduce_sum_kernel(const float *__restrict__ x, size_t n, int square,
@@ -694,6 +731,34 @@ extern "C" int slk_reduce_rows_sum_f32(const float *x, int nrow, size_t n, doubl
     hipStream_t s = slk_stream(stream);
     hipLaunchKernelGGL(reduce_rows_partial_kernel, dim3(RS_PIECES, nrow), dim3(256), 0, s, x, n, scratch);
     hipLaunchKernelGGL(reduce_rows_final_kernel, dim3(nrow), dim3(RS_PIECES), 0, s, (const double *)scratch, out);
+    return slk_launch_status();
+}
+
+// out[0] = sum of x[0..n) as a 64-bit integer (the number of correct positions of a validation batch: T.sum(T.eq(...)),
+// validate_network.py:51).  Up to 256 workgroups add a strided share each and one lane per workgroup adds it to out[0] (zeroed first)
+// with an integer atomic: integer addition is exact, so the result does not depend on the order.
+__global__ void __launch_bounds__(256) reduce_sum_i32_kernel(const int32_t *__restrict__ x, size_t n, unsigned long long *__restrict__ out)
+{
+    __shared__ long long part[256];
+    long long acc = 0;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) acc += x[e];
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) atomicAdd(out, (unsigned long long)part[0]);      // (two's complement: negative shares add correctly)
+}
+
+extern "C" int slk_reduce_rows_sum_i32(const int32_t *x, size_t n, long long *out, slk_stream_t stream)
+{
+    if (!x || !out || n < 1) return SLK_ERR_INVALID_ARG;
+    hipStream_t s = slk_stream(stream);
+    if (hipMemsetAsync(out, 0, sizeof(long long), s) != hipSuccess) return SLK_ERR_LAUNCH;
+    const size_t blocks = (n + 2047) / 2048;
+    hipLaunchKernelGGL(reduce_sum_i32_kernel, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(256), 0, s, x, n,
+                       reinterpret_cast<unsigned long long *>(out));
     return slk_launch_status();
 }
 

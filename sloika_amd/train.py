@@ -1015,9 +1015,14 @@ def training_batches(all_chunks, all_labels, all_weights, label_weights, niterat
 
 def train_loop(network, data, output, niteration=50000, batch_size=100, chunk_len_range=(0.5, 1.0), drop=20,
                adam=(1e-3, 0.9, 0.999), lrdecay=5000.0, min_prob=1e-30, l2=0.0, save_every=5000, smooth=0.45, seed=None,
-               transducer=True, bad=True, ilf=False, quiet=False):
+               transducer=True, bad=True, ilf=False, quiet=False, validation=None, validate_every=None):
     """train_network.py:180-330 for an already built network and loaded data (`load_chunk_file`): writes model.log,
-    model_checkpoint_NNNNN.pkl every `save_every` iterations and model_final.pkl into `output`; returns the step."""
+    model_checkpoint_NNNNN.pkl every `save_every` iterations and model_final.pkl into `output`; returns the step.
+
+    validation, validate_every (both or neither; not in the reference, whose validation is a script of its own): held-out chunks
+    as a data dict like `data`, scored with validate.validate_network (same `transducer` / `bad`, batches of up to `batch_size`
+    chunks) every `validate_every` iterations on the parameters as they then stand; one `* Validation` line per scoring goes to the
+    log.  Without them the loop's output is what it was."""
     import os
     import time
     rank, world = rank_and_world()
@@ -1040,6 +1045,11 @@ def train_loop(network, data, output, niteration=50000, batch_size=100, chunk_le
     if all_labels.min() < 0 or all_labels.max() >= network.size:
         raise ValueError("labels must lie in [0, %d)" % network.size)
     fg = wrap_network(network, min_prob=min_prob, l2=l2, drop=drop, adam=adam[1:])
+    fv = None
+    if validation is not None and validate_every is not None:
+        from . import validate
+        fv = validate.wrap_network(network)              # (reads the parameters through the same device mirrors the step updates)
+        vbatch = min(int(batch_size), len(validation["chunks"]))
     total_ev = 0
     score_smoothed, acc_smoothed = ExponentialSmoother(smooth), ExponentialSmoother(smooth)
     log.write('* Dumping initial model\n')
@@ -1067,6 +1077,11 @@ def train_loop(network, data, output, niteration=50000, batch_size=100, chunk_le
                 (i + 1) // 50, score_smoothed.value, 100.0 * acc_smoothed.value, dt, total_ev / 1000.0 / dt))
             total_ev = 0
             t0 = tn
+        if fv is not None and (i + 1) % validate_every == 0:
+            res = validate.validate_network(network, validation, batch=vbatch, transducer=transducer, bad=bad, step=fv)
+            log.write('{}* Validation {:5d} {:5.3f}  {:5.2f}%  {:5.2f}s ({:.2f} kev/s)\n'.format(
+                '' if (i + 1) % 50 == 0 else '\n', i + 1, res["score"], 100.0 * res["accuracy"], res["seconds"],
+                res["nev"] / 1000.0 / res["seconds"]))
     if rank == 0:
         save_model(network, output, step=fg)                                        # :330
     if world > 1:
