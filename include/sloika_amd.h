@@ -500,6 +500,33 @@ SLK_API int slk_raw_chunk_labels_interp_i32(const int64_t *start, const int64_t 
                                             int zero_repeats, int32_t *labels_out, int64_t *pos_out, int *status,
                                             slk_stream_t stream);
 
+/* f3 for event models: `chunkify remap` (sloika/batch.py:143-190, sloika/tools/chunkify_with_remap.py:52-59) for a ragged set of
+ * reads (csrc/event_remap.hip).
+ *
+ * slk_remap_pack_log_post_f32 = log(prepare_post(post)) (batch.py:146 with decode.py:36, then transducer.py:30 np.log(trans)) of
+ *   the reads of a ragged batch, packed for slk_map_to_sequence_batch_f32:
+ *   post: the network-layout posterior, row (t, b) of S floats at post + t * row_stride + b * batch_stride (strides in floats,
+ *   batch_stride >= S; the tensor need not be dense); nstep:[B] int32 steps of read b; ev_off:[B+1] int64; out:[ev_off[B]][S].
+ *   out row ev_off[b] + t = what slk_prepare_post_f32 followed by slk_log_post_f32(SLK_POST_LN) gives for row t of read b, bit
+ *   for bit (the same device functions).  Rows t >= min(nstep[b], ev_off[b+1] - ev_off[b], T) are neither read nor written. */
+SLK_API int slk_remap_pack_log_post_f32(const float *post, long row_stride, long batch_stride, int T, int B, int S,
+                                        const int32_t *nstep, const int64_t *ev_off, float min_prob, float *out,
+                                        slk_stream_t stream);
+/* slk_event_remap_labels_i32 = the labels of batch.chunkify (batch.py:69-78) on the table batch.remap returns (batch.py:157-158:
+ *   seq_pos = path, kmer = kmers[path], so model_kmer_len == kmer_len and the label is the k-mer's state + 1), and the strand-list
+ *   fields of tools/chunkify_with_remap.py:57-58, for `nread` reads straight from the DP's paths:
+ *   path:[sum nev] int32 and ev_off:[nread+1] as slk_map_to_sequence_batch_f32 leaves them; seq:[sum npos] int32 (state + 1 per
+ *   reference position) with pos_off:[nread+1]; row_off:[nread] int64 -- read b's (nev_b / chunk_len) * chunk_len labels start at
+ *   labels_out[row_off[b]]; labels_out:[total_rows].
+ *   label of event e = seq[path[e]], 0 where e % chunk_len != 0 and path[e] == path[e-1] (a chunk's first event keeps its label).
+ *   stats_out:[nread][3] int32 over ALL events of a read: #{e >= 1: path[e] == path[e-1]} (np.sum(np.ediff1d(path, to_begin=1)
+ *   == 0)), min(path), max(path).
+ *   status (device int, zeroed by the caller): bit 1 for a path entry outside [0, npos_b) (label -1; nothing is read through
+ *   it), bit 2 for a read whose labels would not fit into total_rows (none of them is written). */
+SLK_API int slk_event_remap_labels_i32(const int32_t *path, const int64_t *ev_off, const int32_t *seq, const int64_t *pos_off,
+                                       int nread, int chunk_len, const int64_t *row_off, int64_t total_rows, int32_t *labels_out,
+                                       int32_t *stats_out, int *status, slk_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * f2. The training step: bin/train_network.py:124-142 (`wrap_network`: loss, accuracy, th.grad, updates.adam) and
  * sloika/updates.py:9-103.  The reference crosses into Theano once per batch (`fg(indata, labels, weights, rate)`,

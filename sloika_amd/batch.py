@@ -4,9 +4,13 @@
     normalise_chunks(chunks, 'per-chunk'|...)      median/MAD normalisation (chunkify_raw.py:178-185)
     chunks_to_network_input(chunks)                [ml, chunk_len] -> [chunk_len, ml, 1] (bin/train_network.py:304)
     trim_ends_and_filter, chunkify, chunkify_many  chunks of event tables with their labels (batch.py:23-87)
+    remap, remap_many                              an event read mapped to its reference (batch.py:143-160)
+    chunk_remap_worker, chunk_remap_many           `chunkify remap`: remap, then chunks with labels (batch.py:163-190)
+    strand_list_row                                the strand-list line of a remapped read (tools/chunkify_with_remap.py:57-58)
 """
 import contextlib
 import os
+import sys
 import threading
 
 import numpy as np
@@ -503,14 +507,11 @@ def _kmer_text(ev, n):
     return np.ascontiguousarray(kmers), kmers.dtype.itemsize
 
 
-def chunkify_many(evs, chunk_len, kmer_len, use_scaled, normalisation, on_device=False):
-    """chunkify for a list of event tables: the features of ALL reads are one launch of slk_event_features_f32, the labels one launch
-    of slk_kmer_labels_i32 (compare chunkify_raw.raw_chunkify_many).  -> a list of (chunks, labels, bad) per read, each what
-    chunkify gives for that read alone, bit for bit -- numpy arrays, or device tensors with on_device=True."""
+def _chunk_features(evs, chunk_len, use_scaled, normalisation):
+    """The feature half of chunkify_many (batch.py:33-62): ONE launch of slk_event_features_f32 for all reads.  -> (float32 device
+    tensor [sum ml * chunk_len, 4], row_off int64 [n + 1]: read r owns rows row_off[r] .. row_off[r + 1] - 1, ml: chunks per read)."""
     import torch
-    from . import chunkify_raw, device as D, features
-    if len(evs) == 0:
-        raise ValueError("chunkify_many needs at least one event table")
+    from . import features
     tag = 'scaled_' if use_scaled else ''
     nev = [len(ev['length']) for ev in evs]                    # (a structured array or a dict of columns)
     for n in nev:
@@ -519,9 +520,21 @@ def chunkify_many(evs, chunk_len, kmer_len, use_scaled, normalisation, on_device
     row_off = np.concatenate([[0], np.cumsum([m * chunk_len for m in ml])]).astype(np.int64)
     cols, off = features.upload_tables(evs, tag)
     segs = [event_segments(n, chunk_len, normalisation, int(off[r]), int(row_off[r])) for r, n in enumerate(nev)]
-    total = int(row_off[-1])
-    feats = torch.empty((total, 4), dtype=torch.float32, device=cols.device)
+    feats = torch.empty((int(row_off[-1]), 4), dtype=torch.float32, device=cols.device)
     features.launch(cols, *(np.concatenate([s[k] for s in segs]) for k in range(4)), feats, 4, normalise=segs[0][4])
+    return feats, row_off, ml
+
+
+def chunkify_many(evs, chunk_len, kmer_len, use_scaled, normalisation, on_device=False):
+    """chunkify for a list of event tables: the features of ALL reads are one launch of slk_event_features_f32, the labels one launch
+    of slk_kmer_labels_i32 (compare chunkify_raw.raw_chunkify_many).  -> a list of (chunks, labels, bad) per read, each what
+    chunkify gives for that read alone, bit for bit -- numpy arrays, or device tensors with on_device=True."""
+    import torch
+    from . import chunkify_raw, device as D
+    if len(evs) == 0:
+        raise ValueError("chunkify_many needs at least one event table")
+    feats, row_off, ml = _chunk_features(evs, chunk_len, use_scaled, normalisation)
+    total = int(row_off[-1])
     # labels: the rightmost middle k-mer's state + 1 (batch.py:69-73), 0 where the position did not change inside a chunk (:75-78)
     texts = [_kmer_text(ev, m * chunk_len) for ev, m in zip(evs, ml)]
     old_len = texts[0][1]
@@ -529,14 +542,14 @@ def chunkify_many(evs, chunk_len, kmer_len, use_scaled, normalisation, on_device
         raise ValueError("the event tables hold k-mers of different lengths")
     assert kmer_len <= old_len
     alphabet = chunkify_raw._alphabet(kmer_len)
-    text = torch.from_numpy(np.frombuffer(b''.join(t.tobytes() for t, _ in texts), dtype=np.uint8).copy()).to(cols.device)
-    labels = torch.empty(total, dtype=torch.int32, device=cols.device)
-    status = torch.zeros(1, dtype=torch.int32, device=cols.device)
+    text = torch.from_numpy(np.frombuffer(b''.join(t.tobytes() for t, _ in texts), dtype=np.uint8).copy()).to(feats.device)
+    labels = torch.empty(total, dtype=torch.int32, device=feats.device)
+    status = torch.zeros(1, dtype=torch.int32, device=feats.device)
     _lib.check(_lib.lib().slk_kmer_labels_i32(text.data_ptr(), total, old_len, kmer_len, alphabet, len(alphabet), 1,
                                               labels.data_ptr(), status.data_ptr(), D.stream_ptr()), "chunkify.kmer_labels")
     seq_pos = torch.from_numpy(np.concatenate([np.asarray(ev['seq_pos'][:m * chunk_len], dtype=np.int64)
-                                               for ev, m in zip(evs, ml)])).to(cols.device)
-    stay = torch.zeros(total, dtype=torch.bool, device=cols.device)
+                                               for ev, m in zip(evs, ml)])).to(feats.device)
+    stay = torch.zeros(total, dtype=torch.bool, device=feats.device)
     stay[1:] = seq_pos[1:] == seq_pos[:-1]
     stay[::chunk_len] = False                          # (ediff1d(..., to_begin=1): a chunk's first event always keeps its label)
     labels[stay] = 0
@@ -547,7 +560,7 @@ def chunkify_many(evs, chunk_len, kmer_len, use_scaled, normalisation, on_device
         bad = np.logical_not(np.asarray(ev['good_emission'][:hi - lo])).reshape(ml[r], chunk_len)      # batch.py:80-81
         c, lab = feats[lo:hi].reshape(ml[r], chunk_len, 4), labels[lo:hi].reshape(ml[r], chunk_len)
         if on_device:
-            out.append((c, lab, torch.from_numpy(bad).to(cols.device)))
+            out.append((c, lab, torch.from_numpy(bad).to(feats.device)))
         else:
             out.append((c.cpu().numpy(), lab.cpu().numpy(), bad))
     return out
@@ -558,3 +571,240 @@ def chunkify(ev, chunk_len, kmer_len, use_scaled, normalisation):
     'length', 'kmer', 'seq_pos', 'good_emission') as training chunks: -> (chunks [ml, chunk_len, 4] float32, labels [ml, chunk_len]
     int32, bad [ml, chunk_len] bool).  The k-mer -> state mapping is the one init_chunk_identity_worker set (b'ACGT' otherwise)."""
     return chunkify_many([ev], chunk_len, kmer_len, use_scaled, normalisation)[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# `chunkify remap` for event models (sloika/batch.py:143-190): the network's posterior, csrc/event_remap.hip, csrc/transducer.hip
+# ---------------------------------------------------------------------------------------------------------------------------
+
+#: the columns remap appends to the event table, in the reference's order (batch.py:157-158)
+REMAP_FIELDS = ('seq_pos', 'kmer', 'good_emission')
+
+
+def _remap_calc_post(calc_post_):
+    f = calc_post_ if calc_post_ is not None else calc_post
+    if f is None:
+        raise ValueError("remap needs a compiled model: pass calc_post= or call batch.init_chunk_remap_worker first")
+    return f
+
+
+def _remap_network(network):
+    from . import layers
+    net = network if network is not None else getattr(calc_post, 'network', None)
+    if not isinstance(net, layers.Layer):
+        raise ValueError("remap_many needs a network: pass network= (a sloika_amd.layers.Layer) or call "
+                         "batch.init_chunk_remap_worker first")
+    return net
+
+
+def _refuse_remap_columns(ev):
+    """Raise what numpy's append_fields raises on a table that already has one of the columns remap appends (batch.py:157-158)."""
+    import numpy.lib.recfunctions as nprf
+    names = getattr(getattr(ev, 'dtype', None), 'names', None)
+    if names is None:
+        raise TypeError("remap appends columns to the event table: it must be a numpy structured array")
+    if set(names) & set(REMAP_FIELDS):
+        nprf.append_fields(ev[:0], list(REMAP_FIELDS), [np.zeros(0, 'i4'), np.zeros(0, 'S1'), np.zeros(0, '?')], usemask=False)
+        raise ValueError("the event table already has one of the columns %s" % (REMAP_FIELDS,))
+
+
+def _remapped_table(ev, path, kmers):
+    import numpy.lib.recfunctions as nprf
+    return nprf.append_fields(ev, list(REMAP_FIELDS), [path, kmers[path], np.repeat(True, len(ev))], usemask=False)
+
+
+def _remap_priors(seqs, prior):
+    from . import util
+    p0 = None if prior[0] is None else [util.geometric_prior(len(q), prior[0]) for q in seqs]
+    p1 = None if prior[1] is None else [util.geometric_prior(len(q), prior[1], rev=True) for q in seqs]
+    return p0, p1
+
+
+def remap(read_ref, ev, min_prob, kmer_len, prior, slip, calc_post=None):
+    """Map an event read to its reference sequence with the transducer model (sloika/batch.py:143-160):
+    -> (score float32, the event table with the columns 'seq_pos' (int32), 'kmer' ('S<kmer_len>') and 'good_emission' (all True)
+    appended in that order, path int32 [nev], seq = state + 1 of every k-mer of the reference).
+
+    The features of the read (features.from_events(ev, tag=''), studentised over the read) go through `calc_post` as a
+    [nev, 1, 4] batch, then decode.prepare_post and transducer.map_to_sequence(log=False), all on the device.  `prior` = (mean of
+    the geometric start prior or None, the same for the end); `calc_post` defaults to the compiled model of the process
+    (init_chunk_remap_worker), as in the reference.  The returned table is a plain structured array: the reference's is a numpy
+    MaskedArray with nothing masked (the default of append_fields).  A table that already has one of the three columns raises what
+    numpy's append_fields raises."""
+    from . import chunkify_raw, decode, features, transducer
+    f = _remap_calc_post(calc_post)
+    _refuse_remap_columns(ev)
+    kmers, seq = chunkify_raw._reference_states(read_ref, kmer_len)
+    inmat = features.from_events(ev, tag='', device=True)[:, None, :]
+    post = decode.prepare_post(f(inmat), min_prob=min_prob, drop_bad=False)
+    if post.shape[0] != len(ev):
+        raise ValueError("the network gave %d steps for %d events: remap needs one step per event" % (post.shape[0], len(ev)))
+    p0, p1 = _remap_priors([seq], prior)
+    score, path = transducer.map_to_sequence(post, seq, slip=slip, prior_initial=None if p0 is None else p0[0],
+                                             prior_final=None if p1 is None else p1[0], log=False)
+    return score, _remapped_table(ev, path, kmers), path, seq
+
+
+def _remap_many_device(refs, evs, min_prob, kmer_len, prior, slip, network, names=None):
+    """The launches of remap_many: -> (scores float32 device [n], paths int32 device [sum nev], ev_off host int64 [n + 1], device
+    tensors of ev_off, the concatenated sequences and their offsets, [(kmers, seq)] per read)."""
+    import torch
+    from . import chunkify_raw, device as D, features, pipeline, transducer
+    net = _remap_network(network)
+    n = len(evs)
+    if n == 0 or len(refs) != n:
+        raise ValueError("remap_many needs one reference per read")
+    names = ["read %d" % r for r in range(n)] if names is None else names
+    cols = []
+    for r, (ref, ev) in enumerate(zip(refs, evs)):
+        _refuse_remap_columns(ev)
+        npos = len(chunkify_raw._as_bytes(ref)) - kmer_len + 1
+        if npos < 3:
+            raise ValueError("%s cannot be remapped: its reference has %d positions, the remap needs 3" % (names[r], max(npos, 0)))
+        if npos > transducer.MAX_POSITIONS:
+            raise ValueError("%s cannot be remapped: its reference has %d positions, the remap takes %d"
+                             % (names[r], npos, transducer.MAX_POSITIONS))
+        c = features.event_columns(ev, '')
+        if c.shape[1] < 1:
+            raise ValueError("%s cannot be remapped: it has no events" % names[r])
+        if not np.isfinite(c).all():
+            raise ValueError("%s cannot be remapped: it holds values that are not finite" % names[r])
+        cols.append(c)
+    refk = [chunkify_raw._reference_states(ref, kmer_len) for ref in refs]
+    seqs = [q for _, q in refk]
+    nev = [c.shape[1] for c in cols]
+    ev_off = np.concatenate([[0], np.cumsum(nev)]).astype(np.int64)
+    # the features of all reads in one launch, straight into the zero-padded network input (pipeline.Basecaller._call_event_pass)
+    dcols, off = features.upload_tables([{"mean": c[0], "stdv": c[1], "length": c[2]} for c in cols], '')
+    x = torch.zeros((max(nev), n, 4), dtype=torch.float32, device=dcols.device)
+    features.launch(dcols, off[:-1], nev, nev, np.arange(n), x, 4 * n, normalise=True)
+    post, steps = pipeline.Basecaller(net, kmer_len=kmer_len, min_prob=min_prob)._ragged_posterior(lambda ctx: x, nev)
+    if post.dim() != 3 or post.shape[1] != n or steps.cpu().numpy().tolist() != nev:
+        raise ValueError("remap needs one network step per event: this network changes the number of steps")
+    if post.stride(2) != 1:
+        post = post.contiguous()
+    nst = int(post.shape[2])
+    ev_d = torch.from_numpy(ev_off).to(post.device)
+    ltrans = torch.empty((int(ev_off[-1]), nst), dtype=torch.float32, device=post.device)
+    with profiler.region("remap_pack", 0.0, 8.0 * ltrans.numel()):
+        rc = _lib.lib().slk_remap_pack_log_post_f32(post.data_ptr(), post.stride(0), post.stride(1), int(post.shape[0]), n, nst,
+                                                    steps.data_ptr(), ev_d.data_ptr(), float(min_prob), ltrans.data_ptr(),
+                                                    D.stream_ptr())
+    _lib.check(rc, "remap_many.pack")
+    p0, p1 = _remap_priors(seqs, prior)
+    scores, paths, ev_d, seq_d, pos_d = transducer.map_to_sequence_packed(ltrans, ev_off, seqs, slip, prior_initial=p0,
+                                                                          prior_final=p1, on_device=True)
+    return scores, paths, ev_off, ev_d, seq_d, pos_d, refk
+
+
+def remap_many(refs, evs, min_prob, kmer_len, prior, slip, network=None):
+    """remap (sloika/batch.py:143-160) for a list of event reads: -> a list of (score, table, path, seq), each bit for bit what remap
+    gives for that read alone.  The features of all reads are one launch, the network runs once on the reads as a ragged batch
+    (layers.ragged), then one slk_remap_pack_log_post_f32 and one slk_map_to_sequence_batch_f32 (one workgroup per read).
+    `network`: the Layer to run; None takes the model init_chunk_remap_worker compiled.  Before anything is launched, a read that
+    cannot be remapped -- fewer than 3 reference positions or more than transducer.MAX_POSITIONS, no events, a value that is not
+    finite -- raises a ValueError that names it."""
+    scores, paths, ev_off, _, _, _, refk = _remap_many_device(refs, evs, min_prob, kmer_len, prior, slip, network)
+    scores, paths = scores.cpu().numpy(), paths.cpu().numpy()
+    out = []
+    for r, (ev, (kmers, seq)) in enumerate(zip(evs, refk)):
+        path = paths[ev_off[r]:ev_off[r + 1]]
+        out.append((scores[r], _remapped_table(ev, path, kmers), path, seq))
+    return out
+
+
+def _read_events(fn, section, segmentation):
+    """(short name, events) of a worker's `fn`: a fast5 path, or an object that offers `get_section_events` and `filename_short`."""
+    if hasattr(fn, 'get_section_events'):
+        return fn.filename_short, fn.get_section_events(section, analysis=segmentation)
+    from . import fast5
+    f5 = fast5.Fast5(fn)
+    return os.path.splitext(os.path.basename(fn))[0], f5.get_section_events(section, analysis=segmentation)
+
+
+def chunk_remap_worker(fn, trim, min_prob, kmer_len, prior, slip, chunk_len, use_scaled, normalisation, min_length, section,
+                       segmentation, references):
+    """Worker of `chunkify remap` for one read (sloika/batch.py:163-190): same arguments, the same tuple
+    (sn + '.fast5', score, events, path, seq, chunks, labels, bad) or None with the reference's message on stderr.  `fn` is a fast5
+    path read through sloika_amd.fast5.Fast5.get_section_events, or an object that offers `get_section_events(section, analysis=)`
+    and `filename_short`.  The reference falls back on the stored basecall's events when the segmentation has no such section
+    (get_basecall_data); that is outside this project's scope, and such a file is reported as a failure to read events."""
+    try:
+        sn, ev = _read_events(fn, section, segmentation)
+    except Exception as e:
+        sys.stderr.write('Failure reading events from {}.\n{}\n'.format(fn, repr(e)))
+        return None
+    try:
+        read_ref = references[sn]
+    except Exception as e:
+        sys.stderr.write('No reference found for {}.\n{}\n'.format(fn, repr(e)))
+        return None
+    ev = trim_ends_and_filter(ev, trim, min_length, chunk_len)
+    if ev is None:
+        sys.stderr.write('{} is too short.\n'.format(fn))
+        return None
+    score, ev, path, seq = remap(read_ref, ev, min_prob, kmer_len, prior, slip)
+    chunks, labels, bad_ev = chunkify(ev, chunk_len, kmer_len, use_scaled, normalisation)
+    return sn + '.fast5', score, len(ev), path, seq, chunks, labels, bad_ev
+
+
+def chunk_remap_many(tables, names, references, trim, min_prob, kmer_len, prior, slip, chunk_len, use_scaled, normalisation,
+                     min_length, network=None):
+    """chunk_remap_worker for a list of event tables in one pass: `names[r]` is the short name of read r (its key in `references`;
+    messages call it by that name).  remap_many's launches first; the chunks are chunkify_many's feature launch ('scaled_' columns
+    with use_scaled, the chosen normalisation); labels and the strand-list statistics come from the paths on the device
+    (slk_event_remap_labels_i32), with no k-mer text in between; `bad` is all False (remap marks every emission good).
+    -> (results, strand): per read the worker's tuple or None, and (nstay, start, end) or None -- strand_list_row takes both.
+    A read without a reference and a read that is too short are skipped with the worker's messages; the others are unaffected."""
+    import torch
+    from . import chunkify_raw, device as D
+    if len(tables) != len(names):
+        raise ValueError("chunk_remap_many needs one name per event table")
+    results, strand = [None] * len(tables), [None] * len(tables)
+    good, refs, evs = [], [], []
+    for r, (ev, sn) in enumerate(zip(tables, names)):
+        try:
+            read_ref = references[sn]
+        except Exception as e:
+            sys.stderr.write('No reference found for {}.\n{}\n'.format(sn, repr(e)))
+            continue
+        ev = trim_ends_and_filter(ev, trim, min_length, chunk_len)
+        if ev is None:
+            sys.stderr.write('{} is too short.\n'.format(sn))
+            continue
+        good.append(r)
+        refs.append(read_ref)
+        evs.append(ev)
+    if not good:
+        return results, strand
+    scores, paths, ev_off, ev_d, seq_d, pos_d, refk = _remap_many_device(refs, evs, min_prob, kmer_len, prior, slip, network,
+                                                                         names=[names[r] for r in good])
+    feats, row_off, ml = _chunk_features(evs, chunk_len, use_scaled, normalisation)
+    total = int(row_off[-1])
+    dev = feats.device
+    labels = torch.empty(total, dtype=torch.int32, device=dev)
+    stats = torch.empty((len(good), 3), dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    row_d = torch.from_numpy(row_off).to(dev)
+    _lib.check(_lib.lib().slk_event_remap_labels_i32(paths.data_ptr(), ev_d.data_ptr(), seq_d.data_ptr(), pos_d.data_ptr(), len(good),
+                                                     int(chunk_len), row_d.data_ptr(), total, labels.data_ptr(), stats.data_ptr(),
+                                                     status.data_ptr(), D.stream_ptr()), "chunk_remap_many.labels")
+    chunkify_raw._status(status, "chunk_remap_many")
+    scores, paths, feats, labels, stats = (t.cpu().numpy() for t in (scores, paths, feats, labels, stats))
+    for i, r in enumerate(good):
+        lo, hi = int(row_off[i]), int(row_off[i + 1])
+        path = paths[ev_off[i]:ev_off[i + 1]]
+        results[r] = (names[r] + '.fast5', scores[i], len(evs[i]), path, refk[i][1], feats[lo:hi].reshape(ml[i], chunk_len, 4),
+                      labels[lo:hi].reshape(ml[i], chunk_len), np.zeros((ml[i], chunk_len), dtype=bool))
+        strand[r] = tuple(int(v) for v in stats[i])
+    return results, strand
+
+
+def strand_list_row(result, stats=None):
+    """The seven fields of a strand-list line (sloika/tools/chunkify_with_remap.py:57-58) for a worker's result: [filename, nev,
+    -score / nev, nstay, seqlen, start, end]; the tool writes '\\t'.join(str(x) for x in them).  `stats`: the (nstay, start, end)
+    chunk_remap_many returns for the read; without them they are counted from the path here."""
+    read, score, nev, path, seq = result[:5]
+    if stats is None:
+        stats = (np.sum(np.ediff1d(path, to_begin=1) == 0), min(path), max(path))
+    return [read, nev, -score / nev, stats[0], len(seq), stats[1], stats[2]]

@@ -75,6 +75,34 @@ def map_to_sequence_batch(trans_list, sequence_list, slip, prior_initial=None, p
                    "map_to_sequence.log")
         td = lt
     ev_off = np.concatenate([[0], np.cumsum(nev)]).astype(np.int64)
+    return map_to_sequence_packed(td, ev_off, sequence_list, slip, prior_initial=prior_initial, prior_final=prior_final)
+
+
+#: the longest sequence slk_map_to_sequence_batch_f32 takes: 28 bytes of LDS per position (include/sloika_amd.h)
+MAX_POSITIONS = 5846
+
+
+def map_to_sequence_packed(ltrans, ev_off, sequence_list, slip, prior_initial=None, prior_final=None, on_device=False):
+    """map_to_sequence_batch on what it builds first: `ltrans` is the LOG-space float32 device tensor [ev_off[-1], nstate] that holds
+    the reads' rows one after the other (read b: rows ev_off[b] .. ev_off[b + 1] - 1; slk_remap_pack_log_post_f32 writes it), `ev_off`
+    a host int64 array [nread + 1].  Same launch, same returns; with on_device=True the scores and the concatenated paths stay on the
+    device: -> (scores float32 [nread], path int32 [ev_off[-1]], device tensors of ev_off, the sequences and their offsets)."""
+    import torch
+    from . import device as D
+    assert slip is not None and slip >= 0.0, 'Slip penalty should be non-negative'
+    nread = len(sequence_list)
+    ev_off = np.ascontiguousarray(ev_off, dtype=np.int64)
+    if nread == 0 or len(ev_off) != nread + 1:
+        raise ValueError("map_to_sequence_packed needs one sequence and one row range per read")
+    if (not isinstance(ltrans, torch.Tensor) or not ltrans.is_cuda or ltrans.dtype != torch.float32 or ltrans.dim() != 2
+            or not ltrans.is_contiguous() or ltrans.shape[0] != int(ev_off[-1]) or ev_off[0] != 0):
+        raise ValueError("ltrans must be a contiguous float32 device tensor [ev_off[-1], nstate]")
+    td, dev, nst = ltrans, ltrans.device, int(ltrans.shape[1])
+    nev = np.diff(ev_off).tolist()
+    npos = [len(q) for q in sequence_list]
+    if min(npos) < 3 or min(nev) < 1:
+        raise ValueError("every read needs at least one event and three sequence positions")
+    L = _lib.lib()
     pos_off = np.concatenate([[0], np.cumsum(npos)]).astype(np.int64)
     ws_sizes = np.array([e * p for e, p in zip(nev, npos)], dtype=np.int64)
     ws_off = np.concatenate([[0], np.cumsum(ws_sizes)[:-1]]).astype(np.int64)
@@ -95,5 +123,7 @@ def map_to_sequence_batch(trans_list, sequence_list, slip, prior_initial=None, p
                                          max(npos), float(slip), D.ptr(pi), D.ptr(pf), ws.data_ptr(), wso_d.data_ptr(),
                                          score.data_ptr(), path.data_ptr(), D.stream_ptr())
     _lib.check(rc, "map_to_sequence_batch")
+    if on_device:
+        return score, path, ev_d, seq, pos_d
     ph = path.cpu().numpy()
     return score.cpu().numpy(), [ph[ev_off[b]:ev_off[b + 1]] for b in range(nread)]
