@@ -16,12 +16,13 @@
 //     chunk h, the 16 steps x 4 to-states 4j .. 4j+3 (j = 32w + c) that thread j of viterbi_forward4_kernel owns.  The logits
 //     go from the matrix pipe to the dynamic programme without leaving the registers of the lane that consumes them.
 //   * the block AFTER the one being decoded is produced meanwhile (same waves, same basic blocks: MFMAs, exponentials and
-//     logarithms fill the issue slots the dependent max-plus chain leaves empty): step 0 splits the x rows into fp16 hi/lo
-//     operand images in LDS (row scales by powers of two, f16split.h), steps 1-9 run the 12 * K/16 MFMAs per wave with the
-//     weight fragments streamed from L2 three pairs ahead (pre-packed in fragment order: one 1-KiB coalesced load per
-//     fragment), steps 10-13 reduce the row maximum and the row sum over the 32 lanes of a half (a halving butterfly on
-//     v_permlane16_swap + DPP) and over the eight waves (through LDS, on the barriers the DP has anyway), steps 14-15 turn
-//     the exponentials into log-posteriors.
+//     logarithms fill the issue slots the dependent max-plus chain leaves empty; the steps: SvSched below): the x rows are
+//     split into fp16 hi/lo operand images in LDS (row scales by powers of two, f16split.h); the 12 * K/16 MFMAs per wave
+//     run K block after K block (the two operand images of a K block are read from LDS once and serve the wave's four
+//     tiles) with the weight fragments streamed from L2 three pairs ahead (pre-packed as fragments: one 1-KiB coalesced load
+//     per fragment); the row maximum and the row sum are reduced over the 32 lanes of a half (a halving butterfly on
+//     v_permlane16_swap + DPP) and over the eight waves (through LDS, on the barriers the DP has anyway); the exponentials
+//     become log-posteriors a row at a time, in the step that consumes them.
 //   * the blank column (state 0) is a float32 dot product on the vector unit (one row per 16-lane DPP row).
 //   * the DP itself is viterbi_forward4_kernel's (decode.hip): ping-pong score vectors in LDS (bank-conflict-free padding),
 //     one barrier per step, quad-DPP skip arg-max, first-maximum tie rules of np.argmax, the traceback packed into ONE BYTE per
@@ -38,7 +39,7 @@
 #define SV_AS 320               /* floats between the four first-base blocks of a score vector (5 x 64 dwords: ds_read2st64) */
 #define SV_VP (4 * SV_AS)       /* padded score vector: element a*256 + r lives at a*SV_AS + r + 8 * (r >> 6) */
 constexpr int SV_D = 3;                 /* weight fragment pairs in flight per wave */
-constexpr int SV_AHEAD = 4;             /* positions between the LDS request of a pair's A images and its first MFMA */
+constexpr int SV_AHEAD = 4;             /* positions between the LDS request of a K block's A images and its first MFMA */
 #define SV_ETA 1e-10f
 #define SV_LOG2E 1.4426950408889634f
 #define SV_LN2 0.6931471805599453f
@@ -237,12 +238,13 @@ __device__ __forceinline__ float sv_logpost(float p, float min_prob, float one_m
 // comes from).  k = step:
 //   every k             log-posteriors of row k of the block being decoded, made from its exponentials just before they are used
 //                       (eight vector instructions in the shadow of the dynamic programme's LDS reads)
-//   k = 0 .. MMA_LAST   the MFMAs of block nb, tile after tile (weight fragments SV_D pairs ahead)
-//   k = FIN(n)          tile n's accumulators -> logits (in place), running row maxima         [the step after the tile's last MFMA]
-//   k = FIN(3)          ... and the wave's maxima (butterfly, own LDS row)
-//   k = E0 + n          tile n: exponentials (in place), running row sums                      [E0 = FIN(3) + 1]
-//   k = E0 + 3          ... and the wave's sums
-//   k = ROW_K           row statistics (waves 0-3; needs every wave's sums: the barrier of step E0 + 3) | operand images of block
+//   k = 0 .. MMA_LAST   the MFMAs of block nb, K block after K block: the hi and lo A image of a K block are requested ONCE and serve
+//                       the block's twelve MFMAs (four tiles x three terms); weight fragments SV_D pairs ahead.  (Tile after tile,
+//                       the order until design/decode_kmajor.md, every tile fetched the images of every K block again.)
+//   k = FIN_K           the four tiles' accumulators -> logits (in place) with ONE load of the 16 row scales, the row maxima over the
+//                       four tiles, the wave's maxima (butterfly, own LDS row)                  [the step after the last MFMA]
+//   k = E0              the four tiles' exponentials (in place) with ONE load of the wave's 16 maxima, the row sums, the wave's sums
+//   k = ROW_K           row statistics (waves 0-3; needs every wave's sums: the barrier of step SUM_K) | operand images of block
 //                       nb + 1 (waves 4-7)
 //   k = ROW_K + 1       operand images of block nb + 1 (waves 0-3)
 //   after step 15       the finished exponentials move to the registers the next period decodes from
@@ -263,13 +265,14 @@ template <int KS> struct SvSched {
     static constexpr int slot_lo(int q) { return (q * MPS) / NPOS; }
     static constexpr int slot_hi(int q) { return q >= NPOS - 1 ? MPS : slot_lo(q + 1); }
     static constexpr int mf_step(int m) { return m / MPS; }
-    static constexpr int fin_step(int n) { return mf_step(3 * KS * (n + 1) - 1) + 1; }
-    static constexpr int E0 = fin_step(3) + 1, SUM_K = E0 + 3, ROW_K = SUM_K + 1, LOADX_K = MMA_LAST + 2;
+    static constexpr int FIN_K = mf_step(NMF - 1) + 1;          // every tile's last MFMA belongs to the last K block
+    static constexpr int E0 = FIN_K + 1, SUM_K = E0, ROW_K = 14, LOADX_K = MMA_LAST + 2;
     // the traceback stores of the previous block: behind the last weight fragment (vmcnt counts in order: a wait for a fragment issued
     // after them would wait for the stores to reach memory)
     static constexpr int FLUSH_K = MMA_LAST + 1;
-    static constexpr int WFIRST_K = SUM_K;                      // the first weight fragments of the NEXT block are requested here
-    static_assert(ROW_K + 1 <= 15, "the production of a block must fit its period");
+    static constexpr int WFIRST_K = ROW_K - 1;                  // the first weight fragments of the NEXT block are requested here
+    static_assert(FIN_K <= MMA_LAST + 1 && SUM_K < ROW_K && LOADX_K < ROW_K && WFIRST_K > FLUSH_K && ROW_K + 1 <= 15,
+                  "the production of a block must fit its period");
 };
 
 // One 512-thread workgroup decodes TWO chunks: lane half h (lanes 32h .. 32h+31) owns chunk h.
@@ -451,34 +454,38 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
         }
     };
     auto wload = [&](auto pc) __attribute__((always_inline)) {
+        // pair p in issue order = (K block p / 4, tile p % 4); the pack keeps sv_pack_kernel's order [tile][K block]
         constexpr int p = decltype(pc)::value;
         if constexpr (p < NP) {
-            wfh[p % SV_D] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane, wwave + p * 2048, 0));
-            wfl[p % SV_D] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane, wwave + p * 2048 + 1024, 0));
+            constexpr int frag = ((p % 4) * KS + p / 4) * 2048;
+            wfh[p % SV_D] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane, wwave + frag, 0));
+            wfl[p % SV_D] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane, wwave + frag + 1024, 0));
         }
     };
-    // MFMA m of a block = term m % 3 of fragment pair p = m / 3 = (tile n = p / KS, K block s = p % KS): three fp16 terms per product,
-    // small terms first (gemm_rows_f16x3.hip): a_lo.w_hi, a_hi.w_lo, a_hi.w_hi.  The MFMAs are asm statements of their own, placed
+    // MFMA m of a block = term m % 3 of fragment pair p = m / 3 = (K block s = p / 4, tile n = p % 4): three fp16 terms per product,
+    // small terms first (gemm_rows_f16x3.hip): a_lo.w_hi, a_hi.w_lo, a_hi.w_hi.  An accumulator sees its K blocks in rising order and the
+    // three terms of each in this order, whichever tile's MFMAs run between them: the sums are those of the tile-major order, bit for bit.
+    // The MFMAs are asm statements of their own, placed
     // BETWEEN the chunks of the hand-scheduled dynamic programme (asm volatile statements keep their order): round 4's kernel issued a
     // step's MFMAs and its programme one after the other, and the ablation builds showed their times adding up -- a wave issues in order,
     // the matrix pipe idled while the programme's fifty vector instructions went by and the vector unit while the wave waited for the pipe.
     // The accumulators are read-write operands even where C = 0: a freshly defined destination may be given registers that operands of
     // MFMAs still in the pipe have just vacated (round 3: rows computed from overwritten operands whenever the pipe was contended).
-    half8 ah[NP], al[NP];                                      // A operand images of a pair: live from their LDS read to the pair's last MFMA
-    auto aload = [&](auto pc, int apar) __attribute__((always_inline)) {
-        constexpr int p = decltype(pc)::value;
-        if constexpr (p < NP) {
-            const uint8_t *ab = smem + OFF_A + apar * KS * 2048 + (p % KS) * 2048 + lane * 16;
-            ah[p] = *reinterpret_cast<const half8 *>(ab);
-            al[p] = *reinterpret_cast<const half8 *>(ab + 1024);
+    half8 ah[KS], al[KS];                                      // A operand images of a K block: live from their LDS read to the block's last MFMA
+    auto aload = [&](auto sc, int apar) __attribute__((always_inline)) {
+        constexpr int s = decltype(sc)::value;
+        if constexpr (s < KS) {
+            const uint8_t *ab = smem + OFF_A + apar * KS * 2048 + s * 2048 + lane * 16;
+            ah[s] = *reinterpret_cast<const half8 *>(ab);
+            al[s] = *reinterpret_cast<const half8 *>(ab + 1024);
         }
     };
     auto mfma_m = [&](auto mc) __attribute__((always_inline)) {
         constexpr int m = decltype(mc)::value;
         if constexpr (m < Sched::NMF) {
-            constexpr int p = m / 3, term = m % 3, n = p / KS;
-            constexpr bool zero = (p % KS == 0) && term == 0;
-            const half8 a = term == 0 ? al[p] : ah[p];
+            constexpr int p = m / 3, term = m % 3, s = p / 4, n = p % 4;
+            constexpr bool zero = s == 0 && term == 0;
+            const half8 a = term == 0 ? al[s] : ah[s];
             const half8 w = term == 1 ? wfl[p % SV_D] : wfh[p % SV_D];
             // ("+&v": the accumulator is written while later passes still read A and B -- no operand may share its registers, which
             //  hipcc would otherwise allow where the accumulator's incoming value is undefined: tools/mfma_overlap_scan.py)
@@ -502,12 +509,11 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
             mfma_run(ic<base + Sched::slot_lo(c8)>{}, ic<base + Sched::slot_hi(c8)>{}, mfma_run);
         }
     };
-    // the pairs whose first MFMA lies in chunk c8 of step k: their A images are requested a chunk earlier (at the top of the step for
-    // chunks 0 and 1; a pair that straddles the top of a step was requested in the step before)
+    // the K blocks whose first MFMA (of twelve) lies in chunk c8 of step k: their A images are requested SV_AHEAD positions earlier
     auto aload_run = [&](auto lo_c, auto hi_c, int apar, auto &&self) __attribute__((always_inline)) {
         constexpr int lo = decltype(lo_c)::value, hi = decltype(hi_c)::value;
         if constexpr (lo < hi) {
-            if constexpr (lo < Sched::NMF && lo % 3 == 0) aload(ic<lo / 3>{}, apar);
+            if constexpr (lo < Sched::NMF && lo % 12 == 0) aload(ic<lo / 12>{}, apar);
             self(ic<lo + 1>{}, hi_c, apar, self);
         }
     };
@@ -519,7 +525,7 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
         }
     };
     // the A images for position P of the block's linear position count (step P / NPOS, position P % NPOS): requested SV_AHEAD positions
-    // before the MFMA that opens the pair -- an LDS read takes 64 - 130 cycles, a position ~35, and the MFMA behind a late read waits
+    // before the MFMA that opens the K block -- an LDS read takes 64 - 130 cycles, a position ~35, and the MFMA behind a late read waits
     auto aload_pos = [&](auto Pc, int apar) __attribute__((always_inline)) {
         constexpr int P = decltype(Pc)::value;
         if constexpr (P >= 0 && P / Sched::NPOS <= Sched::MMA_LAST) aload_for(ic<P / Sched::NPOS>{}, ic<P % Sched::NPOS>{}, apar);
@@ -546,25 +552,33 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
     float *const my_max = reinterpret_cast<float *>(smem + OFF_REDA) + (hch * 8 + wave) * 16;
     float *const my_sum = reinterpret_cast<float *>(smem + OFF_REDB) + (hch * 8 + wave) * 16;
     const float *const my_fac = reinterpret_cast<const float *>(smem + OFF_FAC) + (hch * 8 + wave) * 16;      // + 256 * parity
-    // scaled accumulators of tile n -> logits in place (gemm_rows_f16x3.hip's finish), running row maxima
-    auto fin_tile = [&](auto nc, int nb) __attribute__((always_inline)) {
-        constexpr int n = decltype(nc)::value;
+    // scaled accumulators of the four tiles -> logits in place (gemm_rows_f16x3.hip's finish), row maxima over the four tiles: the 16 row
+    // scales are loaded once (they were loaded per tile as long as the tiles finished in steps of their own), the column constants of the
+    // lane's four k-mers as two float4
+    auto fin_all = [&](int nb) __attribute__((always_inline)) {
         float xinv[16];
         load16p(reinterpret_cast<const float *>(smem + OFF_XINV) + (nb & 1) * 32 + hch * 16, xinv);
-        const float civ = reinterpret_cast<const float *>(smem + OFF_CINV)[4 * j + n];
-        const float cbv = reinterpret_cast<const float *>(smem + OFF_CBIAS)[4 * j + n];
+        const float4 civ4 = reinterpret_cast<const float4 *>(smem + OFF_CINV)[j];
+        const float4 cbv4 = reinterpret_cast<const float4 *>(smem + OFF_CBIAS)[j];
+        const float civs[4] = {civ4.x, civ4.y, civ4.z, civ4.w}, cbvs[4] = {cbv4.x, cbv4.y, cbv4.z, cbv4.w};
+        static_for_sv<0, 4>([&](auto nc) {
+            constexpr int n = decltype(nc)::value;
+            const float civ = civs[n], cbv = cbvs[n];
 #pragma unroll
-        for (int i = 0; i < 16; i += 2) {
-            const f32x2 a = {acc[n][i], acc[n][i + 1]}, xi = {xinv[i], xinv[i + 1]};
-            const f32x2 v = __builtin_elementwise_fma(a * xi, f32x2{civ, civ}, f32x2{cbv, cbv});
-            acc[n][i] = v.x;
-            acc[n][i + 1] = v.y;
-        }
-        // (sv_max: fmaxf would canonicalise both operands first -- three instructions per maximum; its only reader is reduce_max's asm)
+            for (int i = 0; i < 16; i += 2) {
+                const f32x2 a = {acc[n][i], acc[n][i + 1]}, xi = {xinv[i], xinv[i + 1]};
+                const f32x2 v = __builtin_elementwise_fma(a * xi, f32x2{civ, civ}, f32x2{cbv, cbv});
+                acc[n][i] = v.x;
+                acc[n][i + 1] = v.y;
+            }
+        });
+        // (sv_max / sv_max3: fmaxf would canonicalise its operands first -- three instructions per maximum; the only reader is reduce_max's
+        //  asm.  A maximum is exact, so its grouping is free: no copy of the first tile.)
 #pragma unroll
-        for (int i = 0; i < 16; i++) rst[i] = n == 0 ? acc[0][i] : sv_max(rst[i], acc[n][i]);
-        // pinned to this step: the values are first needed steps later, and the compiler would sink the whole tile there
-        asm volatile("" : "+v"(acc[n]));
+        for (int i = 0; i < 16; i++) rst[i] = sv_max3(sv_max(acc[0][i], acc[1][i]), acc[2][i], acc[3][i]);
+        // pinned to this step: the values are first needed a step later, and the compiler would sink the work there
+#pragma unroll
+        for (int n = 0; n < 4; n++) asm volatile("" : "+v"(acc[n]));
 #pragma unroll
         for (int i = 0; i < 16; i++) keepf(rst[i]);
     };
@@ -572,30 +586,30 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
         const float r = sv_half_reduce16_asm<false>(rst, 0xCCCCCCCCCCCCCCCCull);
         if (!(c & 1)) my_max[c >> 1] = r;
     };
-    // tile n: exponentials in place, running row sums (the order of round 4's sum: ((t0 + t1) + t2) + t3)
-    auto exp_tile = [&](auto nc) __attribute__((always_inline)) {
-        constexpr int n = decltype(nc)::value;
+    // the four tiles' exponentials in place with one load of the wave's 16 maxima; row sums in the order ((t0 + t1) + t2) + t3
+    auto exp_all = [&]() __attribute__((always_inline)) {
         asm volatile("" ::: "memory");                         // the wave's own LDS writes (reduce_max), read back in order
         float m[16];
         load16p(my_max, m);
+        static_for_sv<0, 4>([&](auto nc) {
+            constexpr int n = decltype(nc)::value;
 #pragma unroll
-        for (int i = 0; i < 16; i += 2) {
-            const f32x2 d = f32x2{acc[n][i], acc[n][i + 1]} - f32x2{m[i], m[i + 1]};
-            acc[n][i] = __builtin_amdgcn_exp2f(d.x);
-            acc[n][i + 1] = __builtin_amdgcn_exp2f(d.y);
-        }
-#pragma unroll
-        for (int i = 0; i < 16; i += 2) {
-            if constexpr (n == 0) {
-                rst[i] = acc[0][i];
-                rst[i + 1] = acc[0][i + 1];
-            } else {
-                const f32x2 t = f32x2{rst[i], rst[i + 1]} + f32x2{acc[n][i], acc[n][i + 1]};
-                rst[i] = t.x;
-                rst[i + 1] = t.y;
+            for (int i = 0; i < 16; i += 2) {
+                const f32x2 d = f32x2{acc[n][i], acc[n][i + 1]} - f32x2{m[i], m[i + 1]};
+                acc[n][i] = __builtin_amdgcn_exp2f(d.x);
+                acc[n][i + 1] = __builtin_amdgcn_exp2f(d.y);
             }
+        });
+#pragma unroll
+        for (int i = 0; i < 16; i += 2) {
+            f32x2 t = f32x2{acc[0][i], acc[0][i + 1]} + f32x2{acc[1][i], acc[1][i + 1]};
+            t = t + f32x2{acc[2][i], acc[2][i + 1]};
+            t = t + f32x2{acc[3][i], acc[3][i + 1]};
+            rst[i] = t.x;
+            rst[i + 1] = t.y;
         }
-        asm volatile("" : "+v"(acc[n]));                       // pinned to this step (see fin_tile)
+#pragma unroll
+        for (int n = 0; n < 4; n++) asm volatile("" : "+v"(acc[n]));       // pinned to this step (see fin_all)
 #pragma unroll
         for (int i = 0; i < 16; i++) keepf(rst[i]);
     };
@@ -640,18 +654,12 @@ __global__ void __launch_bounds__(SV_THREADS) softmax_viterbi_kernel(const float
     auto side = [&](auto kc, int nb) __attribute__((always_inline)) {
         constexpr int k = decltype(kc)::value;
         if constexpr (k == Sched::LOADX_K) load_x(nb + 1);
-        if constexpr (k == Sched::fin_step(0)) fin_tile(ic<0>{}, nb);
-        if constexpr (k == Sched::fin_step(1)) fin_tile(ic<1>{}, nb);
-        if constexpr (k == Sched::fin_step(2)) fin_tile(ic<2>{}, nb);
-        if constexpr (k == Sched::fin_step(3)) {
-            fin_tile(ic<3>{}, nb);
+        if constexpr (k == Sched::FIN_K) {
+            fin_all(nb);
             reduce_max();
         }
-        if constexpr (k == Sched::E0) exp_tile(ic<0>{});
-        if constexpr (k == Sched::E0 + 1) exp_tile(ic<1>{});
-        if constexpr (k == Sched::E0 + 2) exp_tile(ic<2>{});
-        if constexpr (k == Sched::E0 + 3) {
-            exp_tile(ic<3>{});
+        if constexpr (k == Sched::E0) {
+            exp_all();
             reduce_sum();
         }
         if constexpr (k == Sched::WFIRST_K) wload_first(ic<0>{}, wload_first);

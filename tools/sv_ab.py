@@ -54,7 +54,7 @@ def main():
         torch.cuda.synchronize()
         same = all(torch.equal(a, b_) for a, b_ in zip(outs[0], outs[1]))
         res = [[] for _ in libs]
-        for rnd in range(7):
+        for rnd in range(-3, 9):                        # three untimed rounds first: the clock settles over the first ~50 launches
             for k, c in enumerate(fns):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
@@ -62,10 +62,16 @@ def main():
                     c()
                 e1.record()
                 torch.cuda.synchronize()
-                res[k].append(e0.elapsed_time(e1) / 5)
+                if rnd >= 0:
+                    res[k].append(e0.elapsed_time(e1) / 5)
         a, b2 = float(np.median(res[0])), float(np.median(res[1]))
-        print("K=%d T=%d B=%d: %.3f -> %.3f ms per call incl. backtrace (%+.1f %%), same paths / scores / lengths: %s"
-              % (K, T, B, a, b2, (b2 / a - 1) * 100, same), flush=True)
+        # spread = largest - smallest of a build's own rounds: a difference between the builds counts from three times the first's
+        sp = [max(r) - min(r) for r in res]
+        diff = max(float((x_.float() - y_.float()).abs().max()) for x_, y_ in zip(outs[0], outs[1]))
+        print("K=%d T=%d B=%d: %.4f -> %.4f ms per call incl. backtrace (%+.2f %%; spread of the rounds %.4f / %.4f ms), same paths / "
+              "scores / lengths: %s (largest difference %g)" % (K, T, B, a, b2, (b2 / a - 1) * 100, sp[0], sp[1], same, diff), flush=True)
+        for r in res:
+            print("    rounds (ms per call, five calls each):", " ".join("%.4f" % v for v in r), flush=True)
 
 
 if __name__ == "__main__":
