@@ -462,6 +462,31 @@ SLK_API int slk_map_to_sequence_batch_f32(const float *ltrans, int nst, const in
                                   const double *prior_initial, const double *prior_final, void *workspace,
                                   const int64_t *ws_off, float *score_out, int32_t *path_out, slk_stream_t stream);
 
+/* The same remap for references of any length (design/remap_long.md): the two entries above keep their whole state in LDS and
+ * refuse more than 5846 positions; these keep the two score rows in the workspace, behind the traceback, and one tile of positions
+ * in LDS at a time.  Score and path are bit for bit those of the entries above (and of the reference).
+ *   tile: positions per tile, a multiple of 64 from 64 to 6784 (what 160 KB of LDS hold); 0 selects the default, 4096.  Another
+ *     value: SLK_ERR_INVALID_ARG.
+ *   slk_map_to_sequence_long_workspace_bytes(nev, npos, tile): the nev * npos int32 traceback plus two float32 score rows of
+ *     npos + 16 each; 0 for a bad argument.  Host only.
+ *   slk_map_to_sequence_long_f32: the arguments of slk_map_to_sequence_f32 and `tile`; a workspace smaller than the function above
+ *     gives SLK_ERR_WORKSPACE.
+ *   slk_map_to_sequence_long_batch_f32: the arguments of slk_map_to_sequence_batch_f32 and `tile`; ws_off[b] is the offset (in int32
+ *     elements) of read b's workspace, slk_map_to_sequence_long_workspace_bytes(nev_b, npos_b, tile) / 4 elements long; as in that
+ *     entry the length of `workspace` is the caller's to get right.  max_npos bounds the tile (short reads ask for little LDS) and
+ *     has no upper limit.  A read with fewer than 3 positions or no events gets score -inf; its path and its workspace are left
+ *     untouched.
+ * Nothing is written when a call is refused. */
+SLK_API size_t slk_map_to_sequence_long_workspace_bytes(int nev, int npos, int tile);
+SLK_API int slk_map_to_sequence_long_f32(const float *ltrans, int nev, int nst, const int32_t *seq, int npos, float slip,
+                                 const double *prior_initial, const double *prior_final, void *workspace,
+                                 size_t workspace_bytes, int tile, float *score_out, int32_t *path_out, slk_stream_t stream);
+SLK_API int slk_map_to_sequence_long_batch_f32(const float *ltrans, int nst, const int64_t *ev_off, const int32_t *seq,
+                                       const int64_t *pos_off, int nread, int max_npos, float slip,
+                                       const double *prior_initial, const double *prior_final, void *workspace,
+                                       const int64_t *ws_off, int tile, float *score_out, int32_t *path_out,
+                                       slk_stream_t stream);
+
 /* f3, second half: the labels of raw_chunkify (sloika/tools/chunkify_raw.py:164-210), from the mapping table raw_remap
  * (chunkify_raw.py:260-296) produces.  Integer work, bit-exact.  `alphabet` is a HOST string of `nbase` <= 8 letters
  * (batch.init_chunk_identity_worker's alphabet, sloika/batch.py:17-27); every other pointer is device memory.

@@ -84,6 +84,9 @@ PROTOTYPES = {
     "slk_map_to_sequence_workspace_bytes": (_sz, [_i, _i]),
     "slk_map_to_sequence_f32": (_i, [_vp, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "slk_map_to_sequence_batch_f32": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "slk_map_to_sequence_long_workspace_bytes": (_sz, [_i, _i, _i]),
+    "slk_map_to_sequence_long_f32": (_i, [_vp, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    "slk_map_to_sequence_long_batch_f32": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "slk_kmer_labels_i32": (_i, [_vp, _l, _i, _i, C.c_char_p, _i, _i, _vp, _vp, _vp]),
     "slk_raw_chunk_labels_workspace_bytes": (_sz, [_l]),
     "slk_raw_chunk_labels_i32": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _l, _i, _i, _vp, _sz, _vp, _vp]),

@@ -620,7 +620,7 @@ def _remap_priors(seqs, prior):
     return p0, p1
 
 
-def remap(read_ref, ev, min_prob, kmer_len, prior, slip, calc_post=None):
+def remap(read_ref, ev, min_prob, kmer_len, prior, slip, calc_post=None, long_reference=False):
     """Map an event read to its reference sequence with the transducer model (sloika/batch.py:143-160):
     -> (score float32, the event table with the columns 'seq_pos' (int32), 'kmer' ('S<kmer_len>') and 'good_emission' (all True)
     appended in that order, path int32 [nev], seq = state + 1 of every k-mer of the reference).
@@ -630,7 +630,8 @@ def remap(read_ref, ev, min_prob, kmer_len, prior, slip, calc_post=None):
     the geometric start prior or None, the same for the end); `calc_post` defaults to the compiled model of the process
     (init_chunk_remap_worker), as in the reference.  The returned table is a plain structured array: the reference's is a numpy
     MaskedArray with nothing masked (the default of append_fields).  A table that already has one of the three columns raises what
-    numpy's append_fields raises."""
+    numpy's append_fields raises.  long_reference=True takes a reference of more than transducer.MAX_POSITIONS positions
+    (transducer.map_to_sequence)."""
     from . import chunkify_raw, decode, features, transducer
     f = _remap_calc_post(calc_post)
     _refuse_remap_columns(ev)
@@ -641,11 +642,12 @@ def remap(read_ref, ev, min_prob, kmer_len, prior, slip, calc_post=None):
         raise ValueError("the network gave %d steps for %d events: remap needs one step per event" % (post.shape[0], len(ev)))
     p0, p1 = _remap_priors([seq], prior)
     score, path = transducer.map_to_sequence(post, seq, slip=slip, prior_initial=None if p0 is None else p0[0],
-                                             prior_final=None if p1 is None else p1[0], log=False)
+                                             prior_final=None if p1 is None else p1[0], log=False, long_reference=long_reference)
     return score, _remapped_table(ev, path, kmers), path, seq
 
 
-def _remap_many_device(refs, evs, min_prob, kmer_len, prior, slip, network, names=None):
+def _remap_many_device(refs, evs, min_prob, kmer_len, prior, slip, network, names=None, long_reference=False,
+                       workspace_limit=None):
     """The launches of remap_many: -> (scores float32 device [n], paths int32 device [sum nev], ev_off host int64 [n + 1], device
     tensors of ev_off, the concatenated sequences and their offsets, [(kmers, seq)] per read)."""
     import torch
@@ -661,7 +663,7 @@ def _remap_many_device(refs, evs, min_prob, kmer_len, prior, slip, network, name
         npos = len(chunkify_raw._as_bytes(ref)) - kmer_len + 1
         if npos < 3:
             raise ValueError("%s cannot be remapped: its reference has %d positions, the remap needs 3" % (names[r], max(npos, 0)))
-        if npos > transducer.MAX_POSITIONS:
+        if npos > transducer.MAX_POSITIONS and not long_reference:
             raise ValueError("%s cannot be remapped: its reference has %d positions, the remap takes %d"
                              % (names[r], npos, transducer.MAX_POSITIONS))
         c = features.event_columns(ev, '')
@@ -692,19 +694,23 @@ def _remap_many_device(refs, evs, min_prob, kmer_len, prior, slip, network, name
                                                     D.stream_ptr())
     _lib.check(rc, "remap_many.pack")
     p0, p1 = _remap_priors(seqs, prior)
+    limit = transducer.WORKSPACE_LIMIT if workspace_limit is None else workspace_limit
     scores, paths, ev_d, seq_d, pos_d = transducer.map_to_sequence_packed(ltrans, ev_off, seqs, slip, prior_initial=p0,
-                                                                          prior_final=p1, on_device=True)
+                                                                          prior_final=p1, on_device=True,
+                                                                          long_reference=long_reference, workspace_limit=limit)
     return scores, paths, ev_off, ev_d, seq_d, pos_d, refk
 
 
-def remap_many(refs, evs, min_prob, kmer_len, prior, slip, network=None):
+def remap_many(refs, evs, min_prob, kmer_len, prior, slip, network=None, long_reference=False, workspace_limit=None):
     """remap (sloika/batch.py:143-160) for a list of event reads: -> a list of (score, table, path, seq), each bit for bit what remap
     gives for that read alone.  The features of all reads are one launch, the network runs once on the reads as a ragged batch
     (layers.ragged), then one slk_remap_pack_log_post_f32 and one slk_map_to_sequence_batch_f32 (one workgroup per read).
     `network`: the Layer to run; None takes the model init_chunk_remap_worker compiled.  Before anything is launched, a read that
     cannot be remapped -- fewer than 3 reference positions or more than transducer.MAX_POSITIONS, no events, a value that is not
-    finite -- raises a ValueError that names it."""
-    scores, paths, ev_off, _, _, _, refk = _remap_many_device(refs, evs, min_prob, kmer_len, prior, slip, network)
+    finite -- raises a ValueError that names it.  long_reference=True lifts the upper limit (transducer.map_to_sequence_packed: the
+    remap then runs in as many launches as `workspace_limit` bytes of traceback, default transducer.WORKSPACE_LIMIT, ask for)."""
+    scores, paths, ev_off, _, _, _, refk = _remap_many_device(refs, evs, min_prob, kmer_len, prior, slip, network,
+                                                              long_reference=long_reference, workspace_limit=workspace_limit)
     scores, paths = scores.cpu().numpy(), paths.cpu().numpy()
     out = []
     for r, (ev, (kmers, seq)) in enumerate(zip(evs, refk)):
@@ -723,12 +729,13 @@ def _read_events(fn, section, segmentation):
 
 
 def chunk_remap_worker(fn, trim, min_prob, kmer_len, prior, slip, chunk_len, use_scaled, normalisation, min_length, section,
-                       segmentation, references):
+                       segmentation, references, long_reference=False):
     """Worker of `chunkify remap` for one read (sloika/batch.py:163-190): same arguments, the same tuple
     (sn + '.fast5', score, events, path, seq, chunks, labels, bad) or None with the reference's message on stderr.  `fn` is a fast5
     path read through sloika_amd.fast5.Fast5.get_section_events, or an object that offers `get_section_events(section, analysis=)`
     and `filename_short`.  The reference falls back on the stored basecall's events when the segmentation has no such section
-    (get_basecall_data); that is outside this project's scope, and such a file is reported as a failure to read events."""
+    (get_basecall_data); that is outside this project's scope, and such a file is reported as a failure to read events.
+    long_reference: as in remap."""
     try:
         sn, ev = _read_events(fn, section, segmentation)
     except Exception as e:
@@ -743,19 +750,20 @@ def chunk_remap_worker(fn, trim, min_prob, kmer_len, prior, slip, chunk_len, use
     if ev is None:
         sys.stderr.write('{} is too short.\n'.format(fn))
         return None
-    score, ev, path, seq = remap(read_ref, ev, min_prob, kmer_len, prior, slip)
+    score, ev, path, seq = remap(read_ref, ev, min_prob, kmer_len, prior, slip, long_reference=long_reference)
     chunks, labels, bad_ev = chunkify(ev, chunk_len, kmer_len, use_scaled, normalisation)
     return sn + '.fast5', score, len(ev), path, seq, chunks, labels, bad_ev
 
 
 def chunk_remap_many(tables, names, references, trim, min_prob, kmer_len, prior, slip, chunk_len, use_scaled, normalisation,
-                     min_length, network=None):
+                     min_length, network=None, long_reference=False, workspace_limit=None):
     """chunk_remap_worker for a list of event tables in one pass: `names[r]` is the short name of read r (its key in `references`;
     messages call it by that name).  remap_many's launches first; the chunks are chunkify_many's feature launch ('scaled_' columns
     with use_scaled, the chosen normalisation); labels and the strand-list statistics come from the paths on the device
     (slk_event_remap_labels_i32), with no k-mer text in between; `bad` is all False (remap marks every emission good).
     -> (results, strand): per read the worker's tuple or None, and (nstay, start, end) or None -- strand_list_row takes both.
-    A read without a reference and a read that is too short are skipped with the worker's messages; the others are unaffected."""
+    A read without a reference and a read that is too short are skipped with the worker's messages; the others are unaffected.
+    long_reference / workspace_limit: as in remap_many."""
     import torch
     from . import chunkify_raw, device as D
     if len(tables) != len(names):
@@ -778,7 +786,9 @@ def chunk_remap_many(tables, names, references, trim, min_prob, kmer_len, prior,
     if not good:
         return results, strand
     scores, paths, ev_off, ev_d, seq_d, pos_d, refk = _remap_many_device(refs, evs, min_prob, kmer_len, prior, slip, network,
-                                                                         names=[names[r] for r in good])
+                                                                         names=[names[r] for r in good],
+                                                                         long_reference=long_reference,
+                                                                         workspace_limit=workspace_limit)
     feats, row_off, ml = _chunk_features(evs, chunk_len, use_scaled, normalisation)
     total = int(row_off[-1])
     dev = feats.device

@@ -355,9 +355,12 @@ def _calc_post(calc_post):
     return f
 
 
-def raw_remap_many(refs, signals, min_prob, kmer_len, prior, slip, calc_post=None):
+def raw_remap_many(refs, signals, min_prob, kmer_len, prior, slip, calc_post=None, long_reference=False,
+                   workspace_limit=transducer.WORKSPACE_LIMIT):
     """raw_remap (chunkify_raw.py:260-296) for a list of reads.  The network runs read by read (batch 1, as the reference's
     worker does); the remap DP of ALL reads is one launch (slk_map_to_sequence_batch_f32, one workgroup per read).
+    long_reference=True takes references of more than transducer.MAX_POSITIONS positions, in as many launches as
+    `workspace_limit` bytes of traceback ask for (transducer.map_to_sequence_packed).
     Returns a list of (score, mapping_table, path, seq)."""
     f = _calc_post(calc_post)
     if len(refs) != len(signals) or len(refs) == 0:
@@ -367,7 +370,8 @@ def raw_remap_many(refs, signals, min_prob, kmer_len, prior, slip, calc_post=Non
     seqs = [s for _, s in refk]
     p0 = None if prior[0] is None else [util.geometric_prior(len(s), prior[0]) for s in seqs]
     p1 = None if prior[1] is None else [util.geometric_prior(len(s), prior[1], rev=True) for s in seqs]
-    scores, paths = transducer.map_to_sequence_batch(posts, seqs, slip, prior_initial=p0, prior_final=p1, log=False)
+    scores, paths = transducer.map_to_sequence_batch(posts, seqs, slip, prior_initial=p0, prior_final=p1, log=False,
+                                                     long_reference=long_reference, workspace_limit=workspace_limit)
     out = []
     for i, (signal, (kmers, seq)) in enumerate(zip(signals, refk)):
         path = paths[i].astype(np.int64)
@@ -376,26 +380,29 @@ def raw_remap_many(refs, signals, min_prob, kmer_len, prior, slip, calc_post=Non
     return out
 
 
-def raw_remap(ref, signal, min_prob, kmer_len, prior, slip, calc_post=None):
+def raw_remap(ref, signal, min_prob, kmer_len, prior, slip, calc_post=None, long_reference=False):
     """Map raw signal to its reference sequence with the transducer model (chunkify_raw.py:260-296):
     (score float32, mapping_table, path int64[T'], seq = states + 1 of the reference's k-mers).
 
     `prior` = (mean of the geometric start prior or None, the same for the end); `calc_post` is the compiled model (the
-    reference keeps it in the process global `batch.calc_post`)."""
+    reference keeps it in the process global `batch.calc_post`); long_reference=True takes a reference of more than
+    transducer.MAX_POSITIONS positions (transducer.map_to_sequence)."""
     f = _calc_post(calc_post)
     post = _posterior_of_read(signal, min_prob, f)
     kmers, seq = _reference_states(ref, kmer_len)
     prior0 = None if prior[0] is None else util.geometric_prior(len(seq), prior[0])
     prior1 = None if prior[1] is None else util.geometric_prior(len(seq), prior[1], rev=True)
-    score, path = transducer.map_to_sequence(post, seq, slip=slip, prior_initial=prior0, prior_final=prior1, log=False)
+    score, path = transducer.map_to_sequence(post, seq, slip=slip, prior_initial=prior0, prior_final=prior1, log=False,
+                                             long_reference=long_reference)
     path = path.astype(np.int64)
     return score, _mapping_table_of_path(path, kmers, len(signal), kmer_len, signal), path, seq
 
 
 def raw_chunk_remap_worker(fn, trim, min_prob, kmer_len, min_length, prior, slip, chunk_len, normalisation, downsample_factor,
-                           interpolation, open_pore_fraction, references, calc_post=None):
+                           interpolation, open_pore_fraction, references, calc_post=None, long_reference=False):
     """Worker of `chunkify raw_remap` for one single-read fast5 file (chunkify_raw.py:299-337): same arguments, and the same
-    tuple (file name, score, rows, path, seq, chunks, labels, bad) or None with a message on stderr."""
+    tuple (file name, score, rows, path, seq, chunks, labels, bad) or None with a message on stderr.  long_reference: as in
+    raw_remap."""
     import os
     from . import fast5
     try:
@@ -415,7 +422,8 @@ def raw_chunk_remap_worker(fn, trim, min_prob, kmer_len, min_length, prior, slip
         sys.stderr.write('{} is too short.\n'.format(fn))
         return None
     try:
-        score, mapping_table, path, seq = raw_remap(read_ref, signal, min_prob, kmer_len, prior, slip, calc_post=calc_post)
+        score, mapping_table, path, seq = raw_remap(read_ref, signal, min_prob, kmer_len, prior, slip, calc_post=calc_post,
+                                                    long_reference=long_reference)
     except Exception as e:
         sys.stderr.write("Failure remapping read {}.\n{}\n".format(sn, repr(e)))
         return None
