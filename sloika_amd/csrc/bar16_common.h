@@ -202,6 +202,28 @@ __device__ __forceinline__ void pick_mix_kept(const f32x4 &a, float &r, float af
         : "+v"(r)
         : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "n"(WS - 1), "v"(after));
 }
+// ---- the same two MFMAs with the operands exchanged: the STATE is A, the weights are B (gru_bar16.hip) ---------------------------------
+// The result is the transpose: lane (g' = lane >> 4, n = lane & 15) holds rows 4g' .. 4g'+3 of column n, a column is a neuron of the
+// weight tile and a row is whatever the lane that supplies that A row fetched.  With rows 4c + 0 = chunk c's hi image and 4c + 2 = its
+// lo image, lane (c, n) finds hi.W in register 0 and lo.W in register 2: the product for (chunk c, neuron n) is their sum, and all 64
+// lanes hold 64 different (chunk, neuron) pairs -- no row selection, no DPP.  The products are those of mfma2 (fp16 x fp16 is exact and
+// commutative), accumulated over the same k positions in the same order (W_lo first), and hi + lo adds the same two values.
+__device__ __forceinline__ void mfma2t(const half8 &am, const half8 &w_hi, const half8 &w_lo, f32x4 &acc)
+{
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, w_lo, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, w_hi, acc, 0, 0, 0);
+}
+// r = a[0] + a[2] behind WS wait states, in the form of pick_mix_kept (plain asm with `after`, a register kept from step to step).  No
+// DPP source, so one wait state is the least; the eight behind the MFMA that wrote `a` are the caller's to count as before.
+template <int WS = 1>
+__device__ __forceinline__ void pick_sum_kept(const f32x4 &a, float &r, float after)
+{
+    static_assert(WS >= 1 && WS <= 8, "wait states");
+    asm("s_nop %c3\n\t"
+        "v_add_f32 %0, %1, %2"
+        : "+v"(r)
+        : "v"(a[0]), "v"(a[2]), "n"(WS - 1), "v"(after));
+}
 // The same for gru_bar16d.hip's layout (eight chunks per workgroup: the two copies of a chunk sit FOUR columns apart, copy q&1 = 0 carries
 // the hi half and owns rows 4g + {0, 1}, copy 1 the lo half and rows 4g + {2, 3}): value j of the lane = register 2(q&1) + j summed over
 // both copies.  Two instructions: the even quartets take their partner four lanes up, the odd ones four lanes down.

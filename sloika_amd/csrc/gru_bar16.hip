@@ -13,16 +13,19 @@
 //     while its LDS reads of the state are in flight; the service waves (the SIMDs without a chain wave) take the rest,
 //     split x into fp16 halves ONCE per group for everybody (operand images in LDS), and run the x DMA one request at a
 //     time so that they always reach the next barrier before the chain does;
-//   * every chain lane owns (neuron, chunk) pairs and stores its new state straight to h_out (a lane quartet writes 16
+//   * every chain lane owns (neuron, chunk) pairs and stores its new state straight to h_out (sixteen lanes write 64
 //     consecutive bytes, a wave a whole 128-byte line per chunk and step): no staging ring, no copy-out pass.
-// Layout of the 16x16x32 tiles (weights = A, state of the 4 chunks in all four column groups = B, lane (c, q, g) keeps
-// neuron 4g+q of its tile) and the packed operand images are those of gru_fused16.hip.
+// Layout of the recurrent 16x16x32 tiles: the STATE is the A operand and the weights are B (design/gru_transposed.md).  A row
+// 4c + j carries chunk c -- j = 0: its hi half, j = 2: its lo half; rows j = 1, 3 are not used and fetch the neighbouring chunk so
+// that a ds_read_b128 touches every bank once -- and a B column is a neuron of the tile, so lane (chunk c = lane >> 4, neuron
+// n = lane & 15) finds hi.W in register 0 and lo.W in register 2 of its accumulator: a gate's pre-activation is one v_add_f32
+// (bar16_common.h: pick_sum_kept).  The K order of the packed operand images is that of gru_fused16.hip.
 #include <limits.h>
 #include <stdlib.h>
 
 #include "bar16_common.h"
 
-// Recurrent products take TWO MFMAs each: the state's hi and lo halves ride in different column groups (bar16_common.h: pick_mix).
+// Recurrent products take TWO MFMAs each: the state's hi and lo halves ride in different rows of the A operand (bar16_common.h: mfma2t).
 //
 // Diagnostics (per-section shader-clock stamps, ablation launches, workgroup clocks) exist only in builds with -DSLK_DIAG
 // (tools/build_diag_lib.sh; readers: tools/bar16_check.py, tools/bar16_wg_times.py).  ABL bits (results are then garbage):
@@ -89,18 +92,24 @@ __global__ void __launch_bounds__(256, 1) gru_bar16_kernel(const float *__restri
     constexpr int NA = ST < NACAP ? ST : NACAP;                               // of which this many keep their weights in accumulation registers
     static_assert(NCW * CT + NSW * ST == NT16, "tile assignment");
     static_assert(KBLK <= 4 && ST <= 21, "interval plan");
-    // dwords of one operand image: [step][k block][k group][chunk][8 halves]; the steps lie 32 banks apart so that the 16-lane
+    // dwords of one operand image: [step][k block][slot(k group, chunk)][8 halves]; the steps lie 32 banks apart so that the 16-lane
     // groups of a ds_read_b128 (lanes of two k groups and two steps each) find their pieces on different banks
     constexpr int OPSTEP = KBLK * 64 + 32;
     constexpr int OPIMG = GS * OPSTEP;
-    // floats of one step's vI: [tile][g][chunk][r], row = 16 tile + 4g + r; + 16: the steps of a projection tile (one per lane
-    // quartet of its 16-byte writes) on different banks
+    // floats of one step's vI: [tile][g][chunk ^ (g & 2)][r], row = 16 tile + 4g + r; + 16: the steps of a projection tile (one per
+    // lane quartet of its 16-byte writes) on different banks.
+    // slot(g, chunk): where the 16 bytes of (g, chunk) lie among the sixteen of a vI tile or of a K block of a state image.  A chain
+    // lane owns neuron lane & 15 of chunk lane >> 4, so the half waves of its 4-byte accesses are two chunks times every g: with the
+    // plain order 4g + chunk, g and g + 2 would meet on one bank (the banks of 4-byte accesses repeat every 32 dwords); g = 2, 3
+    // therefore keep their chunks in the order 2, 3, 0, 1.  The 16-byte accesses see the same pieces per lane group as before.
     constexpr int VSTEP = NT16 * 64 + 16;
+    auto slot = [](int g_, int c_) { return 4 * g_ + (c_ ^ (g_ & 2)); };
 
     __shared__ __attribute__((aligned(16))) unsigned xop_hi[2 * OPIMG], xop_lo[2 * OPIMG];
     __shared__ __attribute__((aligned(16))) float xinv_lds[2 * 16];
     __shared__ __attribute__((aligned(16))) float vbuf[R * VSTEP];
-    // The lo image lies 32 banks behind the hi image: a ds_read_b128 of the mixed operand serves lane quartets of both in one pass
+    // One image: [k block][slot(g, chunk)][4 dwords = 8 halves].  The lo image lies 32 banks behind the hi image: a 16-lane group of a
+    // ds_read_b128 of the mixed operand (two k groups, every chunk, hi and lo) reads 16 pieces on 64 different banks
     // (2N + 4 put the two on the same banks: SQ_LDS_BANK_CONFLICT was 37 % of the kernel's LDS cycles)
     constexpr int IMG = 2 * N + (2 * N % 64 == 0 ? 32 : 2 * N % 64 == 32 ? 0 : 4);
     __shared__ __attribute__((aligned(16))) unsigned h_img[2 * IMG], rh_img[2 * IMG];             // hi image, then lo image
@@ -120,7 +129,9 @@ __global__ void __launch_bounds__(256, 1) gru_bar16_kernel(const float *__restri
     // ---------------- projection pieces shared by both kinds of wave ----------------
     const int pcol = lane & 15, kg = lane >> 4;          // operand row / column and k group of this lane
     const int pstep = pcol >> 2, pc = pcol & 3;          // as a B column: (step in group, chunk)
-    const int poff = pstep * OPSTEP + kg * 16 + pc * 4;                 // + 64 kb: my 16 bytes of an operand image, in dwords
+    // + 64 kb: my 16 bytes of an operand image, in dwords (the pieces of a K block in the order of slot() as well: every 16-byte access
+    // sees the same pieces per lane group in either order, and the lane's offset into a vI tile stays the one into a K block)
+    const int poff = pstep * OPSTEP + 4 * slot(kg, pc);
     auto ldH = [](const unsigned *img, int off) { return *reinterpret_cast<const half8 *>(img + off); };
     // iW tile -> A operands (lane: row pcol of the tile, k = 32 kb + 8 kg + 0..7), row scale remembered in invw_lds
     auto load_tile = [&](int tile, half8 *hi, half8 *lo) {
@@ -163,7 +174,7 @@ __global__ void __launch_bounds__(256, 1) gru_bar16_kernel(const float *__restri
 #pragma unroll
         for (int r = 0; r < 4; r++) o[r] = fmaf(acc[r] * xin, iw[r], bs[r]);
         const int st = GS * G1 + pstep;
-        *reinterpret_cast<f32x4 *>(&vbuf[(st % R) * VSTEP + ((tile * 4 + kg) * 4 + pc) * 4]) = o;
+        *reinterpret_cast<f32x4 *>(&vbuf[(st % R) * VSTEP + 64 * tile + 4 * slot(kg, pc)]) = o;
     };
     const int NG = (T + GS - 1) / GS;
 
@@ -172,9 +183,10 @@ __global__ void __launch_bounds__(256, 1) gru_bar16_kernel(const float *__restri
         // chain waves
         // =================================================================================================
         const int w = wave;
-        const int c = lane & 3, q = (lane >> 2) & 3, g = lane >> 4;
-        // recurrent weights: A operands, K blocks in the rotated order w, w+1, ... (element (g, j) of block kb is neuron
-        // 32 kb + 16 (j&1) + 4 g + (j>>1), the order the owners' packed writes create), rows scaled to [1, 2)
+        const int g = lane >> 4;                         // as an operand: k group
+        const int cn = lane >> 4, nn = lane & 15;        // as an owner: chunk, neuron of each of my two tiles
+        // recurrent weights: B operands (column lane & 15 = neuron, k group g), K blocks in the rotated order w, w+1, ... (element
+        // (g, j) of block kb is neuron 32 kb + 16 (j&1) + 4 g + (j>>1), the order the owners' packed writes create), rows scaled to [1, 2)
         half8 wz_hi[2][KBS], wz_lo[2][KBS], wr_hi[2][KBS], wr_lo[2][KBS], wc_hi[2][KBS], wc_lo[2][KBS];
         float inv_z[2], inv_r[2], inv_c[2];
 #pragma unroll
@@ -196,7 +208,7 @@ __global__ void __launch_bounds__(256, 1) gru_bar16_kernel(const float *__restri
             }
             float iz, ir, ic_;
             const float sz = pow2_scale(kgroup_max(mz), iz), sr = pow2_scale(kgroup_max(mr), ir), sc = pow2_scale(kgroup_max(mc), ic_);
-            inv_z[p] = __shfl(iz, 4 * g + q); inv_r[p] = __shfl(ir, 4 * g + q); inv_c[p] = __shfl(ic_, 4 * g + q);
+            inv_z[p] = iz; inv_r[p] = ir; inv_c[p] = ic_;   // (kgroup_max: every lane of a row has the row's scale, and its neuron IS its row)
 #pragma unroll
             for (int i = 0; i < KBS; i++) {
 #pragma unroll
@@ -208,6 +220,9 @@ __global__ void __launch_bounds__(256, 1) gru_bar16_kernel(const float *__restri
                     wc_hi[p][i][j] = hc; wc_lo[p][i][j] = (_Float16)(ac - (float)hc);
                 }
             }
+            // (one tile's rows at a time: interleaved, the two conversions are where the kernel needs the most registers, and the
+            //  64-wide instantiations must stay within the 256 that let two workgroups share a CU)
+            __builtin_amdgcn_sched_barrier(0);
         }
         constexpr int CTA = CT > 0 ? CT : 1;
         half8 pw_hi[CTA][KBLK], pw_lo[CTA][KBLK];
@@ -220,15 +235,18 @@ __global__ void __launch_bounds__(256, 1) gru_bar16_kernel(const float *__restri
                 for (int kb = 0; kb < KBLK; kb++) { pw_hi[t][kb] = to_acc_regs(pw_hi[t][kb]); pw_lo[t][kb] = to_acc_regs(pw_lo[t][kb]); }
             }
         }
-        // my 16 bytes of K block (w + i) % KBS in MY column group's image (q = 0, 1: hi; q = 2, 3: lo), in dwords
+        // my 16 bytes of K block (w + i) % KBS as row lane & 15 = 4 ac + aj of the A operand, in dwords: chunk ac's hi image for
+        // aj = 0, its lo image for aj = 2; the rows nobody reads (aj = 1, 3) fetch chunk ac ^ 1 so that the lanes of a row quartet
+        // read four different pieces
+        const int ac = (lane & 15) >> 2, aj = lane & 3;
         int moff[KBS];
 #pragma unroll
-        for (int i = 0; i < KBS; i++) moff[i] = (q >> 1) * IMG + ((((w + i) % KBS) * 4 + g) * 4 + c) * 4;
-        const int wd = ((w * 4 + g) * 4 + c) * 4 + q;                                           // my packed pair, in dwords
-        const int n0 = 32 * w + 4 * g + q;                                                      // my neuron of tile 2w (+16: 2w+1)
-        const int voff = (g * 4 + c) * 4 + q;                                                   // my element of a vI tile
+        for (int i = 0; i < KBS; i++) moff[i] = (aj >> 1) * IMG + 64 * ((w + i) % KBS) + 4 * slot(g, ac ^ (aj & 1));
+        const int wd = 64 * w + 4 * slot(nn >> 2, cn) + (nn & 3);                               // my packed pair, in dwords
+        const int n0 = 32 * w + nn;                                                             // my neuron of tile 2w (+16: 2w+1)
+        const int voff = 4 * slot(nn >> 2, cn) + (nn & 3);                                      // my element of a vI tile
         // my chunk's rows of h_out (ragged batch: chunk bc is Tc <= T steps long; a reversed scan starts at ITS last step)
-        const int bc = b0 + c;
+        const int bc = b0 + cn;
         const bool live = bc < B;
         const int Tc = (lens && live) ? min(max(lens[bc], 1), T) : T;
         const long hstep = (reverse ? -1L : 1L) * (long)B * ldh;
@@ -260,10 +278,10 @@ __global__ void __launch_bounds__(256, 1) gru_bar16_kernel(const float *__restri
         if constexpr (DIAG) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev)::"memory"); }
         float hold[2] = {0.0f, 0.0f};
         [[maybe_unused]] float zkeep[2] = {0.0f, 0.0f};  // SAVE: the update gate of the step before, stored with its h
-        // carried from step to step: my own K block of h(s-1) as B operand, read back right after I wrote it
+        // carried from step to step: my own K block of h(s-1) as A operand, read back right after I wrote it
         half8 oh = {0, 0, 0, 0, 0, 0, 0, 0};
         settle(oh);
-        // registers the asm statements of a step write, kept from step to step (bar16_common.h: pick_mix_kept)
+        // registers the asm statements of a step write, kept from step to step (bar16_common.h: pick_sum_kept)
         float pk0 = 0.0f, pk1 = 0.0f;
         unsigned sp_hi = 0u, sp_lo = 0u;
         // One step = two intervals, each opened by a barrier; MFMAs are issued in an order that keeps the matrix pipe busy
@@ -275,22 +293,22 @@ __global__ void __launch_bounds__(256, 1) gru_bar16_kernel(const float *__restri
         //   B  [others' r*h visible]     request the other K blocks, then the x operands of the next step's share of the
         //      projection; last z block and candidate products with my own block while they fly; candidate products with
         //      the others (tile 0 first), sigmoid(z) in their shadow; tanh, blend, split, write, own block read back, store
-        // The gate arithmetic reads the accumulators from inline asm (pick_mix), where hipcc inserts no wait states, and the
+        // The gate arithmetic reads the accumulators from inline asm (pick_sum_kept), where hipcc inserts no wait states, and the
         // hardware does not interlock a vector read of an MFMA result: seven wait states must lie between a
         // v_mfma_f32_16x16x32_f16 and the read (tools/probes/mfma_read_hazard_probe.hip).  Every tile's last MFMA is therefore
         // pinned (sched_barrier) in front of at least eight wait states of other instructions: tile 1's MFMAs for tile 0 --
         // which also hides their latency behind tile 0's arithmetic -- and tile 0's pick for tile 1.
-        auto mfma2 = [](const half8 &w_hi, const half8 &w_lo, const half8 &bm, f32x4 &acc) {
+        auto mfma2 = [](const half8 &w_hi, const half8 &w_lo, const half8 &am, f32x4 &acc) {
             if constexpr (ABL & 2) {
-                half8 a = w_hi, b = bm;
+                half8 a = w_hi, b = am;
                 asm volatile("" : "+v"(a), "+v"(b), "+v"(acc));
             } else {
-                ::mfma2(w_hi, w_lo, bm, acc);
+                ::mfma2t(am, w_hi, w_lo, acc);
             }
         };
         // wait states in front of tile 0's pick when 2 (KBS - 1) MFMAs of tile 1 (at least two: its own block) follow tile 0's last
-        constexpr int WS0 = KBS > 1 ? (8 - 2 * (KBS - 1) > 2 ? 8 - 2 * (KBS - 1) : 2) : 6;
-        constexpr int WS1 = (8 - WS0 - 4) > 2 ? (8 - WS0 - 4) : 2;         // ... of tile 1's, behind tile 0's pick (WS0 + four reads)
+        constexpr int WS0 = KBS > 1 ? (8 - 2 * (KBS - 1) > 1 ? 8 - 2 * (KBS - 1) : 1) : 6;
+        constexpr int WS1 = (8 - WS0 - 1) > 1 ? (8 - WS0 - 1) : 1;         // ... of tile 1's, behind tile 0's pick (WS0 + one read)
         auto step = [&](auto PHC, const int s, const int G) {
             constexpr int ph = decltype(PHC)::value;
             constexpr bool PROJ = CT > 0 && ph < KBLK;
@@ -359,8 +377,8 @@ __global__ void __launch_bounds__(256, 1) gru_bar16_kernel(const float *__restri
                 mfma2(wz_hi[1][i], wz_lo[1][i], bh[i], accZ[1]);
             }
             float rr[2];
-            pick_mix_kept<WS0>(accR[0], pk0, accR[1][0]);                     // behind tile 1's MFMAs
-            pick_mix_kept<WS1>(accR[1], pk1, pk0);                            // behind tile 0's pick
+            pick_sum_kept<WS0>(accR[0], pk0, accR[1][0]);                     // behind tile 1's MFMAs
+            pick_sum_kept<WS1>(accR[1], pk1, pk0);                            // behind tile 0's pick
             rr[0] = (ABL & 4) ? fmaf(pk0, inv_r[0], vr[0]) * 0.01f : sigmoid4(fmaf(pk0, inv_r[0], vr[0]));
             rr[1] = (ABL & 4) ? fmaf(pk1, inv_r[1], vr[1]) * 0.01f : sigmoid4(fmaf(pk1, inv_r[1], vr[1]));
             split2_kept(rr[0] * hold[0], rr[1] * hold[1], sp_hi, sp_lo);
@@ -414,12 +432,13 @@ __global__ void __launch_bounds__(256, 1) gru_bar16_kernel(const float *__restri
 #pragma unroll
             for (int i = 1; i < KBS; i++) mfma2(wc_hi[1][i], wc_lo[1][i], ch[i], accC[1]);
             asm volatile("" : "+v"(accC[1]));
-            // sigmoid(z): its last MFMAs were issued in front of the candidate's own-block products (four MFMAs ago at least)
+            // sigmoid(z): its last MFMAs were issued in front of the candidate's own-block products (four MFMAs ago at least: the four
+            // wait states of these picks count from those, not from each other, so they are what they were with pick_mix)
             float zz[2], omz[2], zh[2];
 #pragma unroll
             for (int p = 0; p < 2; p++) {
                 float &pz = p ? pk1 : pk0;
-                pick_mix_kept<4>(accZ[p], pz, accZ[1][0]);
+                pick_sum_kept<4>(accZ[p], pz, accZ[1][0]);
                 zz[p] = (ABL & 4) ? fmaf(pz, inv_z[p], vz[p]) * 0.01f : sigmoid4(fmaf(pz, inv_z[p], vz[p]));
                 omz[p] = 1.0f - zz[p];
                 zh[p] = zz[p] * hold[p];
@@ -434,8 +453,8 @@ __global__ void __launch_bounds__(256, 1) gru_bar16_kernel(const float *__restri
             BSTAMP(6)
             float hn[2];
             {
-                pick_mix_kept<WS0>(accC[0], pk0, accC[1][0]);
-                pick_mix_kept<WS1>(accC[1], pk1, pk0);
+                pick_sum_kept<WS0>(accC[0], pk0, accC[1][0]);
+                pick_sum_kept<WS1>(accC[1], pk1, pk0);
                 const float h0 = (ABL & 4) ? fmaf(pk0, inv_c[0], vc[0]) * 0.01f : tanh5(fmaf(pk0, inv_c[0], vc[0]));
                 const float h1 = (ABL & 4) ? fmaf(pk1, inv_c[1], vc[1]) * 0.01f : tanh5(fmaf(pk1, inv_c[1], vc[1]));
                 hn[0] = fmaf(omz[0], h0, zh[0]);                              // layers.py:1020
@@ -604,7 +623,7 @@ __global__ void __launch_bounds__(256, 1) gru_bar16_kernel(const float *__restri
             if constexpr (t1 < ST) a1 = tile_acc(ic<t1 < ST ? t1 : 0>{});
             mfma_drain2(a0, a1);
             const int st = GS * G1 + pstep;
-            float *dst = &vbuf[(st % R) * VSTEP + (kg * 4 + pc) * 4];
+            float *dst = &vbuf[(st % R) * VSTEP + 4 * slot(kg, pc)];
             f32x4 o;
 #pragma unroll
             for (int r = 0; r < 4; r++) o[r] = fmaf(a0[r] * xin, iw0[r], bs0[r]);

@@ -1,5 +1,7 @@
 """A/B of two library builds on ONE device, one process: per-launch time of slk_gru_bar16_f32 (whole Gru layer, T' = 800) for the
-four- / eight- / sixteen-chunk plans, interleaved rounds, and the largest difference between the two builds' results.
+four- / eight- / sixteen-chunk plans, interleaved rounds (three untimed, nine timed; each build's rounds and their spread are printed:
+a difference between the builds counts from three times the spread of the first build's own rounds), and the largest difference
+between the two builds' results.
     python tools/gru_ab.py tools/_build/libref_<rev>.so [sloika_amd/_build/libsloika_amd.so] [IxN ...]"""
 import ctypes as C
 import os
@@ -45,7 +47,7 @@ def main():
             torch.cuda.synchronize()
             diff = (ys[0] - ys[1]).abs().max().item()
             res = [[] for _ in libs]
-            for rnd in range(5):
+            for rnd in range(-3, 9):                    # three untimed rounds first: the clock settles over the first ~50 launches
                 for k in range(len(libs)):
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record()
@@ -53,10 +55,14 @@ def main():
                         run(k, r & 1)
                     e1.record()
                     torch.cuda.synchronize()
-                    res[k].append(e0.elapsed_time(e1) / 6)
+                    if rnd >= 0:
+                        res[k].append(e0.elapsed_time(e1) / 6)
             a, b = float(np.median(res[0])), float(np.median(res[1]))
-            print("%d->%d plan %d (%2d chunks per workgroup) B=%4d: %.3f -> %.3f ms per launch (%+.1f %%), largest difference %.3g"
-                  % (I, n, plan, 4 << (plan - 1), B, a, b, (b / a - 1) * 100, diff), flush=True)
+            sp = [max(r) - min(r) for r in res]         # spread = largest - smallest of a build's own rounds
+            print("%d->%d plan %d (%2d chunks per workgroup) B=%4d: %.4f -> %.4f ms per launch (%+.2f %%; spread of the rounds %.4f / %.4f "
+                  "ms), largest difference %.3g" % (I, n, plan, 4 << (plan - 1), B, a, b, (b / a - 1) * 100, sp[0], sp[1], diff), flush=True)
+            for r in res:
+                print("    rounds (ms per launch, six launches each):", " ".join("%.4f" % v for v in r), flush=True)
 
 
 if __name__ == "__main__":
