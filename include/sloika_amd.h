@@ -266,6 +266,35 @@ SLK_API int slk_gru_f32(const float *x, long ldx, const float *iW, const float *
 SLK_API int slk_gru_bar16_f32(const float *x, long ldx, const float *iW, const float *sW, const float *sW2, const float *bias,
                       float *y, long ldy, int T, int B, int insize, int n, int reverse, int act, int gate_act,
                       const int32_t *lens, float *zr_out, slk_stream_t stream);
+/* The four-chunk plan of slk_gru_bar16_f32 for weights that stay the same from call to call (inference), and for several layers at
+ * once.  slk_gru_bar16_pack_f32 writes what every workgroup of that kernel otherwise makes in its prologue -- the fp16 hi / lo images
+ * of sW, sW2 and iW in the order its lanes hold them, the rows' inverse scales and the bias (NULL: zeros) -- into `pack`
+ * (slk_gru_bar16_pack_bytes(insize, n) bytes, 16-byte aligned; 0 bytes / SLK_ERR_UNSUPPORTED: no packed kernel for the shape; this
+ * build has (96,96) and (64,64)).  The images are the bits the prologue makes; a pack is good until a weight changes.
+ * slk_gru_bar16_stack_f32 runs nlayer (1 .. SLK_GRU_STACK_MAX) layers of one (insize, n) -- insize == n unless nlayer is 1 -- in ONE
+ * launch of ceil(B / 4) workgroups: layer k reads layers[k].x (rows ldx floats apart, 16-byte aligned, ldx % 4 == 0) and writes
+ * layers[k].h_out, which is usually layers[k+1].x.  A workgroup reads and writes the rows of its own four chunks only, so the
+ * layers need no grid-wide step between them; every layer's result is, bit for bit, that of slk_gru_bar16_f32 with bits 8-9 of
+ * `reverse` = 1 on the same operands.  `reverse` of a layer: bit 0 the direction, SLK_GRU_STACK_NO_LENS: the layer ignores `lens`
+ * (scans and stores all T steps of every chunk, as slk_gru_bar16_f32 does with lens = NULL).  A layer's x and h_out must not
+ * overlap; a layer may write where an earlier layer of the call READ (two buffers used in turn): a workgroup has consumed the
+ * rows of its chunks by then and touches no others.  tanh / sigmoid only. */
+#define SLK_GRU_STACK_MAX 8
+#define SLK_GRU_STACK_NO_LENS 2
+typedef struct {
+    const float *x;
+    long ldx;
+    float *h_out;
+    long ldh;
+    const void *pack;
+    int reverse;
+    int reserved;
+} slk_gru_stack_layer;
+SLK_API size_t slk_gru_bar16_pack_bytes(int insize, int n);
+SLK_API int slk_gru_bar16_pack_f32(const float *iW, const float *bias, const float *sW, const float *sW2, int insize, int n,
+                           void *pack, slk_stream_t stream);
+SLK_API int slk_gru_bar16_stack_f32(int nlayer, const slk_gru_stack_layer *layers, int insize, int n, int T, int B,
+                            const int32_t *lens, slk_stream_t stream);
 /* Ragged batches (whole reads of different lengths, zero-padded to T steps; the reference calls reads one at a time,
  * sloika/basecall.py:88-121): lens[b] in [1, T] (int32, device) is the number of valid steps of chunk b.  Steps
  * t >= lens[b] of y / h_out are left untouched, and with reverse = 1 the scan of chunk b starts at ITS last step,

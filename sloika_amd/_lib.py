@@ -16,6 +16,14 @@ SLK_ERR_UNSUPPORTED = -2
 SLK_ERR_LAUNCH = -3
 SLK_ERR_WORKSPACE = -4
 SLK_ERR_NO_DEVICE = -5
+SLK_GRU_STACK_MAX = 8          # include/sloika_amd.h: layers per slk_gru_bar16_stack_f32 launch
+SLK_GRU_STACK_NO_LENS = 2      # ... bit of a layer's `reverse`: the layer ignores the ragged lengths
+
+
+class GruStackLayer(C.Structure):
+    """slk_gru_stack_layer of include/sloika_amd.h."""
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_long), ("h_out", C.c_void_p), ("ldh", C.c_long), ("pack", C.c_void_p),
+                ("reverse", C.c_int), ("reserved", C.c_int)]
 
 POST_RAW, POST_PLAIN, POST_LOG, POST_LN = 0, 1, 2, 3
 
@@ -66,6 +74,9 @@ PROTOTYPES = {
     "slk_gru_workspace_bytes": (_sz, [_i, _i, _i]),
     "slk_gru_f32": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "slk_paths_to_bases": (_i, [_vp, _l, _vp, _i, _i, _i, _i, C.c_ulonglong, _vp, _l, _vp, _vp]),
+    "slk_gru_bar16_pack_bytes": (_sz, [_i, _i]),
+    "slk_gru_bar16_pack_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "slk_gru_bar16_stack_f32": (_i, [_i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "slk_gru_bar16_f32": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "slk_lstm_recurrent_f32": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _vp]),
     "slk_lstm_recurrent_ragged_f32": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _vp, _vp]),

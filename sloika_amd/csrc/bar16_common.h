@@ -284,3 +284,98 @@ __device__ __forceinline__ void tile2_mfma_acc(f32x4 &a0, f32x4 &a1, const half8
         hook(ic<6 * kb + 5>{});
     });
 }
+
+// ---- the weight images of the four-chunk kernel (gru_bar16.hip) -----------------------------------------------------------------------
+// Every workgroup of gru_bar16_kernel makes them in its prologue (gru_bar16_body.h: load_tile, and the chain waves' loop over their
+// two tiles); gru_bar16_pack_kernel makes them once per set of weights with the two functions below, which repeat that arithmetic
+// statement for statement -- same loads, same pow2_scale(kgroup_max(.)), same conversions -- so that a pack holds the bits the
+// prologue makes (tests/test_gpu_gru_stack.py compares results bit for bit).  Change one, change the other.  All 64 lanes of the
+// wave call these (kgroup_max swaps across lanes).
+// One iW tile -> A operands (lane: row pcol of the tile, k = 32 kb + 8 kg + 0..7); returns the row's inverse scale.
+template <int I, int KBLK_>
+__device__ __forceinline__ float bar16_proj_tile(const float *iW, int tile, int pcol, int kg, half8 *hi, half8 *lo)
+{
+    const int row = 16 * tile + pcol;
+    float u[KBLK_][8];
+    float m = 0.0f;
+#pragma unroll
+    for (int kb = 0; kb < KBLK_; kb++) {
+        const int k0 = 32 * kb + 8 * kg;
+        const bool kok = (I % 32 == 0) || k0 < I;
+        const float *src = iW + (size_t)row * I + (kok ? k0 : 0);
+        const float4 u0 = *reinterpret_cast<const float4 *>(src), u1 = *reinterpret_cast<const float4 *>(src + 4);
+        const float t[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            u[kb][j] = kok ? t[j] : 0.0f;
+            m = fmaxf(m, fabsf(u[kb][j]));
+        }
+    }
+    float inv;
+    const float ws = pow2_scale(kgroup_max(m), inv);
+#pragma unroll
+    for (int kb = 0; kb < KBLK_; kb++) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const float v = u[kb][j] * ws;
+            const _Float16 h = (_Float16)v;
+            hi[kb][j] = h;
+            lo[kb][j] = (_Float16)(v - (float)h);
+        }
+    }
+    return inv;
+}
+// Recurrent weights of chain wave w, tile p of its two: B operands (column lane & 15 = neuron, k group g = lane >> 4), K blocks in the
+// rotated order w, w+1, ... (element (g, j) of block kb is neuron 32 kb + 16 (j&1) + 4 g + (j>>1), the order the owners' packed writes
+// create), rows scaled to [1, 2); iz / ir / ic: the rows' inverse scales (every lane of a row has the row's, and its neuron IS its row).
+template <int N, int KBS_>
+__device__ __forceinline__ void bar16_rec_tile(const float *sW, const float *sW2, int w, int p, int lane, half8 *wz_hi, half8 *wz_lo,
+                                               half8 *wr_hi, half8 *wr_lo, half8 *wc_hi, half8 *wc_lo, float &iz, float &ir, float &ic_)
+{
+    const int g = lane >> 4;
+    const int row = 32 * w + 16 * p + (lane & 15);
+    float vz[KBS_][8], vr[KBS_][8], vc[KBS_][8];
+    float mz = 0.0f, mr = 0.0f, mc = 0.0f;
+#pragma unroll
+    for (int i = 0; i < KBS_; i++) {
+        const int kb = (w + i) % KBS_;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const int k = 32 * kb + 16 * (j & 1) + 4 * g + (j >> 1);
+            vz[i][j] = sW[(size_t)row * N + k];
+            vr[i][j] = sW[(size_t)(N + row) * N + k];
+            vc[i][j] = sW2[(size_t)row * N + k];
+            mz = fmaxf(mz, fabsf(vz[i][j])); mr = fmaxf(mr, fabsf(vr[i][j])); mc = fmaxf(mc, fabsf(vc[i][j]));
+        }
+    }
+    const float sz = pow2_scale(kgroup_max(mz), iz), sr = pow2_scale(kgroup_max(mr), ir), sc = pow2_scale(kgroup_max(mc), ic_);
+#pragma unroll
+    for (int i = 0; i < KBS_; i++) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const float az = vz[i][j] * sz, ar = vr[i][j] * sr, ac = vc[i][j] * sc;
+            const _Float16 hz = (_Float16)az, hr = (_Float16)ar, hc = (_Float16)ac;
+            wz_hi[i][j] = hz; wz_lo[i][j] = (_Float16)(az - (float)hz);
+            wr_hi[i][j] = hr; wr_lo[i][j] = (_Float16)(ar - (float)hr);
+            wc_hi[i][j] = hc; wc_lo[i][j] = (_Float16)(ac - (float)hc);
+        }
+    }
+}
+// Where the pack keeps them, in 16-byte pieces: every image is 64 consecutive pieces, one per lane, so a wave's prologue is a run of
+// 1-KiB loads.  Per chain wave the images of its two tiles -- item(p, gate z / r / c, K block i in ITS rotated order, hi / lo) -- and
+// two pieces of inverse scales {iz0, iz1, ir0, ir1}, {ic0, ic1, -, -}; then the projection tiles [tile][K block][hi / lo] as the lane
+// of ANY wave holds them (which wave takes which tile is the kernel's business); then invw[3N] and bias[3N] as floats.
+template <int I, int N>
+struct Bar16Pack {
+    static constexpr int NCW = N / 32, KBS = N / 32, NT16 = 3 * N / 16, KBLK = (I + 31) / 32;
+    static constexpr int REC_ITEMS = 12 * KBS + 2;
+    static constexpr size_t PROJ0 = (size_t)NCW * REC_ITEMS * 64;
+    static constexpr size_t FLT0 = PROJ0 + (size_t)NT16 * KBLK * 2 * 64;
+    static constexpr size_t BYTES = FLT0 * 16 + (size_t)6 * N * sizeof(float);
+    __host__ __device__ static constexpr size_t rec(int w, int p, int gate, int i, int hl)
+    {
+        return ((size_t)w * REC_ITEMS + ((p * 3 + gate) * KBS + i) * 2 + hl) * 64;
+    }
+    __host__ __device__ static constexpr size_t rec_inv(int w, int k) { return ((size_t)w * REC_ITEMS + 12 * KBS + k) * 64; }
+    __host__ __device__ static constexpr size_t proj(int tile, int kb, int hl) { return PROJ0 + ((size_t)(tile * KBLK + kb) * 2 + hl) * 64; }
+};

@@ -1041,10 +1041,32 @@ class Gru(RNN):
         d = dict(self.__dict__)
         d.pop("_pad_cache", None)
         d.pop("_iw16", None)         # device caches: never pickled
+        d.pop("_bar16pack", None)
         return d
+
+    def bar16_pack(self):
+        """The weights as the four-chunk kernel's lanes hold them (csrc/gru_bar16.hip: gru_bar16_pack_kernel), or None where there is no
+        packed kernel for the shape.  Kept like Softmax.viterbi_pack: made at first use, re-made when a weight changes."""
+        import torch
+        L = _lib.lib()
+        nbytes = L.slk_gru_bar16_pack_bytes(self.insize, self.size)
+        if nbytes == 0:
+            return None
+
+        def build():
+            iW = self.iW.dev()
+            pack = torch.empty(nbytes, dtype=torch.uint8, device=iW.device)
+            _lib.check(L.slk_gru_bar16_pack_f32(iW.data_ptr(), self.b.dev().data_ptr(), self.sW.dev().data_ptr(),
+                                                self.sW2.dev().data_ptr(), self.insize, self.size, pack.data_ptr(), _stream()),
+                       "gru_bar16_pack")
+            return pack
+
+        return _derived_cache(self, "_bar16pack", (self.iW, self.sW, self.sW2, self.b), build)
 
     def _forward(self, x, out, reverse):
         import torch
+        if _gru_stack_ok([(self, reverse)], x):
+            return _gru_stack_run([(self, reverse)], x, out)
         T, B, _ = x.shape
         n = self.size
         target = gru_pad_shape(self.insize, n, self.fun, self.gatefun)
@@ -1309,14 +1331,89 @@ class Serial(Layer):
     def _forward(self, x, out, reverse):
         if reverse:
             return _flip_run(self, x, out)
-        tmp = x
-        last = len(self.layers) - 1
-        for i, layer in enumerate(self.layers):
-            tmp = layer._forward(tmp, out if i == last else None, False)
-        return tmp
+        return run_layers(self.layers, x, out)
 
     def spec(self):
         return {"type": "serial", "sublayers": [l.spec() for l in self.layers]}
+
+
+def _as_gru(layer):
+    """(the Gru, reversed?) behind any number of Reverse wrappers, or None for every other layer."""
+    rev = False
+    while isinstance(layer, Reverse):
+        layer, rev = layer.layer, not rev
+    return (layer, rev) if type(layer) is Gru else None
+
+
+def _gru_stack_ok(grus, x):
+    """Can [(Gru, reversed?), ...] applied to x run as ONE slk_gru_bar16_stack_f32 launch: layers of one shape that has a packed
+    four-chunk kernel and needs no padded twin, the four-chunk plan chosen (as many workgroups as the batch has groups of four chunks,
+    all on the chip at once), rows of x the kernel can read in 16-byte pieces."""
+    import torch
+    g0 = grus[0][0]
+    I, n = g0.insize, g0.size
+    T, B, _ = x.shape
+    if len(grus) > _lib.SLK_GRU_STACK_MAX or (len(grus) > 1 and I != n):
+        return False
+    for g, _ in grus:
+        if ((g.insize, g.size) != (I, n) or gru_plan(I, n, g.fun, g.gatefun) != "layer"
+                or gru_pad_shape(I, n, g.fun, g.gatefun) != (I, n)):
+            return False
+    if _lib.lib().slk_gru_bar16_pack_bytes(I, n) == 0:
+        return False
+    bits = g0._plan_bits(x, B)
+    if not (bits == 1 or (bits == 0 and (B + 3) // 4 <= _cu_count(x.device))):
+        return False
+    return (x.dtype == torch.float32 and x.stride(2) == 1 and x.stride(0) == B * x.stride(1) and x.stride(1) % 4 == 0
+            and x.data_ptr() % 16 == 0)
+
+
+def _gru_stack_run(grus, x, out):
+    """[(Gru, reversed?), ...] on x in one launch (_gru_stack_ok said yes); the layers between the first and the last write to two
+    buffers in turn.  As in Gru._forward only a reversed scan is told where the chunks end."""
+    import ctypes
+    import torch
+    T, B, _ = x.shape
+    I, n = grus[0][0].insize, grus[0][0].size
+    rows = T * B
+    lens = ragged.current if any(rev for _, rev in grus) else None
+    if lens is not None and (lens.numel() != B or lens.device != x.device):
+        raise ValueError("ragged lengths do not match the batch")
+    y = _alloc_out(x, T, B, n, out)
+    tmp = [_scratch((T, B, n), torch.float32, x.device) for _ in range(min(2, len(grus) - 1))]
+    descs = (_lib.GruStackLayer * len(grus))()
+    cur = x
+    for k, (g, rev) in enumerate(grus):
+        dst = y if k == len(grus) - 1 else tmp[k & 1]
+        descs[k] = _lib.GruStackLayer(cur.data_ptr(), _row_stride(cur), dst.data_ptr(), _row_stride(dst), g.bar16_pack().data_ptr(),
+                                      1 if rev else _lib.SLK_GRU_STACK_NO_LENS, 0)
+        cur = dst
+    nl = len(grus)
+    with profiler.region("gru_fused", nl * 6.0 * rows * n * (n + I), nl * 4.0 * rows * (I + n),
+                         f16x3_flops=nl * 6.0 * rows * n * I, f16x2_flops=nl * 6.0 * rows * n * n):
+        _lib.check(_lib.lib().slk_gru_bar16_stack_f32(nl, descs, I, n, T, B, None if lens is None else lens.data_ptr(), _stream()),
+                   "Gru")
+    return y
+
+
+def run_layers(seq, x, out=None):
+    """The layers of `seq` one after the other (Serial._forward, pipeline.Basecaller); consecutive Gru layers that can share a launch
+    (_gru_stack_ok) do, up to SLK_GRU_STACK_MAX at a time."""
+    i, last = 0, len(seq)
+    while i < last:
+        grus = []
+        while i + len(grus) < last and len(grus) < _lib.SLK_GRU_STACK_MAX:
+            g = _as_gru(seq[i + len(grus)])
+            if g is None or not _gru_stack_ok(grus + [g], x):
+                break
+            grus.append(g)
+        if len(grus) > 1:
+            x = _gru_stack_run(grus, x, out if i + len(grus) == last else None)
+            i += len(grus)
+        else:
+            x = seq[i]._forward(x, out if i + 1 == last else None, False)
+            i += 1
+    return x
 
 
 def _keeps_time(layer):

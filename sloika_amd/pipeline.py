@@ -107,8 +107,7 @@ class Basecaller(object):
         keep = layers._HINTS.in_flight, layers._HINTS.deterministic       # (thread local: one forward pass per host thread at a time)
         layers._HINTS.in_flight, layers._HINTS.deterministic = self.in_flight, self.deterministic
         try:
-            for layer in rest:
-                x = layer._forward(x, None, False)
+            x = layers.run_layers(rest, x)
         finally:
             layers._HINTS.in_flight, layers._HINTS.deterministic = keep
         return x
@@ -180,8 +179,7 @@ class Basecaller(object):
         try:
             with layers.ragged(lengths) as ctx:
                 x = first(ctx)
-                for layer in self.network.layers:
-                    x = layer._forward(x, None, False)
+                x = layers.run_layers(self.network.layers, x)
                 out_lengths = layers.ragged.current.contiguous()
         finally:
             layers._HINTS.in_flight, layers._HINTS.deterministic = keep
@@ -335,9 +333,7 @@ class Basecaller(object):
         try:
             with layers.ragged(nsamp) as ctx:
                 x = batch.normalise_reads_ragged(padded, ctx.lengths)      # per-read normalisation (basecall.py:117-118)
-                hid = x
-                for layer in net.layers[:-1]:
-                    hid = layer._forward(hid, None, False)
+                hid = layers.run_layers(net.layers[:-1], x)
                 lengths = layers.ragged.current
                 packed = self._fused_pack(net.layers[-1], hid)
                 pack = packed[0] if packed is not None else None
@@ -441,9 +437,7 @@ class Basecaller(object):
         layers._HINTS.in_flight, layers._HINTS.deterministic = 1, self.deterministic
         try:
             with layers.ragged(nev):
-                hid = x
-                for layer in net.layers[:-1]:
-                    hid = layer._forward(hid, None, False)
+                hid = layers.run_layers(net.layers[:-1], x)
                 lengths = layers.ragged.current
                 logits, stats, ld = net.layers[-1].logits_and_stats(hid)
         finally:
