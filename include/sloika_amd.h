@@ -719,6 +719,31 @@ SLK_API int slk_adamski_update_f32(float *param, const float *grad, float *momen
 SLK_API int slk_sgd_update_f32(float *param, const float *grad, float *vel, size_t n, float rate, float momentum, float clip,
                        float l2, float gscale, slk_stream_t stream);
 
+/* Read accuracy: what misc/align.py gets from `bwa mem -A 1 -B 2 -O 2 -E 1` (align.py:22) and from pysam's walk over every
+ * alignment's CIGAR and NM tag (samacc, align.py:70-133), computed on the device (csrc/align.hip, design/align.md).  This is the
+ * OPTIMAL local alignment with affine gaps under those scores (a gap of k letters costs gap_open + k * gap_extend), not bwa's
+ * heuristic.  Ties: a gap's opening beats its extension; in a cell the diagonal beats a deletion beats an insertion; a cell whose
+ * best is <= 0 is empty; the alignment ends in the cell of greatest score, smallest query index, then smallest reference index.
+ *   slk_align_pass_width (host only): P, the reference columns one pass of the kernel covers; references longer than P need the
+ *     workspace.
+ *   slk_align_local_workspace_bytes: bytes of workspace for B pairs whose queries have at most max_qlen and whose references at most
+ *     max_rlen letters (0 when max_rlen <= P, or when a bound is beyond the limit below).
+ *   slk_align_local_batch_u8: q:[B][ldq] bytes, row b valid for qlen[b] letters (device int32: what slk_paths_to_bases writes, so a
+ *     call's bases are aligned where they lie); r: the references end to end, pair b's at r[roff[b] .. roff[b + 1]) (roff:[B + 1]
+ *     device int64).  Letters are compared for equality.  max_qlen / max_rlen (host): upper bounds of the lengths, at most 65535
+ *     each -- the counts are carried in 16-bit fields -- SLK_ERR_INVALID_ARG beyond that, as for match or gap_extend < 1, mismatch or
+ *     gap_open < 0 or any score > 16384.  A pair whose device-side length exceeds the bound it was launched with is not truncated:
+ *     its row is (-1, 0, ...).  out:[B][9] int32 = score, q_start, q_end, r_start, r_end (0-based, half open), match, mismatch,
+ *     insertion (query letters against a gap), deletion (reference letters against a gap); all 0 for the empty alignment.
+ *   slk_revcomp_u8: out[off[b] + k] = complement(seq[off[b + 1] - 1 - k]) for B packed sequences (off:[B + 1] device int64, max_len
+ *     (host) >= the longest); A<->T, C<->G, every other byte unchanged; out must not be seq (the '-' strand of align.py:40-41).    */
+SLK_API int slk_align_pass_width(void);
+SLK_API size_t slk_align_local_workspace_bytes(int B, int max_qlen, int max_rlen);
+SLK_API int slk_align_local_batch_u8(const uint8_t *q, long ldq, const int32_t *qlen, const uint8_t *r, const int64_t *roff, int B,
+                                     int max_qlen, int max_rlen, int match, int mismatch, int gap_open, int gap_extend, int32_t *out,
+                                     void *workspace, size_t workspace_bytes, slk_stream_t stream);
+SLK_API int slk_revcomp_u8(const uint8_t *seq, const int64_t *off, int B, long max_len, uint8_t *out, slk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

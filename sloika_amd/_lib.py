@@ -136,6 +136,10 @@ PROTOTYPES = {
     "slk_train_col2im_f32": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp]),
     "slk_adamski_update_f32": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _f, _f, _f, _vp]),
     "slk_sgd_update_f32": (_i, [_vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _vp]),
+    "slk_align_pass_width": (_i, []),
+    "slk_align_local_workspace_bytes": (_sz, [_i, _i, _i]),
+    "slk_align_local_batch_u8": (_i, [_vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "slk_revcomp_u8": (_i, [_vp, _vp, _i, _l, _vp, _vp]),
 }
 
 _lib = None

@@ -1,5 +1,7 @@
 """Basecall the example reads of tests/golden/reads.npz with the trained pretrained.pkl weights and compare with the basecall
-ONT's software stored in the fast5 files (sequence identity from the edit distance)."""
+ONT's software stored in the fast5 files: accuracy and identity of the optimal local alignment on the device (sloika_amd.align, the
+samacc row of misc/align.py) and, beside it, the older figure 1 - edit distance / longer length from a host loop.  They are different
+measures: the edit distance is global and charges every unaligned end, the alignment is local and reports its coverage."""
 import os
 import sys
 import time
@@ -22,7 +24,7 @@ def edit_distance(a, b):
 
 
 def main():
-    from sloika_amd import basecall, bio, models
+    from sloika_amd import align, basecall, bio, models
     g = np.load(os.path.join(ROOT, "tests", "golden", "reads.npz"))
     net = models.from_weights_npz(os.path.join(ROOT, "tests", "golden", "pretrained_weights.npz"))
     calc_post = net.compile()
@@ -49,8 +51,13 @@ def main():
             dt = time.perf_counter() - t0
             seq = bio.kmers_to_sequence([kmers[i] for i in call], always_move=True)
             d = edit_distance(seq, stored)
-            print("read%d skip=%.0f: %d samples -> %d bases (stored %d) in %.2f s; edit distance %d, identity %.3f; %s..." % (
-                n, skip, nsamp, len(seq), len(stored), dt, d, 1.0 - d / max(len(seq), len(stored)), seq[:50]))
+            res, strand = align.align_batch([seq], [stored], both_strands=True)
+            rows = align.samacc_rows(res, strand, [len(seq)], names=["read%d" % n], min_coverage=0.0)
+            acc = ("alignment (%s): accuracy %.3f, id %.3f, coverage %.3f, match %d mismatch %d insertion %d deletion %d" % (
+                rows[0]['strand'], rows[0]['accuracy'], rows[0]['id'], rows[0]['coverage'], rows[0]['match'], rows[0]['mismatch'],
+                rows[0]['insertion'], rows[0]['deletion'])) if rows else "alignment: empty"
+            print("read%d skip=%.0f: %d samples -> %d bases (stored %d) in %.2f s; %s; edit distance %d, 1 - d / longer %.3f; %s..." % (
+                n, skip, nsamp, len(seq), len(stored), dt, acc, d, 1.0 - d / max(len(seq), len(stored)), seq[:50]))
 
 
 def ragged_throughput():
