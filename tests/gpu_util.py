@@ -20,3 +20,13 @@ def dev(a, dtype=None):
 def stream():
     import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+def assert_grads_close(got, want, tol=2e-4):
+    """Gradients of a training step against the float64 oracle's, relative to the largest entry of each tensor: float32 sums over
+    T*B rows against float64."""
+    assert len(got) == len(want)
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert g.shape == w.shape, k
+        scale = max(float(np.abs(w).max()), 1e-6)
+        np.testing.assert_allclose(g / scale, w / scale, atol=tol, err_msg="parameter %d" % k)

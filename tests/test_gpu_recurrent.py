@@ -137,6 +137,33 @@ def test_lstm_ragged_reverse_vs_oracle(oracle, n):
         np.testing.assert_allclose(y[:tb, b:b + 1], want, atol=TOL, err_msg="chunk %d" % b)
 
 
+@pytest.mark.parametrize("I,winlen,stride,mode", [(1, 4, 1, 'same_left'), (3, 5, 3, 'valid'), (2, 5, 1, 'full'), (1, 11, 5, 'half'),
+                                                  (1, 3, 5, 'valid')])
+def test_convolution_ragged_vs_oracle(oracle, I, winlen, stride, mode):
+    """Ragged batch through a Convolution and a bidirectional Gru: the convolution maps every chunk's length to
+    (length + padding - winlen) // stride + 1 (conv.py:66-77), and over that many output steps chunk b, zero-padded to T, must give
+    what it gives alone -- the reversed Gru starts at the mapped length, so a length mapped wrongly shows in every step of its half.
+    Lengths: the whole batch length, one window, one window plus one sample, and random ones between."""
+    torch = need_gpu()
+    from sloika_amd import layers
+    rs = np.random.RandomState(winlen * 10 + stride)
+    init = lambda shape: (rs.normal(size=shape) * 0.5).astype(np.float32)
+    T = 58
+    lens = [T, winlen, winlen + 1] + [int(v) for v in rs.randint(winlen + 2, T, size=4)]
+    x = np.zeros((T, len(lens), I), dtype=np.float32)
+    for b, tb in enumerate(lens):
+        x[:tb, b] = rs.normal(size=(tb, I))
+    conv = layers.Convolution(I, 16, winlen, stride, init=init, has_bias=True, padding_mode=mode)
+    net = layers.Serial([conv, layers.birnn(layers.Gru(16, 16, init=init, has_bias=True), layers.Gru(16, 16, init=init, has_bias=True))])
+    with layers.ragged(lens):
+        y = net.run(torch.from_numpy(x).cuda()).cpu().numpy()
+    for b, tb in enumerate(lens):
+        want = oracle.run_network(net.spec(), x[:tb, b:b + 1])
+        to = (tb + conv.padding[0] + conv.padding[1] - winlen) // stride + 1
+        assert to >= 1 and want.shape == (to, 1, 32)
+        np.testing.assert_allclose(y[:to, b:b + 1], want, atol=TOL, err_msg="chunk %d of length %d" % (b, tb))
+
+
 def test_layer_input_validation():
     torch = need_gpu()
     from sloika_amd import layers

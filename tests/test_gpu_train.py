@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from tests import ref_reverse_scans
-from tests.gpu_util import need_gpu, dev, stream
+from tests.gpu_util import need_gpu, dev, stream, assert_grads_close as _assert_grads_close
 
 pytestmark = pytest.mark.gpu
 
@@ -32,15 +32,6 @@ def _batch(rs, net, T, B, nfeat=1):
     labels = rs.randint(0, net.size, size=(To, B)).astype(np.int32)
     weights = rs.uniform(0.5, 1.5, size=(To, B)).astype(np.float32)
     return x, labels, weights
-
-
-def _assert_grads_close(got, want, tol=2e-4):
-    """Relative to the largest entry of each tensor: float32 sums over T*B rows against float64."""
-    assert len(got) == len(want)
-    for k, (g, w) in enumerate(zip(got, want)):
-        assert g.shape == w.shape, k
-        scale = max(float(np.abs(w).max()), 1e-6)
-        np.testing.assert_allclose(g / scale, w / scale, atol=tol, err_msg="parameter %d" % k)
 
 
 @pytest.mark.parametrize("n,nstate,T,B,min_prob,l2,drop,bias", [

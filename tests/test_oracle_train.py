@@ -137,3 +137,36 @@ def test_adamski_first_steps_closed_form():
     lr1, md1 = adam.scalars(1e-3)
     assert md1 == pytest.approx(0.9, rel=1e-6)
     assert lr1 == pytest.approx(1e-3 * np.sqrt(1 - 0.999) / (1 - 0.9), rel=1e-4)
+
+
+def _conv_case_names():
+    from tests import conv_train_nets
+    return conv_train_nets.FINITE_DIFFERENCE_CASES
+
+
+@pytest.mark.parametrize("name", _conv_case_names())
+def test_convolution_geometries_match_finite_differences(name):
+    """The networks of tests/test_gpu_train_conv.py (tests/conv_train_nets.py) in float64: convolutions past the first layer, after a
+    recurrent layer, as the branches of a Parallel and under a Gru, at strides above one, even windows, asymmetric padding and input
+    samples that no window covers -- the reference every gradient of that file is compared with."""
+    from tests import conv_train_nets
+    net, spec, x, labels, weights, (min_prob, l2, drop) = conv_train_nets.make(name, np.float64)
+    x = x.astype(np.float64)
+    loss, acc, grads = ot.loss_and_grads(spec, x, labels, weights, min_prob, l2, drop)
+    loss2, acc2 = ot.loss_only(spec, x, labels, weights, min_prob, l2, drop)
+    assert loss == pytest.approx(loss2, rel=1e-12) and acc == acc2
+    assert conv_train_nets.relu_margin(spec, ot._forward(spec, x)[1]) >= 1e-4      # no relu kink within reach of eps
+    params = ot.params_of(spec)
+    assert len(params) == len(grads) == len(net.params()) and all(np.shape(p) == g.shape for p, g in zip(params, grads))
+    rs = np.random.RandomState(7)
+    eps = 1e-6
+    for p, g in zip(params, grads):
+        flat = p.reshape(-1)                       # a view: perturbing it perturbs the network
+        for idx in rs.choice(flat.size, size=min(8, flat.size), replace=False):
+            keep = flat[idx]
+            flat[idx] = keep + eps
+            up, _ = ot.loss_only(spec, x, labels, weights, min_prob, l2, drop)
+            flat[idx] = keep - eps
+            dn, _ = ot.loss_only(spec, x, labels, weights, min_prob, l2, drop)
+            flat[idx] = keep
+            assert g.reshape(-1)[idx] == pytest.approx((up - dn) / (2 * eps), rel=2e-5, abs=1e-8)
