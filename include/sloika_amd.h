@@ -744,6 +744,30 @@ SLK_API int slk_align_local_batch_u8(const uint8_t *q, long ldq, const int32_t *
                                      void *workspace, size_t workspace_bytes, slk_stream_t stream);
 SLK_API int slk_revcomp_u8(const uint8_t *seq, const int64_t *off, int B, long max_len, uint8_t *out, slk_stream_t stream);
 
+/* f6. The forward (sum-product) score of a sequence under a transducer posterior: decode.score / decode.forwards
+ * (sloika/decode.py:96-139), for `nread` (posterior, sequence) pairs in one launch, one workgroup per pair, in float64
+ * (csrc/forward_score.hip, design/forward_score.md).  The score is the reference's up to rounding (it sums in another order and
+ * scales by powers of two); a pair's score has the same bits alone, in any batch, in either layout and in any launch.
+ *   post: rows of `nstate` probabilities, `ld` >= nstate values apart; row t of pair b is row row_off[b] + t * row_step
+ *     (row_off:[nread] device int64).  The network layout [T][B][S] is row_off[b] = b, row_step = B; packed ragged rows are
+ *     row_off = ev_off, row_step = 1.  nrow:[nread] device int32, the rows of each pair (0: the score of no rows).
+ *   seq:[sum npos] int32 column indices, pair b owns pos_off[b] .. pos_off[b + 1] (pos_off:[nread + 1] device int64); a pair may have
+ *     no positions.  max_npos (host): the longest sequence; above slk_forward_score_max_positions() (host only: 8191, the state lives
+ *     in registers, 32 values per thread) the call is refused with SLK_ERR_UNSUPPORTED and nothing is written.  A pair longer than
+ *     max_npos, or with a symbol that is no column, gets NaN and reads nothing out of bounds.
+ *   blank: the column of the stay emission (the reference's is the last, decode.py:131; this project's k-mer transducers have it at
+ *     0).  full: decode.py:122-124, 139 (every position must be emitted: -inf when there are more positions than rows).
+ *   min_prob (float32 rows only): when > 0 every value read goes through decode.prepare_post's transform first (decode.py:36), the
+ *     same bits as slk_prepare_post_f32; must be < 1.  The float64 entry exists so the reference's known answers run unrounded.
+ *   score_out:[nread] float64. */
+SLK_API int slk_forward_score_max_positions(void);
+SLK_API int slk_forward_score_batch_f32(const float *post, long ld, const int64_t *row_off, long row_step, const int32_t *nrow,
+                                        int nstate, const int32_t *seq, const int64_t *pos_off, int nread, int max_npos, int blank,
+                                        int full, float min_prob, double *score_out, slk_stream_t stream);
+SLK_API int slk_forward_score_batch_f64(const double *post, long ld, const int64_t *row_off, long row_step, const int32_t *nrow,
+                                        int nstate, const int32_t *seq, const int64_t *pos_off, int nread, int max_npos, int blank,
+                                        int full, double *score_out, slk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

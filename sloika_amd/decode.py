@@ -4,9 +4,14 @@
     prepare_post(post, min_prob=1e-5, drop_bad=False)      decode.py:21-36
     viterbi(post, klen, skip_pen=0.0, log=False, nbase=4)  decode.py:39-93      -> (score, [states])
     viterbi_batch(post[T,B,S], ...)                        batched extension    -> (scores[B], paths[B,T], lens[B])
+    score(post, seq, full=False)                           decode.py:96-105
+    forwards(post, seq, full=False)                        decode.py:108-139    -> float64 (csrc/forward_score.hip)
+    forwards_batch(post[T,B,S] | rows + row_off, seqs)     batched extension    -> scores[B] float64, on the device
 
 Inputs may be numpy arrays or device tensors; float32 arithmetic (the network's dtype).  float64 input is
-converted to float32 first -- unlike numpy, which would then decode in float64.
+converted to float32 first -- unlike numpy, which would then decode in float64.  The forward score is the exception:
+it runs in float64 on float32 or float64 rows, as numpy does.
+forwards_transpose / backwards_transpose (decode.py:142-211) have no counterpart: design/forward_score.md.
 """
 import numpy as np
 
@@ -196,3 +201,149 @@ def viterbi(post, klen, skip_pen=0.0, log=False, nbase=4):
     scores, paths, lens = viterbi_batch(pd[:, None, :], klen, skip_pen=skip_pen, log=log, nbase=nbase)
     n = int(lens[0].item())
     return np.float32(scores[0].item()), [int(v) for v in paths[0, :n].cpu().numpy()]
+
+
+def forward_max_positions():
+    """The longest sequence score / forwards / forwards_batch take (slk_forward_score_max_positions: the state of a pair lives in
+    the registers of one workgroup)."""
+    return int(_lib.lib().slk_forward_score_max_positions())
+
+
+def _forward_post(post):
+    """`post` as the kernel reads it: float32 or float64, anything else is widened to float64 as numpy would (decode.py:131)."""
+    import torch
+    from . import device as D
+    if isinstance(post, torch.Tensor):
+        if post.dtype not in (torch.float32, torch.float64):
+            raise ValueError("post must be float32 or float64")
+        return post.to(D.device())
+    a = np.asarray(post)
+    if a.dtype != np.float32:
+        a = a.astype(np.float64)
+    return torch.from_numpy(np.ascontiguousarray(a)).to(D.device())
+
+
+def forwards_batch(post, seqs, lengths=None, full=False, blank=-1, min_prob=None, row_off=None):
+    """decode.forwards (decode.py:108-139) for a batch of (posterior, sequence) pairs in one launch (csrc/forward_score.hip): the
+    log-likelihood of each sequence under its posterior, summed over all alignments.
+
+    post: float32 or float64, numpy or device tensor, either
+      * [T, B, S], the network layout, read where it lies (the state axis contiguous, rows evenly spaced: a [:, :, :S] view of wider
+        rows is fine); pair b runs over its first lengths[b] rows (all T when lengths is None; host integers, or an int32
+        device tensor whose values the caller keeps within 0 .. T), or
+      * [R, S] packed rows with row_off [B] or [B + 1] (host integers): pair b owns rows row_off[b] .. row_off[b] + lengths[b] - 1;
+        lengths defaults to the differences of a [B + 1] row_off.
+    seqs: one sequence of column indices per pair (a pair may have none).  blank: the column of the stay emission, -1 = the last, as
+    in the reference.  min_prob: if given (float32 only), every value goes through decode.prepare_post's transform first, i.e. `post`
+    is the raw network output.  full: force full length mapping.
+
+    Returns a device float64 tensor [B].  A sequence longer than forward_max_positions() raises ValueError."""
+    import torch
+    shape = tuple(post.shape)
+    if len(shape) == 3 and row_off is None:
+        T, B, S = shape
+        packed = False
+    elif len(shape) == 2 and row_off is not None:
+        R, S = shape
+        row_off = np.asarray(row_off, dtype=np.int64).reshape(-1)
+        B = len(seqs)
+        if len(row_off) not in (B, B + 1):
+            raise ValueError("row_off needs one entry per pair (or one more, the end of the last)")
+        if lengths is None:
+            if len(row_off) != B + 1:
+                raise ValueError("packed rows need lengths, or a row_off of one entry more than there are pairs")
+            lengths = np.diff(row_off)
+        row_off = row_off[:B]
+        packed = True
+    else:
+        raise ValueError("forwards_batch expects a [time, batch, state] posterior, or [rows, state] with row_off")
+    if len(seqs) != B or B < 1:
+        raise ValueError("forwards_batch needs one sequence per pair (%d sequences for %d pairs)" % (len(seqs), B))
+    if S < 1:
+        raise ValueError("posterior has no states")
+    blank = int(blank)
+    if blank < 0:
+        blank += S
+    if not 0 <= blank < S:
+        raise ValueError("blank column %d outside the %d states" % (blank, S))
+    seqs = [np.asarray(q).reshape(-1) for q in seqs]
+    npos = [len(q) for q in seqs]
+    limit = forward_max_positions()
+    if max(npos) > limit:
+        raise ValueError("a sequence of %d positions is above the forward score's limit of %d" % (max(npos), limit))
+    cat = np.concatenate(seqs).astype(np.int64) if sum(npos) else np.zeros(0, dtype=np.int64)
+    if cat.size and (cat.min() < 0 or cat.max() >= S):
+        raise ValueError("sequence symbols must be columns 0 .. %d of the posterior" % (S - 1))
+    if min_prob is not None and not 0.0 <= float(min_prob) < 1.0:
+        raise ValueError("min_prob must lie in [0, 1)")
+    lens_dev = None
+    if isinstance(lengths, torch.Tensor):
+        if lengths.dtype != torch.int32 or lengths.numel() != B or not lengths.is_cuda or packed:
+            raise ValueError("device lengths must be int32 with one entry per chunk of a [time, batch, state] posterior")
+        lens_dev = lengths.contiguous()
+    else:
+        lens = np.full(B, T, dtype=np.int64) if lengths is None else np.asarray(lengths, dtype=np.int64).reshape(-1)
+        if len(lens) != B or lens.min() < 0:
+            raise ValueError("lengths needs one non-negative row count per pair")
+        if packed:
+            if row_off.min() < 0 or (row_off + lens).max() > R:
+                raise ValueError("a pair's rows lie outside the %d packed rows" % R)
+        elif lens.max() > T:
+            raise ValueError("a pair cannot have more than the posterior's %d rows" % T)
+    if min_prob is not None and float(min_prob) > 0.0 and not str(post.dtype).endswith("float32"):
+        raise ValueError("min_prob applies to float32 posteriors (decode.prepare_post is float32 arithmetic)")
+    from . import device as D
+    pd = _forward_post(post)
+    if pd.stride(-1) != 1 or (not packed and pd.stride(0) != B * pd.stride(1)) or pd.stride(-2) < S:
+        pd = pd.contiguous()
+    ld = pd.stride(-2)
+    dev = pd.device
+    if packed:
+        roff, step = row_off, 1
+    else:
+        roff, step = np.arange(B, dtype=np.int64), B
+    pos_off = np.concatenate([[0], np.cumsum(npos)]).astype(np.int64)
+    # one upload for the offsets; the sequences and (host) lengths as int32 behind them
+    offs = torch.as_tensor(np.concatenate([roff, pos_off])).to(dev)
+    tail = lens.astype(np.int32) if lens_dev is None else np.zeros(1, np.int32)      # (never an empty upload)
+    ints_d = torch.as_tensor(np.concatenate([cat.astype(np.int32), tail])).to(dev)
+    nrow_ptr = lens_dev.data_ptr() if lens_dev is not None else ints_d.data_ptr() + 4 * cat.size
+    score = D.scratch(B, torch.float64, dev, result=True)
+    L = _lib.lib()
+    common = (pd.data_ptr(), ld, offs.data_ptr(), step, nrow_ptr, S, ints_d.data_ptr(), offs.data_ptr() + 8 * B, B, max(npos), blank,
+              int(bool(full)))
+    rows = float(sum(npos) + B) * (float(T) if not packed else float(np.mean(lens)))
+    with profiler.region("forward_score", 3.0 * rows, rows * pd.element_size()):
+        if pd.dtype == torch.float32:
+            rc = L.slk_forward_score_batch_f32(*common, float(min_prob or 0.0), score.data_ptr(), D.stream_ptr())
+        else:
+            rc = L.slk_forward_score_batch_f64(*common, score.data_ptr(), D.stream_ptr())
+    _lib.check(rc, "decode.forwards_batch")
+    return score
+
+
+def forwards(post, seq, full=False):
+    """ The forwards score for sequence (decode.py:108-139)
+
+    :param post: A 2D array or device tensor [time, nstate], float32 or float64; the blank is the last column
+    :param seq: Sequence to map against
+    :param full: Force full length mapping
+
+    :returns: score (numpy float64)
+    """
+    if len(post.shape) != 2:
+        raise ValueError("forwards expects a [time, state] posterior")
+    T, S = post.shape
+    return np.float64(forwards_batch(post, [seq], full=full, row_off=[0, T])[0].item())
+
+
+def score(post, seq, full=False):
+    """  Compute score of a sequence (decode.py:96-105)
+
+    :param post: A 2D array or device tensor [time, nstate]
+    :param seq: Sequence to map against
+    :param full: Force full length mapping
+
+    :returns: score
+    """
+    return forwards(post, seq, full=full)

@@ -312,6 +312,48 @@ class Basecaller(object):
         scores, paths, lens = self.call_chunks(chunks)
         return scores, bio.paths_to_bases(paths, lens, self.kmer_len, alphabet, always_move=True)
 
+    def score_chunks(self, chunks, sequences, full=True, scaling=None):
+        """How likely is each sequence under the network's posterior of its chunk, summed over all alignments: decode.forwards
+        (decode.py:108-139) of basecall.decode_post's prepared posterior (min_prob as in call_chunks), for the whole batch in one
+        launch.  The posterior is read where posteriors() leaves it (network layout, no transpose or copy).
+
+        sequences: one entry per chunk, either an integer array (or tensor) of k-mer states -- what paths[b, :lens[b]] of
+        call_chunks holds, so a call can be scored against its own chunk -- or a base string, cut into its k-mers (bio.seq_to_kmers)
+        and numbered by bio.kmer_mapping.  full, scaling: as decode.forwards / call_chunks.
+        -> device float64 [B], natural-log likelihoods."""
+        import numpy as np
+        from . import bio
+        if not self.transducer:
+            raise NotImplementedError("score_chunks needs a transducer model: without a blank state there is no forward score")
+        if len(sequences) != len(chunks):
+            raise ValueError("score_chunks needs one sequence per chunk (%d for %d)" % (len(sequences), len(chunks)))
+        mapping = None
+        cols = []
+        for q in sequences:
+            if isinstance(q, (str, bytes)):
+                if self.nbase != 4:
+                    raise ValueError("base strings are read in the alphabet ACGT: hand over states for nbase=%d" % self.nbase)
+                if mapping is None:
+                    mapping = bio.kmer_mapping(self.kmer_len)
+                text = q.decode('utf-8') if isinstance(q, bytes) else q
+                try:
+                    st = np.array([mapping[k] for k in bio.seq_to_kmers(text, self.kmer_len)], dtype=np.int64)
+                except KeyError as exc:
+                    raise ValueError("k-mer %s is outside the model's alphabet" % exc)
+            else:
+                st = np.asarray(q.cpu() if hasattr(q, "cpu") else q).astype(np.int64).reshape(-1)
+                if st.size and (st.min() < 0 or st.max() >= self.nbase ** self.kmer_len):
+                    raise ValueError("k-mer states must lie in 0 .. %d" % (self.nbase ** self.kmer_len - 1))
+            cols.append(st + 1)                                 # column 0 is the blank (variables.nstate, transducer=True)
+
+        def run():
+            post = self.posteriors(chunks, scaling)
+            return decode.forwards_batch(post, cols, full=full, blank=0, min_prob=self.min_prob)
+        if self._arena is None:
+            return run()
+        with self._arena:
+            return run()
+
     def _call_padded(self, padded, nsamp):
         """One padded batch of trimmed reads resident on the device ([B, Lmax], read b in its first nsamp[b] samples): per-read
         normalisation, network and decoder with per-read lengths.  -> (scores, paths, lens) on the device."""
