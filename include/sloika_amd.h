@@ -101,8 +101,9 @@ SLK_API int slk_med_mad_normalise_f32(const float *signal, int nchunk, int chunk
                               slk_stream_t stream);
 /* The same per READ for a batch of whole reads of different lengths (sloika/basecall.py:117-118 normalises a read over its own
  * length): read r is lens[r] samples at signal + r*in_stride; element (r, i), i < lens[r], goes to
- * out[r*out_chunk_stride + i*out_sample_stride]; nothing else is written (the caller zero-fills a padded batch).  Exact order
- * statistics by radix selection, any length >= 1; bit-identical to slk_med_mad_normalise_f32 on each read alone.            */
+ * out[r*out_chunk_stride + i*out_sample_stride]; nothing else is written (the caller zero-fills a padded batch) and nothing
+ * behind lens[r] is read.  A read with lens[r] <= 0 is skipped: none of its outputs is written, med_out[r] and mad_out[r] included.
+ * Exact order statistics by radix selection, any length >= 1; bit-identical to slk_med_mad_normalise_f32 on each read alone. */
 SLK_API int slk_med_mad_normalise_ragged_f32(const float *signal, int nread, long in_stride, const int32_t *lens, float *out,
                                              long out_chunk_stride, long out_sample_stride, float *med_out, float *mad_out,
                                              slk_stream_t stream);
