@@ -365,6 +365,22 @@ SLK_API int slk_lstm_f32(const float *x, long ldx, const float *iW, const float 
 #define SLK_POST_LOG 2
 #define SLK_POST_LN 3 /* slk_log_post_f32 only: lp = log(post), no eta (np.log(trans), sloika/transducer.py:30) */
 SLK_API size_t slk_viterbi_kmer_workspace_bytes(int T, int B, int nbase, int klen);
+/* What slk_viterbi_kmer_*_f32 will launch for a shape (host only: nothing is launched, no device is needed).  The decoder takes
+ * its own decisions from the same function, so this is what runs; tests compute their edge lengths from it.
+ *   ws_align : alignment of the workspace in bytes, a power of two (16 or more: fully aligned)
+ *   kernel       : which forward kernel (below)
+ *   blank_steps  : steps per block of blank-column log-posteriors the forward kernel evaluates at once (0: every step on its own)
+ *   staged_rows  : traceback rows the forward kernel collects in LDS before it stores them (0: every row is stored at once)
+ *   tb_row_bytes : bytes of one traceback row of one chunk
+ *   walker_rows  : traceback rows per block the backtrace stages in LDS (min(12288 / tb_row_bytes, T))
+ *   walker_dma   : 1 if the backtrace stages through its LDS-DMA ring of three blocks, 0 for the plain copy loop           */
+#define SLK_VIT_KERNEL_GENERIC 0    /* any nbase: one workgroup per chunk, a traceback byte per state */
+#define SLK_VIT_KERNEL_WORKGROUP4 1 /* nbase 4: one workgroup per chunk, packed traceback */
+#define SLK_VIT_KERNEL_WAVE4 2      /* nbase 4, large batches: one wave per chunk, packed traceback */
+typedef struct slk_viterbi_plan {
+    int kernel, blank_steps, staged_rows, tb_row_bytes, walker_rows, walker_dma;
+} slk_viterbi_plan;
+SLK_API int slk_viterbi_kmer_plan(int T, int B, int nbase, int klen, int ws_align, slk_viterbi_plan *plan);
 SLK_API int slk_viterbi_kmer_f32(const float *post, int T, int B, int nbase, int klen, float skip_pen, int input_mode,
                          float min_prob, void *workspace, size_t workspace_bytes, float *score_out,
                          int32_t *path_out, int32_t *len_out, slk_stream_t stream);

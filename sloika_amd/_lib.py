@@ -25,7 +25,14 @@ class GruStackLayer(C.Structure):
     _fields_ = [("x", C.c_void_p), ("ldx", C.c_long), ("h_out", C.c_void_p), ("ldh", C.c_long), ("pack", C.c_void_p),
                 ("reverse", C.c_int), ("reserved", C.c_int)]
 
+
+class ViterbiPlan(C.Structure):
+    """slk_viterbi_plan of include/sloika_amd.h (slk_viterbi_kmer_plan: what the stand-alone decoder launches for a shape)."""
+    _fields_ = [("kernel", C.c_int), ("blank_steps", C.c_int), ("staged_rows", C.c_int), ("tb_row_bytes", C.c_int),
+                ("walker_rows", C.c_int), ("walker_dma", C.c_int)]
+
 POST_RAW, POST_PLAIN, POST_LOG, POST_LN = 0, 1, 2, 3
+VIT_KERNEL_GENERIC, VIT_KERNEL_WORKGROUP4, VIT_KERNEL_WAVE4 = 0, 1, 2
 
 _vp, _i, _l, _f, _sz, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t, C.c_double
 
@@ -83,6 +90,7 @@ PROTOTYPES = {
     "slk_lstm_workspace_bytes": (_sz, [_i, _i, _i]),
     "slk_lstm_f32": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "slk_viterbi_kmer_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "slk_viterbi_kmer_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(ViterbiPlan)]),
     "slk_viterbi_kmer_f32": (_i, [_vp, _i, _i, _i, _i, _f, _i, _f, _vp, _sz, _vp, _vp, _vp, _vp]),
     "slk_log_post_f32": (_i, [_vp, _vp, _sz, _i, _f, _vp]),
     "slk_prepare_post_f32": (_i, [_vp, _vp, _sz, _f, _vp]),

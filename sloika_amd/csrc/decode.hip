@@ -251,7 +251,7 @@ __global__ void __launch_bounds__(1024) viterbi_forward_kernel(const float *__re
         for (int w = 1; w < nw; w++)
             if (redv[w] > bv || (redv[w] == bv && redi[w] < bi)) { bv = redv[w]; bi = redi[w]; }
         score_out[b] = bv;
-        best_out[b] = bi;
+        best_out[b] = bi == 0x7fffffff ? 0 : bi;             // no score above -inf: np.argmax's state 0
     }
 }
 
@@ -439,7 +439,7 @@ __global__ void __launch_bounds__(1024) viterbi_forward4_kernel(const float *__r
         for (int w = 1; w < nwv; w++)
             if (redv[w] > bv || (redv[w] == bv && redi[w] < bi)) { bv = redv[w]; bi = redi[w]; }
         score_out[b] = bv;
-        best_out[b] = bi;
+        best_out[b] = bi == 0x7fffffff ? 0 : bi;             // no score above -inf: np.argmax's state 0
     }
 }
 
@@ -625,7 +625,7 @@ __global__ void __launch_bounds__(256) viterbi_forward4_wave_kernel(const float 
     }
     if (lane == 0) {
         score_out[b] = bv;
-        best_out[b] = bi;
+        best_out[b] = bi == 0x7fffffff ? 0 : bi;             // no score above -inf: np.argmax's state 0
     }
 }
 
@@ -902,23 +902,75 @@ extern "C" size_t slk_viterbi_kmer_workspace_bytes(int T, int B, int nbase, int 
     return tb + sizeof(int32_t) * (size_t)B + 256;
 }
 
+static int vit_threads(int nrem1) { return nrem1 < 64 ? 64 : (nrem1 > 1024 ? 1024 : ((nrem1 + 63) / 64) * 64); }
+
+// rows per staged block of the traceback walker (0: a row does not fit), and whether the LDS-DMA ring can stage them
+static int vbt_rows(int rowbytes, int T, size_t align, int *dma)
+{
+    const int tblk = VBT_BLOCK / rowbytes;
+    *dma = (VBT_BLOCK % rowbytes == 0) && (rowbytes % 16 == 0) && (align % 16 == 0);
+    return tblk > T ? T : tblk;
+}
+
+// Every dispatch decision of launch_viterbi, in one place: slk_viterbi_kmer_plan reports it, launch_viterbi executes it.
+// *threads: the forward kernel's workgroup size.
+static int vit_plan(int T, int B, int nbase, int nkmer, size_t ws_align, slk_viterbi_plan *p, int *threads)
+{
+    if (nbase != 4 && nbase != 5) return SLK_ERR_UNSUPPORTED;
+    const int nrem1 = nkmer / nbase;
+    if (nrem1 > 1024) return SLK_ERR_UNSUPPORTED;
+    if (nbase == 4 && nkmer <= 1024 && nkmer >= 64 && B >= 1536) {
+        // one wave per chunk, four chunks per workgroup: fewer instructions per (chunk, step), but a lone wave per SIMD
+        // cannot hide its own dependent-issue and memory latency -- it wins once there are ~2 chunks per SIMD (1024 SIMDs)
+        p->kernel = SLK_VIT_KERNEL_WAVE4;
+        *threads = 256;                                      // four chunks, one wave each
+        p->blank_steps = 64;
+        p->staged_rows = 0;
+    } else if (nbase == 4) {
+        p->kernel = SLK_VIT_KERNEL_WORKGROUP4;
+        *threads = vit_threads(nrem1);
+        p->blank_steps = *threads;                           // viterbi_forward4_kernel: one blank log-posterior per thread and block
+        p->staged_rows = VIT_TBS;
+    } else {
+        p->kernel = SLK_VIT_KERNEL_GENERIC;
+        *threads = vit_threads(nrem1);
+        p->blank_steps = 0;                                  // evaluated by every thread, every step
+        p->staged_rows = 0;
+    }
+    p->tb_row_bytes = p->kernel == SLK_VIT_KERNEL_GENERIC ? nkmer : nkmer / 2;      // bytes, or packed 16-bit words per four states
+    p->walker_rows = vbt_rows(p->tb_row_bytes, T, ws_align, &p->walker_dma);
+    return p->walker_rows < 1 ? SLK_ERR_UNSUPPORTED : SLK_OK;
+}
+
+static size_t pointer_alignment(const void *ptr)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(ptr) | 16;      // 16 bytes is all that anything here asks for
+    return (size_t)(a & (~a + 1));
+}
+
+extern "C" int slk_viterbi_kmer_plan(int T, int B, int nbase, int klen, int ws_align, slk_viterbi_plan *plan)
+{
+    int nkmer;
+    if (!plan || T < 1 || B < 1 || ws_align < 1 || (ws_align & (ws_align - 1)) || !vit_dims(nbase, klen, &nkmer))
+        return SLK_ERR_INVALID_ARG;
+    int threads;
+    return vit_plan(T, B, nbase, nkmer, (size_t)ws_align, plan, &threads);
+}
+
 template <int NB>
 static int launch_viterbi(const float *post, const float *stats, long ld, int T, int B, int klen, int nkmer, float skip_pen, int mode, float min_prob,
                           uint8_t *tb, int32_t *best, float *score_out, int32_t *path_out, int32_t *len_out,
                           const int *lens, hipStream_t s)
 {
-    int nrem1 = nkmer / NB;
-    int threads = nrem1 < 64 ? 64 : (nrem1 > 1024 ? 1024 : ((nrem1 + 63) / 64) * 64);
-    if (nrem1 > 1024) return SLK_ERR_UNSUPPORTED;
-    size_t lds = sizeof(float) * ((size_t)nkmer + nrem1 + 16) + sizeof(int) * ((size_t)nrem1 + 16);
+    slk_viterbi_plan plan;
+    int threads;
+    int rc = vit_plan(T, B, NB, nkmer, pointer_alignment(tb), &plan, &threads);
+    if (rc != SLK_OK) return rc;
+    const int nrem1 = nkmer / NB;
     float one_m = (float)(1.0 - (double)min_prob);
-    bool packed_tb = false;                                  // which traceback format the forward kernel writes
-    if (NB == 4 && nkmer <= 1024 && nkmer >= 64 && B >= 1536) {
-        packed_tb = true;
-        // one wave per chunk, four chunks per workgroup: fewer instructions per (chunk, step), but a lone wave per SIMD
-        // cannot hide its own dependent-issue and memory latency -- it wins once there are ~2 chunks per SIMD (1024 SIMDs)
-        const size_t ldsw = sizeof(float) * 4 * ((size_t)nkmer + 64);
-        const dim3 grid((B + 3) / 4), block(256);
+    if (plan.kernel == SLK_VIT_KERNEL_WAVE4) {
+        const size_t ldsw = sizeof(float) * (threads / 64) * ((size_t)nkmer + 64);
+        const dim3 grid((B + 3) / (threads / 64)), block(threads);
         if (stats)
             hipLaunchKernelGGL((viterbi_forward4_wave_kernel<true>), grid, block, ldsw, s, post,
                                reinterpret_cast<const float2 *>(stats), ld, T, B, nkmer, skip_pen, mode, min_prob, one_m, tb,
@@ -926,8 +978,7 @@ static int launch_viterbi(const float *post, const float *stats, long ld, int T,
         else
             hipLaunchKernelGGL((viterbi_forward4_wave_kernel<false>), grid, block, ldsw, s, post, nullptr, ld, T, B, nkmer,
                                skip_pen, mode, min_prob, one_m, tb, best, score_out, lens);
-    } else if constexpr (NB == 4) {
-        packed_tb = true;
+    } else if (plan.kernel == SLK_VIT_KERNEL_WORKGROUP4) {
         const size_t lds4 = sizeof(float) * (2 * (size_t)nkmer + threads + 32 + (size_t)VIT_TBS * nrem1);
         if (stats)
             hipLaunchKernelGGL((viterbi_forward4_kernel<true>), dim3(B), dim3(threads), lds4, s, post,
@@ -936,37 +987,33 @@ static int launch_viterbi(const float *post, const float *stats, long ld, int T,
         else
             hipLaunchKernelGGL((viterbi_forward4_kernel<false>), dim3(B), dim3(threads), lds4, s, post, nullptr, ld, T, B,
                                nkmer, skip_pen, mode, min_prob, one_m, tb, best, score_out, lens);
-    } else if (stats)
-        hipLaunchKernelGGL((viterbi_forward_kernel<NB, true>), dim3(B), dim3(threads), lds, s, post,
-                           reinterpret_cast<const float2 *>(stats), ld, T, B, nkmer, skip_pen, mode, min_prob, one_m, tb, best,
-                           score_out, lens);
-    else
-        hipLaunchKernelGGL((viterbi_forward_kernel<NB, false>), dim3(B), dim3(threads), lds, s, post, nullptr, ld, T, B, nkmer,
-                           skip_pen, mode, min_prob, one_m, tb, best, score_out, lens);
-    int rc = slk_launch_status();
+    } else {
+        const size_t lds = sizeof(float) * ((size_t)nkmer + nrem1 + 16) + sizeof(int) * ((size_t)nrem1 + 16);
+        if (stats)
+            hipLaunchKernelGGL((viterbi_forward_kernel<NB, true>), dim3(B), dim3(threads), lds, s, post,
+                               reinterpret_cast<const float2 *>(stats), ld, T, B, nkmer, skip_pen, mode, min_prob, one_m, tb, best,
+                               score_out, lens);
+        else
+            hipLaunchKernelGGL((viterbi_forward_kernel<NB, false>), dim3(B), dim3(threads), lds, s, post, nullptr, ld, T, B, nkmer,
+                               skip_pen, mode, min_prob, one_m, tb, best, score_out, lens);
+    }
+    rc = slk_launch_status();
     if (rc != SLK_OK) return rc;
-    const int rowbytes = packed_tb ? nkmer / 2 : nkmer;
-    int tblk = VBT_BLOCK / rowbytes;                         // rows per staged block
-    if (tblk < 1) return SLK_ERR_UNSUPPORTED;
-    const int dma = (VBT_BLOCK % rowbytes == 0) && (rowbytes % 16 == 0) && ((reinterpret_cast<uintptr_t>(tb) & 15) == 0);
-    if (tblk > T) tblk = T;
-    if (packed_tb)
-        hipLaunchKernelGGL((viterbi_backtrace_kernel<NB, true>), dim3(B), dim3(256), 0, s, tb, best, T, nkmer, tblk, dma, path_out,
-                           len_out, lens);
+    if (plan.kernel != SLK_VIT_KERNEL_GENERIC)
+        hipLaunchKernelGGL((viterbi_backtrace_kernel<NB, true>), dim3(B), dim3(256), 0, s, tb, best, T, nkmer, plan.walker_rows,
+                           plan.walker_dma, path_out, len_out, lens);
     else
-        hipLaunchKernelGGL((viterbi_backtrace_kernel<NB, false>), dim3(B), dim3(256), 0, s, tb, best, T, nkmer, tblk, dma, path_out,
-                           len_out, lens);
+        hipLaunchKernelGGL((viterbi_backtrace_kernel<NB, false>), dim3(B), dim3(256), 0, s, tb, best, T, nkmer, plan.walker_rows,
+                           plan.walker_dma, path_out, len_out, lens);
     return slk_launch_status();
 }
 
 int slk_backtrace_packed4(const uint8_t *tb, const int32_t *best, int T, int B, int nkmer, int32_t *path_out, int32_t *len_out,
                           const int *lens, hipStream_t s)
 {
-    const int rowbytes = nkmer / 2;
-    int tblk = VBT_BLOCK / rowbytes;
+    int dma;
+    const int tblk = vbt_rows(nkmer / 2, T, pointer_alignment(tb), &dma);
     if (tblk < 1) return SLK_ERR_UNSUPPORTED;
-    const int dma = (VBT_BLOCK % rowbytes == 0) && (rowbytes % 16 == 0) && ((reinterpret_cast<uintptr_t>(tb) & 15) == 0);
-    if (tblk > T) tblk = T;
     hipLaunchKernelGGL((viterbi_backtrace_kernel<4, true>), dim3(B), dim3(256), 0, s, tb, best, T, nkmer, tblk, dma, path_out,
                        len_out, lens);
     return slk_launch_status();

@@ -73,6 +73,18 @@ def _check(oracle, rs, T, B, K, skip=0.0, ragged=False, wscale=0.5, xscale=1.0, 
     s2, p2, l2 = decode.viterbi_logits_batch(logits, stats, 5, T, B, ld=ld, skip_pen=skip, lengths=lens)
     np.testing.assert_allclose(scn, s2.cpu().numpy(), rtol=2e-6, atol=1e-4)
     assert (pa == p2).all(dim=1).float().mean().item() >= 0.75
+    # ... and, strictly, what the oracle decodes from the log-posteriors the two-kernel path itself consumed (slk_log_post_logits_f32
+    # on the same logits and statistics), over each chunk's own steps: bit for bit, the -1 padding up to T included
+    from sloika_amd import _lib
+    from tests.gpu_util import stream
+    lp2 = torch.empty((T, B, 1025), dtype=torch.float32, device="cuda")
+    assert _lib.lib().slk_log_post_logits_f32(logits.data_ptr(), ld, stats.data_ptr(), lp2.data_ptr(), T * B, 1025, 1e-5, stream()) == 0
+    lp2, s2n, p2n, l2n = lp2.cpu().numpy(), s2.cpu().numpy(), p2.cpu().numpy(), l2.cpu().numpy()
+    for bb in range(B):
+        Tb = int(ln[bb])
+        o_s, o_p, o_l = oracle.viterbi_batch(np.ascontiguousarray(lp2[:Tb, bb:bb + 1]), 5, skip_pen=skip)
+        assert o_l[0] == l2n[bb] and o_s[0] == s2n[bb], (bb, Tb)
+        assert np.array_equal(o_p[0, :o_l[0]], p2n[bb, :o_l[0]]) and (p2n[bb, o_l[0]:] == -1).all(), (bb, Tb)
 
 
 @pytest.mark.parametrize("T,B,K,skip,ragged", [
