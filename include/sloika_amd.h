@@ -785,6 +785,47 @@ SLK_API int slk_forward_score_batch_f64(const double *post, long ld, const int64
                                         int nstate, const int32_t *seq, const int64_t *pos_off, int nread, int max_npos, int blank,
                                         int full, double *score_out, slk_stream_t stream);
 
+/* f7. Where on a genome a call lies, and the reference of each read cut from it: the locating half of what misc/align.py gets from
+ * `bwa mem -k14 -W20 -r10 ... genome.fa calls.fa` (align.py:46-67) and the cut of misc/get_refs_from_sam.py:40-68, on the device
+ * (csrc/genome_map.hip, design/genome_map.md).  A seed-and-vote stage chooses, per query and strand, a band of diagonals; the
+ * alignment inside the window that band gives is slk_align_local_batch_u8's, unchanged.  Integer only: no result depends on the order
+ * in which anything arrives.  Letters are bytes, A C G T = 0..3, any other byte breaks every k-mer that holds it; a k-mer's code is the
+ * base-4 number of its k letters, first letter most significant; k is 8..15 (SLK_ERR_INVALID_ARG otherwise).
+ *   slk_genome_kmer_keys_u8: genome:[G] bytes, the contigs end to end, contig c at contig_off[c] .. contig_off[c + 1] (contig_off:
+ *     [ncontig + 1] device int64, ascending, contig_off[ncontig] = G; ncontig >= 1); G < 2^31 (host), SLK_ERR_INVALID_ARG beyond.
+ *     keys:[G] int64, keys[p] = code << 32 | p; a k-mer that holds another byte, crosses its contig's end or runs past G has the code
+ *     field 0x7FFFFFFF, so that it sorts behind every real code.  nvalid: one device int32, set to the number of real codes (the
+ *     entry zeroes it first).  The caller sorts `keys` ascending (they are distinct: the order is unique) before the next entry.
+ *   slk_genome_seed_workspace_bytes: bytes of workspace for B queries of at most max_qlen letters on a genome of G letters: per
+ *     workgroup one int32 per bin and two per query position, for min(2 B, 2048) workgroups or as many as fit in 4 GiB (at least
+ *     one); 0 for B = 0 or a shape the entry below refuses.  The entry takes any workspace that holds one workgroup's share and
+ *     launches as many workgroups as the workspace it is given holds.
+ *   slk_genome_seed_votes_u8: q:[B][ldq] bytes, row b valid for qlen[b] letters (device int32: the buffer slk_paths_to_bases writes);
+ *     keys: the SORTED keys, of which the first nvalid (host) are real.  For each query, strand s (0: the query; 1: its reverse
+ *     complement, formed from the same letters) and position i with a valid k-mer: its occurrences in the genome -- none of them
+ *     when there are more than max_occ (1..4096) -- each at p give the diagonal D = p - i + 65536, counted in the bins D / bin_width
+ *     and D / bin_width - 1 (bin b covers the diagonals [b W, (b + 2) W)).  bin_width: a power of two, 2..32768, and
+ *     max_qlen + bin_width <= 65536 (then D >= bin_width and no bin is negative); SLK_ERR_INVALID_ARG otherwise, as for
+ *     max_qlen > 65535 or ldq < max_qlen.  out:[B][2][4] int32 = bin (greatest count; ties go to the smallest bin; 0 without a vote),
+ *     votes (that count), second (the greatest count among bins further than 2 from `bin`), nseed (valid k-mers not skipped for
+ *     max_occ).  A query shorter than k or without a valid k-mer has votes = 0.  A query whose device-side length is negative or
+ *     exceeds max_qlen is not truncated: bin = -1 on both strands.  workspace: 4-byte aligned, SLK_ERR_WORKSPACE when it holds less
+ *     than one workgroup's share; its contents on entry do not matter (a workgroup zeroes its share, and leaves it zero).
+ *   slk_genome_windows_u8: for B half-open spans [start[b], end[b]) of the genome (device int64) writes the span -- or, where
+ *     minus[b] != 0 (device int32), its reverse complement, by slk_revcomp_u8's rule: A<->T, C<->G, every other byte unchanged -- to
+ *     out[out_off[b] ..], end to end: out_off:[B + 1] device int64 with out_off[b + 1] - out_off[b] = end[b] - start[b], so `out` and
+ *     `out_off` are the aligner's r / roff as they lie, and the per-read references of get_refs_from_sam.py:57-64.  max_len (host) >=
+ *     the longest span.  A span that is not inside [0, G], or whose length disagrees with out_off, is skipped: nothing is read or
+ *     written for it.  out must not be genome.                                                                                   */
+SLK_API int slk_genome_kmer_keys_u8(const uint8_t *genome, const int64_t *contig_off, int ncontig, long G, int k, int64_t *keys,
+                                    int32_t *nvalid, slk_stream_t stream);
+SLK_API size_t slk_genome_seed_workspace_bytes(int B, int max_qlen, long G, int bin_width);
+SLK_API int slk_genome_seed_votes_u8(const uint8_t *q, long ldq, const int32_t *qlen, int B, int max_qlen, const int64_t *keys,
+                                     int nvalid, long G, int k, int bin_width, int max_occ, int32_t *out, void *workspace,
+                                     size_t workspace_bytes, slk_stream_t stream);
+SLK_API int slk_genome_windows_u8(const uint8_t *genome, long G, const int64_t *start, const int64_t *end, const int32_t *minus,
+                                  const int64_t *out_off, int B, long max_len, uint8_t *out, slk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

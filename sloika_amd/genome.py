@@ -1,0 +1,332 @@
+"""Locate calls on a genome on the device and cut per-read references (reference: misc/align.py:46-67, the genome that
+`bwa mem -k14` is handed, and misc/get_refs_from_sam.py:40-68).
+
+`align.align_batch` needs one reference per read, already cut to the read's locus; a user with a run of reads and a genome FASTA
+has neither bwa nor pysam here.  `Index` holds the genome and its sorted k-mer keys on the device; `Index.map` chooses per read and
+strand a window of the genome by seed and vote (csrc/genome_map.hip) and aligns the read inside it with csrc/align.hip, unchanged.
+
+What is guaranteed (design/genome_map.md): the result is the OPTIMAL local alignment within the chosen window, and equals the
+optimum over the genome whenever that alignment lies inside the window.  It is neither bwa's heuristic nor a proof of global
+optimality: `second` (the best vote elsewhere) and `edge` (the alignment ran into a window end) are what to filter on.  Repeats
+longer than a read are ambiguous, as for any mapper; supplementary or chimeric placements are not reported.
+
+There is no CPU fallback, like the rest of the package.
+"""
+import os
+
+import numpy as np
+
+from . import _lib, align, util
+
+#: added to every diagonal p - i: keeps it positive and makes the bins independent of the batch (csrc/genome_map.hip)
+DIAG0 = 65536
+MIN_K, MAX_K = 8, 15
+MAX_GENOME = 1 << 31
+MAX_OCC = 4096
+MAX_BIN_WIDTH = 32768
+#: the columns of a row of Index.seed's result
+SEED_FIELDS = ("bin", "votes", "second", "nseed")
+
+
+def trim_fast5_extension(fn):
+    """get_refs_from_sam.py:34-37."""
+    base, ext = os.path.splitext(fn)
+    return base if ext == ".fast5" else fn
+
+
+def fasta(records):
+    """The ">name\\nseq\\n" text of a list of (name, sequence) (get_refs_from_sam.py:66)."""
+    return ''.join(">{}\n{}\n".format(name, seq if isinstance(seq, str) else bytes(seq).decode('ascii')) for name, seq in records)
+
+
+def window_of(bin_, n, bin_width, drift):
+    """The window of the packed genome that the winning bin of a query of n letters gives, before it is clipped to a contig:
+    bin b covers the diagonals [b W, (b + 2) W), a query on diagonal d lies at [d, d + n), and either end gets W + ceil(drift * n)
+    letters of slack for the indels that move an alignment off its seeds' diagonal."""
+    slack = bin_width + int(np.ceil(drift * n))
+    return bin_ * bin_width - DIAG0 - slack, (bin_ + 2) * bin_width - DIAG0 + n + slack
+
+
+def align_runs(qlens, wlens, limit):
+    """Cut a batch into consecutive runs [lo, hi) whose aligner workspace (slk_align_local_workspace_bytes: 24 bytes per row of
+    the longest query for every pair of a launch whose longest window is wider than one pass) stays within `limit` bytes; a pair
+    above the limit on its own is a run of one.  None: one run."""
+    n = len(qlens)
+    if limit is None or n == 0:
+        return [(0, n)]
+    P = align.PASS_WIDTH
+    runs, lo, mq, mw = [], 0, 0, 0
+    for r in range(n):
+        q2, w2 = max(mq, int(qlens[r])), max(mw, int(wlens[r]))
+        if r > lo and w2 > P and (r - lo + 1) * 24 * q2 > limit:
+            runs.append((lo, r))
+            lo, q2, w2 = r, int(qlens[r]), int(wlens[r])
+        mq, mw = q2, w2
+    runs.append((lo, n))
+    return runs
+
+
+class Index(object):
+    """A genome on the device with the sorted keys of its k-mers.
+
+    contigs: a dict name -> sequence or a list of (name, sequence); sequences are str (upper-cased), bytes or uint8 arrays.
+    k: seed length, 8..15 (14 is bwa's -k14 of align.py:22).  bin_width: W, a power of two; the vote counts diagonals in half
+    overlapping bins of 2 W.  max_occ: a k-mer with more occurrences in the genome casts no vote."""
+
+    def __init__(self, contigs, k=14, bin_width=256, max_occ=64):
+        items = list(contigs.items()) if isinstance(contigs, dict) else [(n, s) for n, s in contigs]
+        if int(k) != k or k < MIN_K or k > MAX_K:
+            raise ValueError("genome: k = %r outside %d..%d" % (k, MIN_K, MAX_K))
+        if int(bin_width) != bin_width or bin_width < 2 or bin_width > MAX_BIN_WIDTH or bin_width & (bin_width - 1):
+            raise ValueError("genome: bin_width = %r is not a power of two in 2..%d" % (bin_width, MAX_BIN_WIDTH))
+        if int(max_occ) != max_occ or max_occ < 1 or max_occ > MAX_OCC:
+            raise ValueError("genome: max_occ = %r outside 1..%d" % (max_occ, MAX_OCC))
+        seqs = [align._as_u8(s) for _, s in items]
+        self.names = [n for n, _ in items]
+        self.lengths = np.array([len(s) for s in seqs], dtype=np.int64)
+        self.offsets = np.concatenate(([0], np.cumsum(self.lengths))).astype(np.int64)
+        self.G = int(self.offsets[-1])
+        if self.G == 0:
+            raise ValueError("genome: the genome is empty")
+        if self.G >= MAX_GENOME:
+            raise ValueError("genome: %d letters; the limit is 2^31 - 1 (positions are the low half of a 64-bit key)" % self.G)
+        self.k, self.bin_width, self.max_occ = int(k), int(bin_width), int(max_occ)
+        _lib.require_gpu()
+        import torch
+        from . import device as D
+        dev = D.device()
+        self.genome = torch.from_numpy(np.concatenate(seqs)).to(dev)
+        self.offsets_dev = torch.from_numpy(self.offsets).to(dev)
+        keys = torch.empty(self.G, dtype=torch.int64, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().slk_genome_kmer_keys_u8(self.genome.data_ptr(), self.offsets_dev.data_ptr(), len(seqs), self.G, self.k,
+                                                      keys.data_ptr(), count.data_ptr(), D.stream_ptr()), "genome_kmer_keys")
+        self.keys = torch.sort(keys).values                     # distinct keys: the order is unique, positions ascend within a code
+        self.nvalid = int(count.item())
+
+    @classmethod
+    def from_fasta(cls, path, **kw):
+        """An index of every record of a FASTA file, in file order (lower case is upper-cased; an 'N' only breaks its k-mers)."""
+        return cls(util.fasta_records(path), **kw)
+
+    def contig_of(self, pos):
+        """Index of the contig that holds position `pos` of the packed genome."""
+        return int(np.searchsorted(self.offsets, pos, side='right')) - 1
+
+    # ---- seed and vote ---------------------------------------------------------------------------------------------------------
+
+    def _upload(self, queries):
+        import torch
+        from . import device as D
+        qs = [align._as_u8(x) for x in queries]
+        B = len(qs)
+        lens = np.array([len(x) for x in qs], dtype=np.int32)
+        max_qlen = int(lens.max()) if B else 0
+        align._check_len(max_qlen, "a query")
+        ldq = max(max_qlen, 1)
+        qh = np.zeros((B, ldq), dtype=np.uint8)
+        for b, x in enumerate(qs):
+            qh[b, :len(x)] = x
+        dev = D.device()
+        return torch.from_numpy(qh).to(dev), ldq, torch.from_numpy(lens).to(dev), lens, max_qlen
+
+    def _seed_device(self, q, ldq, qlen, max_qlen):
+        """q:[B][ldq] uint8 and qlen:[B] int32 on the device -> host int32 [B, 2, 4]."""
+        import torch
+        from . import device as D
+        L = _lib.lib()
+        B = int(qlen.numel())
+        if max_qlen + self.bin_width > DIAG0:
+            raise ValueError("genome: a query of %d letters with bin_width %d: their sum may not exceed %d"
+                             % (max_qlen, self.bin_width, DIAG0))
+        if B == 0:
+            return np.zeros((0, 2, 4), dtype=np.int32)
+        nbytes = L.slk_genome_seed_workspace_bytes(B, max_qlen, self.G, self.bin_width)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=qlen.device)
+        out = torch.empty((B, 2, 4), dtype=torch.int32, device=qlen.device)
+        _lib.check(L.slk_genome_seed_votes_u8(q.data_ptr(), ldq, qlen.data_ptr(), B, max_qlen, self.keys.data_ptr(), self.nvalid,
+                                              self.G, self.k, self.bin_width, self.max_occ, out.data_ptr(), ws.data_ptr(), nbytes,
+                                              D.stream_ptr()), "genome_seed_votes")
+        res = out.cpu().numpy()
+        if (res[:, :, 0] < 0).any():
+            raise ValueError("genome: a query on the device is longer than the bound it was launched with")
+        return res
+
+    def seed(self, queries):
+        """The seed stage alone: host int32 [B, 2, 4], per query and strand (0 '+', 1 '-') the columns SEED_FIELDS as the kernel
+        writes them: the bin of diagonals with the greatest count (ties to the smallest bin; 0 without a vote), that count, the
+        greatest count among bins further than 2 from it, and the number of valid k-mers not skipped for max_occ."""
+        q, ldq, qlen, _, max_qlen = self._upload(list(queries))
+        return self._seed_device(q, ldq, qlen, max_qlen)
+
+    # ---- cut ---------------------------------------------------------------------------------------------------------------------
+
+    def cut(self, start, end, minus):
+        """Spans [start[b], end[b]) of the PACKED genome, reverse-complemented where minus[b], end to end on the device
+        (slk_genome_windows_u8) -> (uint8 device tensor, host int64 offsets [B + 1], device tensor of the offsets)."""
+        import torch
+        from . import device as D
+        start, end = np.asarray(start, dtype=np.int64), np.asarray(end, dtype=np.int64)
+        if ((start < 0) | (end < start) | (end > self.G)).any():
+            raise ValueError("genome: a span outside the genome")
+        lens = end - start
+        off = np.concatenate(([0], np.cumsum(lens))).astype(np.int64)
+        dev = self.genome.device
+        out = torch.empty(max(int(off[-1]), 8), dtype=torch.uint8, device=dev)
+        off_d = torch.from_numpy(off).to(dev)
+        if len(lens) and off[-1]:
+            start_d, end_d = torch.from_numpy(start).to(dev), torch.from_numpy(end).to(dev)
+            minus_d = torch.from_numpy(np.ascontiguousarray(minus, dtype=np.int32)).to(dev)
+            _lib.check(_lib.lib().slk_genome_windows_u8(self.genome.data_ptr(), self.G, start_d.data_ptr(), end_d.data_ptr(),
+                                                        minus_d.data_ptr(), off_d.data_ptr(), len(lens), int(lens.max()),
+                                                        out.data_ptr(), D.stream_ptr()), "genome_windows")
+        return out, off, off_d
+
+    # ---- map ---------------------------------------------------------------------------------------------------------------------
+
+    def _map_device(self, q, ldq, qlen, lens, max_qlen, names, drift, min_votes, scores, workspace_limit):
+        B = len(lens)
+        seeds = self._seed_device(q, ldq, qlen, max_qlen)
+        W = self.bin_width
+        minus = seeds[:, 1, 1] > seeds[:, 0, 1]                 # more votes wins; a tie goes to '+'
+        pick = np.where(minus[:, None], seeds[:, 1, :], seeds[:, 0, :]) if B else np.zeros((0, 4), dtype=np.int32)
+        mapped = pick[:, 1] >= max(int(min_votes), 1)
+        ws, we = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+        contig = np.full(B, -1, dtype=np.int32)
+        for b in np.flatnonzero(mapped):
+            s, e = window_of(int(pick[b, 0]), int(lens[b]), W, drift)
+            c = self.contig_of(min(max((s + e) // 2, 0), self.G - 1))
+            s, e = max(s, int(self.offsets[c])), min(e, int(self.offsets[c + 1]))
+            if e - s > align.MAX_LEN:
+                raise ValueError("genome: the window of read %s is %d letters long; the aligner's limit is %d (a smaller drift, or "
+                                 "shorter reads)" % (names[b] if names is not None else b, e - s, align.MAX_LEN))
+            if e <= s:
+                mapped[b] = False
+                continue
+            ws[b], we[b], contig[b] = s, e, c
+        strand = np.where(minus & mapped, '-', '+').astype('U1')
+        wlens = we - ws
+        ref, roff, roff_d = self.cut(ws, we, strand == '-')
+        res = np.zeros((B, 9), dtype=np.int32)
+        for lo, hi in align_runs(lens, wlens, workspace_limit):
+            if hi > lo:
+                res[lo:hi], _ = align._align_device(q[lo:hi], ldq, qlen[lo:hi], int(lens[lo:hi].max()), ref, roff_d[lo:hi + 1],
+                                                    wlens[lo:hi], scores, False)
+        edge = np.zeros(B, dtype=np.int32)
+        for b in np.flatnonzero(res[:, 0] > 0):
+            rs, re = int(res[b, 3]), int(res[b, 4])
+            head, tail = res[b, 1] > 0, res[b, 2] < lens[b]     # unaligned query letters in front of / behind the alignment
+            if strand[b] == '-':                                # window coordinates back to the forward strand
+                rs, re = int(wlens[b]) - re, int(wlens[b]) - rs
+                head, tail = tail, head
+            c0, c1 = int(self.offsets[contig[b]]), int(self.offsets[contig[b] + 1])
+            edge[b] = int((rs == 0 and ws[b] > c0 and head) or (re == wlens[b] and we[b] < c1 and tail))
+            res[b, 3], res[b, 4] = rs + ws[b] - c0, re + ws[b] - c0
+        contig[res[:, 0] <= 0] = -1                              # (a window in which nothing aligns: unmapped as well)
+        strand[contig < 0] = '+'
+        info = {'contig': contig, 'votes': pick[:, 1].astype(np.int32), 'second': pick[:, 2].astype(np.int32), 'edge': edge,
+                'window_start': ws, 'window_end': we, 'seeds': seeds}
+        return res, strand, info
+
+    def map(self, queries, drift=1.0 / 16, min_votes=3, match=1, mismatch=2, gap_open=2, gap_extend=1, workspace_limit=None,
+            names=None):
+        """Place every query on the genome and align it there.  -> (res, strand, info).
+
+        The strand with more votes wins (a tie goes to '+'); a query with fewer than min_votes is unmapped: its row of `res` is all
+        0 and info['contig'] = -1.  The window of a query of n letters whose winning bin is b is, with slack = W + ceil(drift * n),
+        [b W - 65536 - slack, (b + 2) W - 65536 + n + slack) clipped to the contig that holds its midpoint; a window longer than
+        65535 letters raises a ValueError that names the read.  The windows are cut on the device ('-' ones reverse-complemented)
+        and ONE slk_align_local_batch_u8 launch aligns the queries as they are against them (workspace_limit: bytes of aligner
+        workspace per launch; the batch is then split into consecutive launches, with the same rows).
+
+        res:[B, 9] int32 has align.FIELDS; r_start / r_end are forward-strand coordinates WITHIN THE CONTIG, as a SAM record gives
+        them, the counts of a '-' row those of the alignment against the reverse complement.  info: dict of arrays -- `contig`
+        (index into Index.names, -1 unmapped), `votes`, `second` (the best count among bins further than 2 from the winner: a
+        second locus), `edge` (1: the alignment touches a window end that is not a contig end while the query has unaligned letters
+        on that side -- rerun with a larger drift; nothing is widened silently), `window_start` / `window_end` (packed-genome
+        coordinates) and `seeds`, the kernel's rows."""
+        align._check_scores(match, mismatch, gap_open, gap_extend)
+        queries = list(queries)
+        _lib.require_gpu()
+        q, ldq, qlen, lens, max_qlen = self._upload(queries)
+        return self._map_device(q, ldq, qlen, lens, max_qlen, names, drift, min_votes,
+                                (int(match), int(mismatch), int(gap_open), int(gap_extend)), workspace_limit)
+
+    def map_paths(self, paths, lens, kmer_len, alphabet='ACGT', drift=1.0 / 16, min_votes=3, match=1, mismatch=2, gap_open=2,
+                  gap_extend=1, workspace_limit=None, names=None):
+        """`map` of decoded paths without the called sequences leaving the device: paths:[B, T] int32 device tensor of k-mer states
+        and lens:[B] int32 device tensor, as any `call_*` returns them, become bases through slk_paths_to_bases(always_move=True)
+        and that buffer is the query operand of the seed stage and of the aligner as it lies.  Only the base counts come to the
+        host.  -> (res, strand, info, nbases)."""
+        import torch
+        from . import device as D
+        align._check_scores(match, mismatch, gap_open, gap_extend)
+        _lib.require_gpu()
+        B, Tmax = paths.shape
+        if lens.numel() != B:
+            raise ValueError("genome: %d paths but %d lengths" % (B, lens.numel()))
+        if isinstance(alphabet, str):
+            alphabet = alphabet.encode('utf-8')
+        cap = max(kmer_len * max(Tmax, 1), kmer_len)
+        bases = torch.empty((B, cap), dtype=torch.uint8, device=paths.device)
+        nb = torch.empty((B,), dtype=torch.int32, device=paths.device)
+        _lib.check(_lib.lib().slk_paths_to_bases(paths.data_ptr(), paths.stride(0), lens.data_ptr(), B, kmer_len, len(alphabet), 1,
+                                                 int.from_bytes(alphabet.ljust(8, b'\0'), 'little'), bases.data_ptr(), cap,
+                                                 nb.data_ptr(), D.stream_ptr()), "paths_to_bases")
+        counts = nb.cpu().numpy()
+        max_qlen = int(counts.max()) if B else 0
+        align._check_len(max_qlen, "a query")
+        res, strand, info = self._map_device(bases, cap, nb, counts, max_qlen, names, drift, min_votes,
+                                             (int(match), int(mismatch), int(gap_open), int(gap_extend)), workspace_limit)
+        return res, strand, info, counts
+
+
+def samacc_rows(index, res, strand, info, query_lengths, names=None, min_coverage=0.6):
+    """align.samacc_rows on the rows of Index.map, with the reference's leading 'reference' column (the contig's name,
+    align.py:118).  align.summary applies to the result unchanged."""
+    rows = []
+    for row in align.samacc_rows(res, strand, query_lengths, names=None, min_coverage=min_coverage):
+        b = row['query']
+        out = {'reference': index.names[int(info['contig'][b])], 'query': names[b] if names is not None else b}
+        out.update((key, val) for key, val in row.items() if key != 'query')
+        rows.append(out)
+    return rows
+
+
+def reference_span(res_row, strand, n, contig_len, pad=50):
+    """get_refs_from_sam.py:57-58 in this project's terms: pysam's query_alignment_start / _end are on the sequence as stored in
+    the SAM record, which for '-' is the reverse complement of the read, so lead = q_start, tail = n - q_end for '+' and
+    lead = n - q_end, tail = q_start for '-'.  -> (start, end) within the contig."""
+    qs, qe, rs, re = (int(res_row[j]) for j in (1, 2, 3, 4))
+    lead, tail = (qs, n - qe) if strand == '+' else (n - qe, qs)
+    return max(0, rs - lead - pad), min(int(contig_len), re + tail + pad)
+
+
+def reference_spans(contig_lengths, contig_offsets, res, strand, contig, query_lengths, min_coverage=0.6, pad=50):
+    """The host half of read_references: which reads get a reference (get_refs_from_sam.py:46-55) and the span of the PACKED genome
+    each is cut from -> (indices of the reads kept, starts, ends)."""
+    res = np.asarray(res)
+    keep, start, end = [], [], []
+    for b in range(len(res)):
+        n, c = int(query_lengths[b]), int(contig[b])
+        if c < 0 or res[b, 0] <= 0 or n <= 0 or float(res[b, 2] - res[b, 1]) / n < min_coverage:
+            continue
+        s, e = reference_span(res[b], strand[b], n, contig_lengths[c], pad)
+        keep.append(b)
+        start.append(s + int(contig_offsets[c]))
+        end.append(e + int(contig_offsets[c]))
+    return keep, start, end
+
+
+def read_references(index, res, strand, info, query_lengths, names, min_coverage=0.6, pad=50):
+    """One padded, strand-corrected reference per mapped read: get_refs (get_refs_from_sam.py:40-68) on the rows of Index.map.
+    -> ([(name, sequence str)], [strand-list names]).  Unmapped reads and reads whose aligned part is under min_coverage of their
+    length are dropped; the sequence is contig[start:end] (reference_span), reverse-complemented for '-', cut on the device by
+    slk_genome_windows_u8; the record's name has a '.fast5' extension trimmed, the strand-list name is name + '.fast5'."""
+    keep, start, end = reference_spans(index.lengths, index.offsets, res, strand, info['contig'], query_lengths, min_coverage, pad)
+    if not keep:
+        return [], []
+    out, off, _ = index.cut(start, end, [strand[b] == '-' for b in keep])
+    text = out.cpu().numpy().tobytes().decode('ascii')
+    records = [(trim_fast5_extension(names[b]), text[off[j]:off[j + 1]]) for j, b in enumerate(keep)]
+    return records, [names[b] + ".fast5" for b in keep]
