@@ -257,7 +257,7 @@ SLK_API int slk_gru_f32(const float *x, long ldx, const float *iW, const float *
  * Execution plan: four waves per workgroup, one per SIMD with 512 registers each, stepping in lock step through two
  * s_barrier per time step; projection weights live in accumulation registers.  This is the plan sloika_amd.layers.Gru runs;
  * SLK_ERR_UNSUPPORTED for shapes without an instantiation ((insize, n) in {(96,96), (64,64), (32,96), (128,96), (64,96),
- * (48,32), (16,64)}, tanh / sigmoid).
+ * (48,32), (16,64)} -- BAR16_SHAPES of csrc/bar16_common.h is the source --, tanh / sigmoid).
  * A workgroup takes four chunks; a batch with more such workgroups than the device has CUs runs the eight-chunk plan of
  * csrc/gru_bar16d.hip instead (two four-chunk tiles through the same MFMAs), one with more eight-chunk workgroups than CUs
  * the sixteen-chunk plan of csrc/gru_bar16q.hip (four and eight chunks: bit-identical results; sixteen: to float32 rounding).

@@ -1,6 +1,7 @@
 // bar16_common.h -- helpers shared by the barrier-stepped Gru kernels (gru_bar16.hip: four chunks per workgroup,
-// gru_bar16d.hip: eight): barriers that wait for LDS the cheap way, the five-instruction tanh, 3-term split MFMA sequences and
-// the projection's MFMAs with weights named in accumulation registers.
+// gru_bar16d.hip: eight, gru_bar16q.hip: sixteen): barriers that wait for LDS the cheap way, the five-instruction tanh, 3-term split
+// MFMA sequences and the projection's MFMAs with weights named in accumulation registers; at the end the host side the three files
+// share: the table of shapes, the entry points they call across files and the launcher of the eight- and sixteen-chunk kernels.
 #pragma once
 #include <type_traits>
 
@@ -379,3 +380,35 @@ struct Bar16Pack {
     __host__ __device__ static constexpr size_t rec_inv(int w, int k) { return ((size_t)w * REC_ITEMS + 12 * KBS + k) * 64; }
     __host__ __device__ static constexpr size_t proj(int tile, int kb, int hl) { return PROJ0 + ((size_t)(tile * KBLK + kb) * 2 + hl) * 64; }
 };
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------------
+// THE (insize, n) the three kernels are instantiated for; every dispatcher expands this table (sloika_amd.layers.GRU_LAYER_SHAPES and
+// the comment of slk_gru_bar16_f32 in include/sloika_amd.h repeat it).  The order is the order of instantiation, and with it the layout of
+// the code object: add at the end.
+#define BAR16_SHAPES(X) X(96, 96) X(64, 64) X(32, 96) X(128, 96) X(64, 96) X(48, 32) X(16, 64)
+// ... and those with a packed four-chunk kernel (slk_gru_bar16_pack_bytes / _pack_f32 / _stack_f32)
+#define BAR16_PACKED_SHAPES(X) X(96, 96) X(64, 64)
+
+// The eight- and sixteen-chunk plans behind slk_gru_bar16_f32 (gru_bar16d.hip, gru_bar16q.hip; same contract): SLK_ERR_UNSUPPORTED when
+// no instantiation covers the request or y cannot take the kernel's state stores -- the caller then takes the next smaller plan.
+extern "C" int slk_gru_bar16d_launch(const float *x, long ldx, const float *iW, const float *sW, const float *sW2, const float *bias,
+                                     float *y, long ldy, int T, int B, int insize, int n, int reverse, const int32_t *lens,
+                                     float *zr_out, hipStream_t s);
+extern "C" int slk_gru_bar16q_launch(const float *x, long ldx, const float *iW, const float *sW, const float *sW2, const float *bias,
+                                     float *y, long ldy, int T, int B, int insize, int n, int reverse, const int32_t *lens,
+                                     float *zr_out, hipStream_t s);
+
+// One workgroup per CHUNKS chunks of the batch; K_SAVE / K_PLAIN: the kernel's instantiations that do / do not write the gates (zr_out).
+// The kernels are template arguments, not run-time pointers: whatever a launcher keeps per device (SLK_PER_DEVICE) it then keeps per kernel.
+template <int CHUNKS, auto K_SAVE, auto K_PLAIN>
+static int launch_bar16_chunks(const float *x, long ldx, const float *iW, const float *bias, const float *sW, const float *sW2,
+                               float *y, long ldy, int T, int B, int reverse, const int *lens, float *zr_out, hipStream_t s)
+{
+    if (zr_out)
+        hipLaunchKernelGGL(K_SAVE, dim3((B + CHUNKS - 1) / CHUNKS), dim3(256), 0, s, x, ldx, iW, bias, sW, sW2, y, ldy, T, B,
+                           reverse & 1, lens, zr_out);
+    else
+        hipLaunchKernelGGL(K_PLAIN, dim3((B + CHUNKS - 1) / CHUNKS), dim3(256), 0, s, x, ldx, iW, bias, sW, sW2, y, ldy, T, B,
+                           reverse & 1, lens, zr_out);
+    return slk_launch_status();
+}

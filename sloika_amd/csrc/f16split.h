@@ -1,5 +1,5 @@
 // f16split.h -- the pieces shared by the kernels that compute float32 products as three fp16 MFMA terms
-// (gru_fused16.hip, gru_bar16.hip): v = hi + lo with both halves fp16, x.w ~ hi.lo + lo.hi + hi.hi in float32
+// (gru_bar16*.hip through bar16_common.h, softmax_viterbi.hip): v = hi + lo with both halves fp16, x.w ~ hi.lo + lo.hi + hi.hi in float32
 // accumulators, operands scaled row-wise by powers of two so that any finite float32 value is in range.
 #pragma once
 #include "common.h"

@@ -1,10 +1,10 @@
 // gru_bar16.hip -- a whole Gru layer (sloika/layers.py:1010-1021) in one persistent kernel of FOUR waves per workgroup,
-// one per SIMD, in lock step: the same arithmetic as gru_fused16.hip (3-term fp16 split products, float32 accumulation,
-// rows scaled by powers of two) on a different execution plan.
+// one per SIMD, in lock step.  Arithmetic: every float32 product as fp16 split terms (f16split.h) with float32 accumulation,
+// rows scaled by powers of two.
 //
-// gru_fused16.hip runs eight waves coupled by progress counters in LDS; a step of its chain costs two counter round trips
-// (poll, ballot, retry), shares its SIMDs with the projection waves, and lives in 256 registers.  Measured there: of
-// ~2200 cycles per step only ~860 are the chain's MFMAs.  Here:
+// The plan this one replaced (tools/experiments/gru_fused16.hip, no longer in the library) ran eight waves coupled by progress
+// counters in LDS; a step of its chain cost two counter round trips (poll, ballot, retry), shared its SIMDs with the projection
+// waves, and lived in 256 registers.  Measured there: of ~2200 cycles per step only ~860 were the chain's MFMAs.  Here:
 //   * one wave per SIMD (256 threads, 512 registers each): nobody competes with the chain for issue slots;
 //   * the two exchanges of a step (r*h, then h) are two s_barrier -- LDS data written before the barrier is simply there
 //     after it, no counters, no retries;
@@ -19,7 +19,7 @@
 // 4c + j carries chunk c -- j = 0: its hi half, j = 2: its lo half; rows j = 1, 3 are not used and fetch the neighbouring chunk so
 // that a ds_read_b128 touches every bank once -- and a B column is a neuron of the tile, so lane (chunk c = lane >> 4, neuron
 // n = lane & 15) finds hi.W in register 0 and lo.W in register 2 of its accumulator: a gate's pre-activation is one v_add_f32
-// (bar16_common.h: pick_sum_kept).  The K order of the packed operand images is that of gru_fused16.hip.
+// (bar16_common.h: pick_sum_kept).  The K order of the packed operand images: bar16_rec_tile there.
 #include <limits.h>
 #include <stdlib.h>
 
@@ -224,17 +224,10 @@ static int launch_bar16(const float *x, long ldx, const float *iW, const float *
     return slk_launch_status();
 }
 
-extern "C" int slk_gru_bar16d_launch(const float *x, long ldx, const float *iW, const float *sW, const float *sW2, const float *bias,
-                                     float *y, long ldy, int T, int B, int insize, int n, int reverse, const int32_t *lens,
-                                     float *zr_out, hipStream_t s);
-
-extern "C" int slk_gru_bar16q_launch(const float *x, long ldx, const float *iW, const float *sW, const float *sW2, const float *bias,
-                                     float *y, long ldy, int T, int B, int insize, int n, int reverse, const int32_t *lens,
-                                     float *zr_out, hipStream_t s);
-
 // More workgroups of four chunks than CUs would run one after the other: such batches take the eight-chunk plan of
 // gru_bar16d.hip, and the sixteen-chunk plan of gru_bar16q.hip when the eight-chunk workgroups do not fit either (bits 8-9 of
-// `reverse` force a plan per call).  Returns chunks per workgroup divided by four.
+// `reverse` force a plan per call).  Returns chunks per workgroup divided by four.  This is plan 0 of the C ABI;
+// sloika_amd.layers.gru_launch restates it (its rule 3) and always passes an explicit plan.
 static int bar16_auto_plan(int B)
 {
     const int ncu = SLK_PER_DEVICE(int, ([] {
@@ -246,7 +239,7 @@ static int bar16_auto_plan(int B)
     return (B + 7) / 8 <= ncu ? 2 : 4;
 }
 
-// Same contract as slk_gru_fused16_f32 (include/sloika_amd.h); SLK_ERR_UNSUPPORTED when no instantiation covers the request.
+// The contract is in include/sloika_amd.h; SLK_ERR_UNSUPPORTED when no instantiation covers the request.
 extern "C" int slk_gru_bar16_f32(const float *x, long ldx, const float *iW, const float *sW, const float *sW2,
                                  const float *bias, float *y, long ldy, int T, int B, int insize, int n, int reverse, int act,
                                  int gate_act, const int32_t *lens, float *zr_out, slk_stream_t stream)
@@ -277,14 +270,12 @@ extern "C" int slk_gru_bar16_f32(const float *x, long ldx, const float *iW, cons
         }                                                                                                                          \
         return rc;                                                                                                                 \
     }
-    BAR16(96, 96) BAR16(64, 64) BAR16(32, 96) BAR16(128, 96) BAR16(64, 96) BAR16(48, 32) BAR16(16, 64)
+    BAR16_SHAPES(BAR16)
 #undef BAR16
     return SLK_ERR_UNSUPPORTED;
 }
 
-// ---- weights packed once per model, layers stacked in one launch (include/sloika_amd.h) ------------------------------------------------
-#define BAR16_PACKED_SHAPES(X) X(96, 96) X(64, 64)
-
+// ---- weights packed once per model, layers stacked in one launch (include/sloika_amd.h; shapes: BAR16_PACKED_SHAPES) ------------------
 extern "C" size_t slk_gru_bar16_pack_bytes(int insize, int n)
 {
 #define BAR16(II, NN) if (insize == II && n == NN) return Bar16Pack<II, NN>::BYTES;

@@ -28,15 +28,6 @@ typedef float f32x2d __attribute__((ext_vector_type(2)));
 constexpr bool BAR16D_HOOKS = false;
 // The recurrent products take two MFMAs each, the two copies of a chunk carrying the hi and the lo half of the state (bar16_common.h:
 // mfma2x2, pick_mix_d) -- the same arithmetic as gru_bar16.hip's, bit for bit.
-// vestigial: only the removed stamp build wrote this buffer; the diagnostic build's reader below now reads zeros
-__device__ unsigned long long slk_dbg_bar16d[4][16];
-#ifdef SLK_DIAG                          /* tools/build_diag_lib.sh */
-extern "C" SLK_API int slk_debug_read_bar16d(unsigned long long *host_out)
-{
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(slk_dbg_bar16d), sizeof(unsigned long long) * 64) == hipSuccess ? SLK_OK
-                                                                                                                 : SLK_ERR_LAUNCH;
-}
-#endif
 
 // first tile of interval k when a service wave has st tiles per group and set (k = 8: st); the leader splits x of set 0 in
 // intervals 1..KBLK and of set 1 in intervals 4.. (or 5..), so the load is even except for interval 0 (operand fetch)
@@ -667,28 +658,16 @@ __global__ void __launch_bounds__(256, 1) gru_bar16d_kernel(const float *__restr
     }
 }
 
-template <int I, int N>
-static int launch_bar16d(const float *x, long ldx, const float *iW, const float *bias, const float *sW, const float *sW2,
-                         float *y, long ldy, int T, int B, int reverse, const int *lens, float *zr_out, hipStream_t s)
-{
-    if (zr_out)
-        hipLaunchKernelGGL((gru_bar16d_kernel<I, N, true>), dim3((B + 7) / 8), dim3(256), 0, s, x, ldx, iW, bias, sW, sW2, y, ldy, T,
-                           B, reverse & 1, lens, zr_out);
-    else
-        hipLaunchKernelGGL((gru_bar16d_kernel<I, N, false>), dim3((B + 7) / 8), dim3(256), 0, s, x, ldx, iW, bias, sW, sW2, y, ldy, T,
-                           B, reverse & 1, lens, zr_out);
-    return slk_launch_status();
-}
-
-// The eight-chunk plan behind slk_gru_bar16_f32 (same contract); SLK_ERR_UNSUPPORTED when no instantiation covers the request
-// (the caller then takes the four-chunk kernel).
+// The eight-chunk plan behind slk_gru_bar16_f32 (bar16_common.h).
 extern "C" int slk_gru_bar16d_launch(const float *x, long ldx, const float *iW, const float *sW, const float *sW2, const float *bias, float *y,
                           long ldy, int T, int B, int insize, int n, int reverse, const int32_t *lens, float *zr_out, hipStream_t s)
 {
     if ((ldy & 1) || (reinterpret_cast<uintptr_t>(y) & 7)) return SLK_ERR_UNSUPPORTED;          // 8-byte state stores
-#define BAR16D(II, NN) \
-    if (insize == II && n == NN) return launch_bar16d<II, NN>(x, ldx, iW, bias, sW, sW2, y, ldy, T, B, reverse, lens, zr_out, s);
-    BAR16D(96, 96) BAR16D(64, 64) BAR16D(32, 96) BAR16D(128, 96) BAR16D(64, 96) BAR16D(48, 32) BAR16D(16, 64)
+#define BAR16D(II, NN)                                                                                                  \
+    if (insize == II && n == NN)                                                                                        \
+        return launch_bar16_chunks<8, gru_bar16d_kernel<II, NN, true>, gru_bar16d_kernel<II, NN, false>>(               \
+            x, ldx, iW, bias, sW, sW2, y, ldy, T, B, reverse, lens, zr_out, s);
+    BAR16_SHAPES(BAR16D)
 #undef BAR16D
     return SLK_ERR_UNSUPPORTED;
 }

@@ -12,7 +12,7 @@
 //   * the reset gate's AND the candidate's weights live in accumulation registers (asm MFMAs, bar16_common.h: both come in one run
 //     in front of their epilogue anyway); the update gate's stay in ordinary registers, its MFMAs are the compiler's to interleave
 //     with the reset gate's epilogue, all in interval A, and its own epilogue covers the LDS round trip of interval B.
-// Arithmetic per (neuron, chunk) is that of the other two plans, instruction for instruction: results are bit-identical.
+// The recurrent products here are three-term splits where the other two plans take two MFMAs: results agree with theirs to float32 rounding.
 #include <limits.h>
 #include <stdlib.h>
 
@@ -627,29 +627,17 @@ __global__ void __launch_bounds__(256, 1) gru_bar16q_kernel(const float *__restr
     }
 }
 
-template <int I, int N>
-static int launch_bar16q(const float *x, long ldx, const float *iW, const float *bias, const float *sW, const float *sW2,
-                         float *y, long ldy, int T, int B, int reverse, const int *lens, float *zr_out, hipStream_t s)
-{
-    if (zr_out)
-        hipLaunchKernelGGL((gru_bar16q_kernel<I, N, true>), dim3((B + 15) / 16), dim3(256), 0, s, x, ldx, iW, bias, sW, sW2, y, ldy, T,
-                           B, reverse & 1, lens, zr_out);
-    else
-        hipLaunchKernelGGL((gru_bar16q_kernel<I, N, false>), dim3((B + 15) / 16), dim3(256), 0, s, x, ldx, iW, bias, sW, sW2, y, ldy, T,
-                           B, reverse & 1, lens, zr_out);
-    return slk_launch_status();
-}
-
-// The sixteen-chunk plan behind slk_gru_bar16_f32 (same contract); SLK_ERR_UNSUPPORTED when no instantiation covers the request
-// (the caller then takes the eight- or four-chunk kernel).
+// The sixteen-chunk plan behind slk_gru_bar16_f32 (bar16_common.h).
 extern "C" int slk_gru_bar16q_launch(const float *x, long ldx, const float *iW, const float *sW, const float *sW2, const float *bias,
                                      float *y, long ldy, int T, int B, int insize, int n, int reverse, const int32_t *lens,
                                      float *zr_out, hipStream_t s)
 {
     if ((ldy & 3) || (reinterpret_cast<uintptr_t>(y) & 15)) return SLK_ERR_UNSUPPORTED;         // 16-byte state stores
-#define BAR16Q(II, NN) \
-    if (insize == II && n == NN) return launch_bar16q<II, NN>(x, ldx, iW, bias, sW, sW2, y, ldy, T, B, reverse, lens, zr_out, s);
-    BAR16Q(96, 96) BAR16Q(64, 64) BAR16Q(32, 96) BAR16Q(128, 96) BAR16Q(64, 96) BAR16Q(48, 32) BAR16Q(16, 64)
+#define BAR16Q(II, NN)                                                                                                  \
+    if (insize == II && n == NN)                                                                                        \
+        return launch_bar16_chunks<16, gru_bar16q_kernel<II, NN, true>, gru_bar16q_kernel<II, NN, false>>(              \
+            x, ldx, iW, bias, sW, sW2, y, ldy, T, B, reverse, lens, zr_out, s);
+    BAR16_SHAPES(BAR16Q)
 #undef BAR16Q
     return SLK_ERR_UNSUPPORTED;
 }

@@ -16,7 +16,7 @@ There is no CPU fallback: without the HIP library / a GPU, `run` raises.
 """
 import abc
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from functools import reduce
 
 import numpy as np
@@ -139,14 +139,15 @@ class _PlanHints(__import__("threading").local):
     """Execution-plan hints of the forward pass that is running ON THIS HOST THREAD (a Basecaller per thread may run with its
     own `in_flight`: two threads no longer race on a module global).  With `deterministic` set results never depend on them, only speed;
     without it the sixteen-chunk Gru plan may be chosen, whose states agree with the other plans' to float32 rounding only.
+    gru_launch reads all three.
 
-    gru_plan_bits  bits 8-9 of the `reverse` argument of slk_gru_bar16_f32 (0 = plan by batch size, 2 / 3 = eight / sixteen
-                   chunks per workgroup): set by Parallel while it runs the directions of a birnn side by side at a batch where
-                   only the eight-chunk plan lets them share the chip
+    gru_side       the GruLaunch Parallel chose for the sub-layers it is running side by side (None: none): set by Parallel while it
+                   runs the directions of a birnn at a batch where only eight chunks per workgroup, or two workgroups per CU, let
+                   them share the chip
     in_flight      batches the caller keeps in flight on streams of their own (pipeline.Basecaller(in_flight=N) sets it around
                    a forward pass): a recurrent layer then counts N times its workgroups when it decides whether they fit the
                    device's CUs together"""
-    gru_plan_bits = 0
+    gru_side = None
     in_flight = 1
     #: pipeline.Basecaller(deterministic=True), the default: never the sixteen-chunk Gru plan (csrc/gru_bar16q.hip), the only plan whose
     #: hidden states differ from the others' (three-term recurrent products where they take two: agreement to float32 rounding, up to 2 %
@@ -157,25 +158,67 @@ class _PlanHints(__import__("threading").local):
 _HINTS = _PlanHints()
 
 
+class GruLaunch(namedtuple("GruLaunch", "chunks share_cu")):
+    """How one call of the whole-layer Gru (slk_gru_bar16_f32) is launched: `chunks` = 4 / 8 / 16 per workgroup (csrc/gru_bar16.hip /
+    gru_bar16d.hip / gru_bar16q.hip); share_cu: two four-chunk workgroups of a layer up to 64 wide on a CU."""
+    __slots__ = ()
+
+    @property
+    def reverse_bits(self):
+        """Bits 8-10 of the `reverse` argument of slk_gru_bar16_f32 (include/sloika_amd.h)."""
+        return {4: 1, 8: 2, 16: 3}[self.chunks] | (4 if self.share_cu else 0)
+
+    @property
+    def two_term(self):
+        """Recurrent products as two fp16 MFMAs each (the sixteen-chunk kernel takes three): the roofline bookkeeping."""
+        return self.chunks <= 8
+
+    @property
+    def stackable(self):
+        """As slk_gru_bar16_stack_f32 launches its layers: four chunks per workgroup, a CU per workgroup."""
+        return self.chunks == 4 and not self.share_cu
+
+
 def _gru_plan_for(B, share, ncu, per_cu=1):
-    """Plan bits for `share` Gru launches of batch B that are meant to run at the same time: 0 when their four-chunk
-    workgroups fit the CUs together (or nothing helps), 2 when only the eight-chunk ones do, 3 when only the sixteen-chunk ones.
+    """The GruLaunch for `share` Gru launches of batch B that are meant to run at the same time, or None (= by batch size) when their
+    four-chunk workgroups fit the CUs together or nothing helps: eight chunks when only the eight-chunk workgroups fit, sixteen when
+    only the sixteen-chunk ones.
     per_cu = 2 for layers up to 64 wide: their eight- and sixteen-chunk kernels (csrc/gru_bar16d.hip, gru_bar16q.hip: < 256
     registers, < 80 KB of LDS) run two workgroups per CU, and two eight-chunk workgroups on a CU beat one of sixteen
     (baseline_raw_gru, eight batches of 256 in flight: 520 -> 545 M samples/s).  The four-chunk kernel keeps a CU to itself."""
     if ((B + 3) // 4) * share <= ncu:
-        return 0
+        return None
     # two four-chunk workgroups per CU where one per CU does not hold what is meant to run together (the directions of a birnn at
     # B = 1024: `baseline_gru` 16.9 -> 14.9 ms per step against the eight-chunk plan on half the chip each)
     if per_cu == 2 and ((B + 3) // 4) * share <= 2 * ncu:
-        return 5                   # four chunks per workgroup, two workgroups per CU (bit 2 = bit 10 of `reverse`: may share a CU)
+        return GruLaunch(4, True)
     if ((B + 7) // 8) * share <= ncu * per_cu:
-        return 2
-    return 3 if ((B + 15) // 16) * share <= ncu * per_cu else 0
+        return GruLaunch(8, False)
+    return GruLaunch(16, False) if ((B + 15) // 16) * share <= ncu * per_cu else None
+
+
+def gru_launch(B, ncu, narrow, side=None, in_flight=1, deterministic=False):
+    """THE launch plan of a whole-layer Gru call of batch B on `ncu` CUs (narrow: max(insize, size) <= 64); everything that needs to know
+    it -- the call itself, the roofline bookkeeping, the stacked launch, the trainer -- asks here.
+      1. the request: `side` (what Parallel chose for its sub-layers), else with batches in flight what lets them share the chip
+         (_gru_plan_for), else "by batch size";
+      2. deterministic: four and eight chunks per workgroup (and two four-chunk workgroups per CU) compute the same bits, sixteen do
+         not -- where sixteen would run (asked for, or by batch size with more eight-chunk workgroups than CUs) eight do, in as many
+         rounds as it takes;
+      3. by batch size: the fewest chunks per workgroup whose workgroups fit the CUs.  This restates bar16_auto_plan of
+         csrc/gru_bar16.hip (plan 0 of the C ABI) and is the only place in Python that does."""
+    want = side
+    if want is None and in_flight > 1:
+        want = _gru_plan_for(B, in_flight, ncu, 2 if narrow else 1)
+    if deterministic and (want.chunks == 16 if want is not None else (B + 7) // 8 > ncu):
+        want = GruLaunch(8, False)
+    if want is None:
+        want = GruLaunch(4 if (B + 3) // 4 <= ncu else 8 if (B + 7) // 8 <= ncu else 16, False)
+    return want
 
 
 #: (insize, size) of the Gru layers that run as ONE kernel, projection included (the instantiations of csrc/gru_bar16.hip,
-#: gru_bar16d.hip, gru_bar16q.hip: every Gru of models/ up to 96 wide)
+#: gru_bar16d.hip, gru_bar16q.hip: every Gru of models/ up to 96 wide).  The source is BAR16_SHAPES of csrc/bar16_common.h.
 GRU_LAYER_SHAPES = frozenset([(96, 96), (64, 64), (32, 96), (128, 96), (64, 96), (48, 32), (16, 64)])
 #: sizes of the fp16-split scan behind a projection GEMM (csrc/gru_scan1t.hip)
 GRU_SCAN16_SIZES = frozenset([112, 128, 144])
@@ -183,7 +226,7 @@ GRU_SCAN16_SIZES = frozenset([112, 128, 144])
 
 def gru_plan(insize, size, fun, gatefun):
     """THE plan table of a Gru layer: which kernels run it.  (How many chunks a workgroup of the "layer" plan takes is a matter
-    of batch size and batches in flight: _gru_plan_for.)
+    of batch size and batches in flight: gru_launch.)
 
       "layer"   one persistent kernel for the whole layer           slk_gru_bar16_f32
       "scan16"  projection GEMM + scan on the fp16 split             slk_gru_scan16_f32
@@ -993,22 +1036,10 @@ class Gru(RNN):
             params += [self.b]
         return params
 
-    def _plan_bits(self, x, B):
-        """Bits 8-9 of `reverse` for slk_gru_bar16_f32: what Parallel decided for its side-by-side sub-layers, else eight chunks
-        per workgroup when that is what lets the batches in flight share the chip."""
-        import torch
-        ncu = _cu_count(x.device)
-        if _HINTS.gru_plan_bits or _HINTS.in_flight <= 1:
-            bits = _HINTS.gru_plan_bits
-        else:
-            bits = _gru_plan_for(B, _HINTS.in_flight, ncu, 2 if max(self.size, self.insize) <= 64 else 1)
-        if _HINTS.deterministic:
-            # one set of bits per chunk whatever the plan: four and eight chunks per workgroup (and two four-chunk workgroups per CU) compute
-            # the same bits, sixteen do not -- where that plan would be chosen (here, or by bar16_auto_plan in the library for a batch
-            # whose eight-chunk workgroups outnumber the CUs) the eight-chunk one runs, in as many rounds as it takes
-            if (bits & 3) == 3 or (bits == 0 and (B + 7) // 8 > ncu):
-                bits = 2
-        return bits
+    def _launch(self, x, B):
+        """The GruLaunch of this layer on x under this host thread's hints."""
+        return gru_launch(B, _cu_count(x.device), max(self.size, self.insize) <= 64, _HINTS.gru_side, _HINTS.in_flight,
+                          _HINTS.deterministic)
 
     def _padded(self, shape=None):
         """Zero-padded copy of this layer with `shape` = (insize, size) (default: both rounded up to multiples of 16, what the MFMA
@@ -1099,16 +1130,16 @@ class Gru(RNN):
         if plan == "layer":
             # projection AND recurrence in one persistent kernel (csrc/gru_bar16.hip; eight / sixteen chunks per workgroup:
             # gru_bar16d.hip / gru_bar16q.hip).  Roofline bookkeeping: up to eight chunks per workgroup the recurrent products
-            # take two MFMAs each, the projection three; the sixteen-chunk plan three everywhere (bar16_auto_plan)
-            bits = self._plan_bits(x, B)
-            ncu = _cu_count(x.device)
-            two_term = bits in (1, 2, 5) or (bits == 0 and (B + 7) // 8 <= ncu)
+            # take two MFMAs each, the projection three; the sixteen-chunk plan three everywhere
+            launch = self._launch(x, B)
+            two_term = launch.two_term
             with profiler.region("gru_fused", 6.0 * rows * n * (n + self.insize), 4.0 * rows * (self.insize + n),
                                  f16x3_flops=6.0 * rows * n * (self.insize if two_term else n + self.insize),
                                  f16x2_flops=6.0 * rows * n * n if two_term else 0.0) as reg:
                 rc = L.slk_gru_bar16_f32(x.data_ptr(), _row_stride(x), self.iW.dev().data_ptr(), self.sW.dev().data_ptr(),
                                          self.sW2.dev().data_ptr(), self.b.dev().data_ptr(), y.data_ptr(), _row_stride(y), T, B,
-                                         self.insize, n, int(reverse) | (bits << 8), act, gact, lens_p, None, _stream())
+                                         self.insize, n, int(reverse) | (launch.reverse_bits << 8), act, gact, lens_p, None,
+                                         _stream())
                 if rc == _lib.SLK_ERR_UNSUPPORTED and reg is not None:
                     reg.cancel()
             if rc != _lib.SLK_ERR_UNSUPPORTED:                 # (unsupported: rows of x that are not 16-byte aligned)
@@ -1221,9 +1252,9 @@ class Parallel(Layer):
         if all(_keeps_time(layer) for layer in self.layers):
             # every sub-layer writes its slice of the concatenated tensor directly (row stride = self.size)
             outs = out if out is not None else _scratch((T, B, self.size), torch.float32, x.device)
-            streams = self._side_streams(x, B)
+            side_by_side = self._side_streams(x, B)
             off = 0
-            if streams is None:
+            if side_by_side is None:
                 for layer in self.layers:
                     layer._forward(x, outs[:, :, off:off + layer.size], reverse)
                     off += layer.size
@@ -1232,11 +1263,12 @@ class Parallel(Layer):
             # workgroup per 4 chunks for the whole scan, so at small batches most CUs idle: run the directions of a
             # birnn side by side on their own HIP streams (the reference runs them one after the other inside one
             # Theano function, layers.py:1486-1487).
+            streams, side = side_by_side
             main = torch.cuda.current_stream(x.device)
             ready = torch.cuda.Event()
             ready.record(main)
-            keep = _HINTS.gru_plan_bits
-            _HINTS.gru_plan_bits = self._side_plan
+            keep = _HINTS.gru_side
+            _HINTS.gru_side = side
             try:
                 for i, layer in enumerate(self.layers):
                     st = main if i == 0 else streams[i - 1]
@@ -1250,7 +1282,7 @@ class Parallel(Layer):
                         main.wait_event(done)
                     off += layer.size
             finally:
-                _HINTS.gru_plan_bits = keep
+                _HINTS.gru_side = keep
             return outs
         cat = torch.cat([layer._forward(x, None, reverse) for layer in self.layers], dim=2)
         if out is not None:
@@ -1260,37 +1292,39 @@ class Parallel(Layer):
 
     _streams_cache = {}
 
-    def _side_streams(self, x, B):
-        """HIP streams for sub-layers 1.. when running them concurrently pays: all sub-layers recurrent and their
-        workgroups (one per 4 chunks each) fit the device's CUs together."""
-        import torch
+    def _side_launch(self, B, ncu):
+        """(do the sub-layers run side by side?, the GruLaunch they take then -- None: by batch size).  Side by side pays when all
+        sub-layers are recurrent and their workgroups (one per 4 chunks each) fit the device's CUs together.  Decides; stores nothing."""
         if len(self.layers) < 2:
-            return None
-        for layer in self.layers:
-            inner = layer.layer if isinstance(layer, Reverse) else layer
-            if not isinstance(inner, (Gru, Lstm)):
-                return None
-        ncu = _cu_count(x.device)
-        self._side_plan = 0
-        share = len(self.layers) * max(1, _HINTS.in_flight)
+            return False, None
         inners = [l.layer if isinstance(l, Reverse) else l for l in self.layers]
+        if not all(isinstance(l, (Gru, Lstm)) for l in inners):
+            return False, None
+        share = len(self.layers) * max(1, _HINTS.in_flight)
         if all(isinstance(l, Lstm) and l.takes_fused_kernel() for l in inners):
             ncu *= 2                   # csrc/lstm_fused16.hip fits two workgroups on a CU: the directions fill each other's waits
-        if ((B + 3) // 4) * share > ncu:
-            # too many four-chunk workgroups to run together; eight chunks per workgroup (csrc/gru_bar16d.hip: 1.4 x the step
-            # time for twice the chunks) may still let the directions share the chip: B = 1024, two directions -> 2 x 128
-            grus = all(isinstance(l.layer if isinstance(l, Reverse) else l, Gru) for l in self.layers)
-            plan = _gru_plan_for(B, share, ncu, 2 if grus and all(max(l.size, l.insize) <= 64 for l in inners) else 1)
-            if not (grus and SPLIT_F16 and plan):
-                return None
-            self._side_plan = plan
+        if ((B + 3) // 4) * share <= ncu:
+            return True, None
+        # too many four-chunk workgroups to run together; eight chunks per workgroup (csrc/gru_bar16d.hip: 1.4 x the step
+        # time for twice the chunks) may still let the directions share the chip: B = 1024, two directions -> 2 x 128
+        if not (SPLIT_F16 and all(isinstance(l, Gru) for l in inners)):
+            return False, None
+        side = _gru_plan_for(B, share, ncu, 2 if all(max(l.size, l.insize) <= 64 for l in inners) else 1)
+        return side is not None, side
+
+    def _side_streams(self, x, B):
+        """(HIP streams for sub-layers 1.., the GruLaunch of _side_launch) when running the sub-layers concurrently pays, else None."""
+        import torch
+        together, side = self._side_launch(B, _cu_count(x.device))
+        if not together:
+            return None
         # side streams belong to the stream the caller runs on: batches in flight on different streams must not meet on one
         key = (x.device.index, len(self.layers), torch.cuda.current_stream(x.device).cuda_stream)
         if key not in Parallel._streams_cache:
             if len(Parallel._streams_cache) >= 64:                 # callers that keep creating streams: do not keep theirs for ever
                 Parallel._streams_cache.clear()
             Parallel._streams_cache[key] = [torch.cuda.Stream(device=x.device) for _ in range(len(self.layers) - 1)]
-        return Parallel._streams_cache[key]
+        return Parallel._streams_cache[key], side
 
     def spec(self):
         return {"type": "parallel", "sublayers": [l.spec() for l in self.layers]}
@@ -1361,8 +1395,7 @@ def _gru_stack_ok(grus, x):
             return False
     if _lib.lib().slk_gru_bar16_pack_bytes(I, n) == 0:
         return False
-    bits = g0._plan_bits(x, B)
-    if not (bits == 1 or (bits == 0 and (B + 3) // 4 <= _cu_count(x.device))):
+    if not g0._launch(x, B).stackable:
         return False
     return (x.dtype == torch.float32 and x.stride(2) == 1 and x.stride(0) == B * x.stride(1) and x.stride(1) % 4 == 0
             and x.data_ptr() % 16 == 0)

@@ -199,7 +199,7 @@ def stack_case(n, nlayer):
 PLANS = {1: ("gru_bar16_body.h", 4), 2: ("gru_bar16d.hip", 8), 3: ("gru_bar16q.hip", 16)}
 KERNEL = {1: "four", 2: "eight", 3: "sixteen"}
 #: Time edges, B = 17 (every plan: full workgroups and a last one with one live chunk).  The four- and eight-chunk kernels project
-#: in groups of GS = 4 steps into a ring of R = 8 (gru_bar16_body.h:18-19, gru_bar16d.hip:66-67), the sixteen-chunk kernel has
+#: in groups of GS = 4 steps into a ring of R = 8 (gru_bar16_body.h:18-19, gru_bar16d.hip:57-58), the sixteen-chunk kernel has
 #: GS = 2, R = 4 (gru_bar16q.hip:46-47); x is requested three groups ahead (load_x(G + 3), gru_bar16_body.h:631).  1 .. 9 holds every
 #: T % 4 and every T % 2, both sides of the first ring turnover (8 | 9; 4 | 5 for sixteen chunks); 12 | 13 the first prefetch that would
 #: pass the end; 16 | 17 the second turnover.

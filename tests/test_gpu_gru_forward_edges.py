@@ -11,7 +11,7 @@ How every launch is set up unless a test says otherwise: outputs start as a NaN 
 and behind y and zr; x rows are ldx = I + 4 apart with NaN in the gaps; every x row at t >= lens[b] is NaN (the layers hand the
 kernels uninitialised rows there: a kernel that reads one of them into a product loses the chunk); after the call the guards, the gaps
 and every output row past a chunk's end hold the bits they held before, and x is unchanged.  Every test first asserts that the ring of
-its plan is two projection groups as the kernel source declares them (gru_bar16_body.h:18-19, gru_bar16d.hip:66-67: GS = 4, R = 2 * GS;
+its plan is two projection groups as the kernel source declares them (gru_bar16_body.h:18-19, gru_bar16d.hip:57-58: GS = 4, R = 2 * GS;
 gru_bar16q.hip:46-47: GS = 2, R = 2 * GS): the lengths of rg.EDGE_T are laid around those, and a kernel change that moves the edges
 must fail here first (the table itself is tied to them in tests/test_ref_gru_forward.py).
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Registers, spills and LDS of every kernel in one .hip file:  tools/kernel_resources.sh sloika_amd/csrc/gru_fused16.hip
+# Registers, spills and LDS of every kernel in one .hip file:  tools/kernel_resources.sh sloika_amd/csrc/gru_bar16.hip
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-fast-math -ffp-contract=off \
   -Rpass-analysis=kernel-resource-usage -c "$1" -o /dev/null 2>&1 | python3 -c '
 import sys, re
