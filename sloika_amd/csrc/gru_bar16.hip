@@ -30,7 +30,8 @@
 // Diagnostics (per-section shader-clock stamps, ablation launches, workgroup clocks) exist only in builds with -DSLK_DIAG
 // (tools/build_diag_lib.sh; readers: tools/bar16_check.py, tools/bar16_wg_times.py).  ABL bits (results are then garbage):
 // 1 = no s_barrier, 2 = chain waves issue no MFMAs, 4 = cheap activations, 8 = service waves only keep the barriers,
-// 16 = no stores to h_out, 32 = every workgroup records where it ran and for how long.
+// 16 = no stores to h_out, 32 = every workgroup records where it ran and for how long, 64 = chain waves issue no z MFMAs and no z
+// epilogue, the blend takes constants (the bound of what moving the update gate off the chain can gain: design/gru_zgate.md).
 #ifdef SLK_DIAG
 __device__ unsigned long long slk_dbg_bar16[4][16];
 extern "C" SLK_API int slk_debug_read_bar16(unsigned long long *host_out)
@@ -201,6 +202,7 @@ static int launch_bar16(const float *x, long ldx, const float *iW, const float *
         DIAG_LAUNCH(1, true, 0) DIAG_LAUNCH(2, false, 1) DIAG_LAUNCH(3, false, 2) DIAG_LAUNCH(4, false, 4) DIAG_LAUNCH(5, false, 8)
         DIAG_LAUNCH(6, false, 16) DIAG_LAUNCH(7, false, 9) DIAG_LAUNCH(8, false, 3) DIAG_LAUNCH(9, false, 11) DIAG_LAUNCH(10, false, 31)
         DIAG_LAUNCH(11, false, 32) DIAG_LAUNCH(12, false, 34) DIAG_LAUNCH(13, false, 40) DIAG_LAUNCH(14, false, 42) DIAG_LAUNCH(15, false, 36)
+        DIAG_LAUNCH(16, false, 64) DIAG_LAUNCH(17, true, 64)
 #undef DIAG_LAUNCH
     }
 #endif

@@ -250,10 +250,10 @@
         // the issuing wave for 4):
         //   A  [others' h(s-1) visible]  request the other K blocks, then vI(s); r products with my own block (already in
         //      registers) and this step's share of the projection while they fly; r products with the others, tile 0 first;
-        //      z products (all but the last block) under sigmoid(r), r*h, split, write, own block read back
+        //      sigmoid(r), r*h, split, write, own block read back; ALL z products somewhere in this interval (NB_S, NB_E below)
         //   B  [others' r*h visible]     request the other K blocks, then the x operands of the next step's share of the
-        //      projection; last z block and candidate products with my own block while they fly; candidate products with
-        //      the others (tile 0 first), sigmoid(z) in their shadow; tanh, blend, split, write, own block read back, store
+        //      projection; candidate products with my own block, then sigmoid(z), 1 - z and z*h while they fly; candidate
+        //      products with the others (tile 0 first); tanh, blend, split, write, own block read back, store
         // The gate arithmetic reads the accumulators from inline asm (pick_sum_kept), where hipcc inserts no wait states, and the
         // hardware does not interlock a vector read of an MFMA result: seven wait states must lie between a
         // v_mfma_f32_16x16x32_f16 and the read (tools/probes/mfma_read_hazard_probe.hip).  Every tile's last MFMA is therefore
@@ -270,6 +270,15 @@
         // wait states in front of tile 0's pick when 2 (KBS - 1) MFMAs of tile 1 (at least two: its own block) follow tile 0's last
         constexpr int WS0 = KBS > 1 ? (8 - 2 * (KBS - 1) > 1 ? 8 - 2 * (KBS - 1) : 1) : 6;
         constexpr int WS1 = (8 - WS0 - 1) > 1 ? (8 - WS0 - 1) : 1;         // ... of tile 1's, behind tile 0's pick (WS0 + one read)
+        // Where a step issues the z products (design/gru_zgate.md; every placement gives each accumulator the same MFMAs in the same
+        // order, own block first).  All of them lie in interval A, so that sigmoid(z) can be formed in interval B while the other
+        // blocks of r*h are on their way from LDS, not between the candidate's MFMAs and its pick:
+        //   blocks 0 .. NB_S-1     in the LDS round trip at the start of A (the own block is in registers);
+        //   blocks NB_S .. NB_E-1  under the r epilogue, one MFMA to three vector instructions;
+        //   blocks NB_E .. KBS-1   behind the write of r*h, where the wave only waits for its writes and for barrier B.
+        // Three K blocks: own block at the start, the others under the epilogue -- twelve MFMAs behind the write keep the matrix pipe
+        // busy past barrier B.  Two K blocks (the 64-wide layers): all eight behind the write; the measured best of five placements each.
+        constexpr int NB_S = KBS == 2 ? 0 : 1, NB_E = KBS == 2 ? 0 : KBS;
         auto step = [&](auto PHC, const int s, const int G) {
             constexpr int ph = decltype(PHC)::value;
             constexpr bool PROJ = CT > 0 && ph < KBLK;
@@ -301,7 +310,7 @@
                 vc[p] = vcur[64 * (2 * NT + 2 * w + p)];
             }
             __builtin_amdgcn_sched_barrier(0);
-            f32x4 accR[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, accZ[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+            f32x4 accR[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
             mfma2(wr_hi[0][0], wr_lo[0][0], bh[0], accR[0]);
             mfma2(wr_hi[1][0], wr_lo[1][0], bh[0], accR[1]);
             if constexpr (PROJ) {                        // my tile of the projection, K block ph: inside the LDS round trip
@@ -317,6 +326,14 @@
                     proj_out(w * CT + t, pacc[t], G + 1);
                 }
             }
+            f32x4 accZ[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+            if constexpr (!(ABL & 64)) {
+#pragma unroll
+                for (int i = 0; i < NB_S; i++) {
+                    mfma2(wz_hi[0][i], wz_lo[0][i], bh[i], accZ[0]);
+                    mfma2(wz_hi[1][i], wz_lo[1][i], bh[i], accZ[1]);
+                }
+            }
             __builtin_amdgcn_sched_barrier(0);
             BSTAMP(1)
 #pragma unroll
@@ -329,13 +346,15 @@
 #pragma unroll
             for (int i = 1; i < KBS; i++) mfma2(wr_hi[1][i], wr_lo[1][i], bh[i], accR[1]);
             asm volatile("" : "+v"(accR[1]));
-            asm volatile("" : "+v"(accZ[0]), "+v"(accZ[1]));                 // the z products: behind the r products
+            if constexpr (NB_E > NB_S && !(ABL & 64)) asm volatile("" : "+v"(accZ[0]), "+v"(accZ[1]));   // the z products: behind the r products
             __builtin_amdgcn_sched_barrier(0);
             BSTAMP(2)
+            if constexpr (!(ABL & 64)) {
 #pragma unroll
-            for (int i = 0; i < KBS - 1; i++) {
-                mfma2(wz_hi[0][i], wz_lo[0][i], bh[i], accZ[0]);
-                mfma2(wz_hi[1][i], wz_lo[1][i], bh[i], accZ[1]);
+                for (int i = NB_S; i < NB_E; i++) {
+                    mfma2(wz_hi[0][i], wz_lo[0][i], bh[i], accZ[0]);
+                    mfma2(wz_hi[1][i], wz_lo[1][i], bh[i], accZ[1]);
+                }
             }
             float rr[2];
             pick_sum_kept<WS0>(accR[0], pk0, accR[1][0]);                     // behind tile 1's MFMAs
@@ -354,9 +373,21 @@
             lds_fence();
             // one MFMA, then up to three VALU instructions, for as long as both last
 #pragma unroll
-            for (int i = 0; i < 4 * (KBS - 1); i++) {
+            for (int i = 0; i < 4 * (NB_E - NB_S); i++) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            // the z products behind the write: the operand statement keeps them there (volatile statements keep their order, the MFMAs
+            // need its result), the accumulator statement in front of the barrier
+            if constexpr (!(ABL & 64) && KBS > NB_E) {
+                asm volatile("" : "+v"(bh[NB_E]));
+#pragma unroll
+                for (int i = NB_E; i < KBS; i++) {
+                    mfma2(wz_hi[0][i], wz_lo[0][i], bh[i], accZ[0]);
+                    mfma2(wz_hi[1][i], wz_lo[1][i], bh[i], accZ[1]);
+                }
+                asm volatile("" : "+v"(accZ[0]), "+v"(accZ[1]));
             }
             const bool store = live && s < Tc && !(ABL & 16);
             // ------------------------------ interval B ------------------------------
@@ -377,14 +408,31 @@
                 pxl = ldH(xop_lo, ob);
             }
             __builtin_amdgcn_sched_barrier(0);
-            mfma2(wz_hi[0][KBS - 1], wz_lo[0][KBS - 1], bh[KBS - 1], accZ[0]);
-            mfma2(wz_hi[1][KBS - 1], wz_lo[1][KBS - 1], bh[KBS - 1], accZ[1]);
             f32x4 accC[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
             mfma2(wc_hi[0][0], wc_lo[0][0], ch[0], accC[0]);
             mfma2(wc_hi[1][0], wc_lo[1][0], ch[0], accC[1]);
-            // everything below -- sigmoid(z) and the other blocks' candidate products -- behind these eight MFMAs
-            asm volatile("" : "+v"(accZ[0]), "+v"(accZ[1]), "+v"(accC[0]), "+v"(accC[1]));
+            // everything below -- sigmoid(z) and the other blocks' candidate products -- behind these four MFMAs
+            asm volatile("" : "+v"(accC[0]), "+v"(accC[1]));
             __builtin_amdgcn_sched_barrier(0);
+            float zz[2], omz[2], zh[2];
+            if constexpr (ABL & 64) {                                         // no update gate: the blend takes constants
+                zz[0] = zz[1] = omz[0] = omz[1] = 0.5f;
+                zh[0] = zh[1] = 0.25f;
+            } else {
+                // sigmoid(z) while the other blocks of r*h are on their way from LDS.  `after` keeps the picks behind the candidate's four
+                // own-block MFMAs, and those behind barrier B.  The z MFMAs behind the write are pinned in front of the barrier; the
+                // last ones under the r epilogue may trail past it (nothing pins a builtin MFMA), and then still have two LDS reads
+                // and the four MFMAs between them and the pick -- and hipcc, which placed them and sees the accumulator among the
+                // operands of the pick's asm, pads what it finds missing (tests/test_isa_hygiene.py scans the outcome).
+                pick_sum_kept<1>(accZ[0], pk0, accC[1][0]);
+                pick_sum_kept<1>(accZ[1], pk1, accC[1][0]);
+                zz[0] = (ABL & 4) ? fmaf(pk0, inv_z[0], vz[0]) * 0.01f : sigmoid4(fmaf(pk0, inv_z[0], vz[0]));
+                zz[1] = (ABL & 4) ? fmaf(pk1, inv_z[1], vz[1]) * 0.01f : sigmoid4(fmaf(pk1, inv_z[1], vz[1]));
+#pragma unroll
+                for (int p = 0; p < 2; p++) { omz[p] = 1.0f - zz[p]; zh[p] = zz[p] * hold[p]; }
+                asm volatile("" : "+v"(zh[0]), "+v"(omz[0]), "+v"(zh[1]), "+v"(omz[1]), "+v"(pk0), "+v"(pk1));
+                __builtin_amdgcn_sched_barrier(0);
+            }
             BSTAMP(5)
 #pragma unroll
             for (int i = 1; i < KBS; i++) mfma2(wc_hi[0][i], wc_lo[0][i], ch[i], accC[0]);
@@ -393,23 +441,6 @@
 #pragma unroll
             for (int i = 1; i < KBS; i++) mfma2(wc_hi[1][i], wc_lo[1][i], ch[i], accC[1]);
             asm volatile("" : "+v"(accC[1]));
-            // sigmoid(z): its last MFMAs were issued in front of the candidate's own-block products (four MFMAs ago at least: the four
-            // wait states of these picks count from those, not from each other, so they are what they were with pick_mix)
-            float zz[2], omz[2], zh[2];
-#pragma unroll
-            for (int p = 0; p < 2; p++) {
-                float &pz = p ? pk1 : pk0;
-                pick_sum_kept<4>(accZ[p], pz, accZ[1][0]);
-                zz[p] = (ABL & 4) ? fmaf(pz, inv_z[p], vz[p]) * 0.01f : sigmoid4(fmaf(pz, inv_z[p], vz[p]));
-                omz[p] = 1.0f - zz[p];
-                zh[p] = zz[p] * hold[p];
-                asm volatile("" : "+v"(zh[p]), "+v"(omz[p]));                 // pinned here: not sunk to the blend below
-            }
-#pragma unroll
-            for (int i = 0; i < 4 * (KBS - 1); i++) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
-            }
             __builtin_amdgcn_sched_barrier(0);
             BSTAMP(6)
             float hn[2];

@@ -48,23 +48,25 @@ for I, n in shapes:
     base = timeit_code(0)
     print("ablations (results garbage), cycles/step at 2.4 GHz; production %.0f" % (base * 1e6 / T * 2.4))
     for code, nm in ((2, "no s_barrier"), (3, "chain: no MFMAs"), (4, "cheap activations"), (5, "service waves idle"), (6, "no h_out stores"),
-                     (7, "no s_barrier + service idle"), (8, "no s_barrier + no chain MFMAs"), (9, "no barrier, no chain MFMAs, service idle"), (10, "everything off")):
+                     (7, "no s_barrier + service idle"), (8, "no s_barrier + no chain MFMAs"), (9, "no barrier, no chain MFMAs, service idle"), (10, "everything off"),
+                     (16, "chain: no z products, no z epilogue")):
         ms = timeit_code(code)
         print("   %-44s %6.0f" % (nm, ms * 1e6 / T * 2.4))
-    import ctypes
     L.slk_debug_read_bar16.argtypes = [ctypes.c_void_p]
-    L.slk_gru_bar16_f32(x.data_ptr(), I, iW.data_ptr(), sW.data_ptr(), sW2.data_ptr(), bb.data_ptr(), y.data_ptr(), n, T, B, I, n, 2, 1, 2, None, None, st)
-    torch.cuda.synchronize()
-    stp = (ctypes.c_ulonglong * 64)()
-    L.slk_debug_read_bar16(stp)
-    names = ["barrier A", "reads + projection MFMAs + wait h", "r MFMAs", "z MFMAs + r epilogue + write", "barrier B", "reads + last z block + wait r*h",
-             "c MFMAs + z epilogue", "tanh, blend, split, writes, stores"]
-    for wv in range(4):
-        v = [stp[wv * 16 + i] / T for i in range(16)]
-        if wv < n // 32:
-            print("chain wave %d: cycles per step, total %.0f" % (wv, sum(v[:8])))
-            for i, nm in enumerate(names):
-                print("   %-44s %7.0f" % (nm, v[i]))
-        else:
-            print("service wave %d: cycles per GROUP: work per interval %s   barrier wait per interval %s" % (
-                wv, " ".join("%5.0f" % (4 * a) for a in v[:8]), " ".join("%5.0f" % (4 * a) for a in v[8:])))
+    names = ["barrier A", "reads + projection MFMAs + own z block + wait h", "r MFMAs", "z MFMAs + r epilogue + write", "barrier B",
+             "reads + own c block + z epilogue + wait r*h", "c MFMAs", "tanh, blend, split, writes, stores"]
+    for code, what in ((1, "production"), (17, "no z products, no z epilogue (results garbage)")):
+        L.slk_gru_bar16_f32(x.data_ptr(), I, iW.data_ptr(), sW.data_ptr(), sW2.data_ptr(), bb.data_ptr(), y.data_ptr(), n, T, B, I, n, 2 * code, 1, 2, None, None, st)
+        torch.cuda.synchronize()
+        stp = (ctypes.c_ulonglong * 64)()
+        L.slk_debug_read_bar16(stp)
+        print("stamps: %s" % what)
+        for wv in range(4):
+            v = [stp[wv * 16 + i] / T for i in range(16)]
+            if wv < n // 32:
+                print("chain wave %d: cycles per step, total %.0f" % (wv, sum(v[:8])))
+                for i, nm in enumerate(names):
+                    print("   %-48s %7.0f" % (nm, v[i]))
+            else:
+                print("service wave %d: cycles per GROUP: work per interval %s   barrier wait per interval %s" % (
+                    wv, " ".join("%5.0f" % (4 * a) for a in v[:8]), " ".join("%5.0f" % (4 * a) for a in v[8:])))

@@ -1,5 +1,5 @@
 """A/B of two library builds on ONE device, one process: per-launch time of slk_gru_bar16_f32 (whole Gru layer, T' = 800) for the
-four- / eight- / sixteen-chunk plans, interleaved rounds (three untimed, nine timed; each build's rounds and their spread are printed:
+four- / eight- / sixteen-chunk plans, interleaved rounds (five untimed, nine timed; each build's rounds and their spread are printed:
 a difference between the builds counts from three times the spread of the first build's own rounds), and the largest difference
 between the two builds' results.
     python tools/gru_ab.py tools/_build/libref_<rev>.so [sloika_amd/_build/libsloika_amd.so] [IxN ...]"""
@@ -47,7 +47,7 @@ def main():
             torch.cuda.synchronize()
             diff = (ys[0] - ys[1]).abs().max().item()
             res = [[] for _ in libs]
-            for rnd in range(-3, 9):                    # three untimed rounds first: the clock settles over the first ~50 launches
+            for rnd in range(-5, 9):                    # five untimed rounds first: the clock settles over the first ~50 launches (three were too few)
                 for k in range(len(libs)):
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record()
