@@ -9,8 +9,9 @@
 //   * the two exchanges of a step (r*h, then h) are two s_barrier -- LDS data written before the barrier is simply there
 //     after it, no counters, no retries;
 //   * the time-parallel projection vI = x.iW^T + b (four steps at a time) is cut into pieces that the waves execute at
-//     fixed places of the step: a chain wave issues its share (CT tiles, one K block per step) right after a barrier,
-//     while its LDS reads of the state are in flight; the service waves (the SIMDs without a chain wave) take the rest,
+//     fixed places of the step: a chain wave issues its share (CT tiles, one K block per step) behind its write of r*h,
+//     under that write's latency (four K blocks of input: right after a barrier, while its LDS reads of the state are in
+//     flight); the service waves (the SIMDs without a chain wave) take the rest,
 //     split x into fp16 halves ONCE per group for everybody (operand images in LDS), and run the x DMA one request at a
 //     time so that they always reach the next barrier before the chain does;
 //   * every chain lane owns (neuron, chunk) pairs and stores its new state straight to h_out (sixteen lanes write 64
@@ -31,7 +32,11 @@
 // (tools/build_diag_lib.sh; readers: tools/bar16_check.py, tools/bar16_wg_times.py).  ABL bits (results are then garbage):
 // 1 = no s_barrier, 2 = chain waves issue no MFMAs, 4 = cheap activations, 8 = service waves only keep the barriers,
 // 16 = no stores to h_out, 32 = every workgroup records where it ran and for how long, 64 = chain waves issue no z MFMAs and no z
-// epilogue, the blend takes constants (the bound of what moving the update gate off the chain can gain: design/gru_zgate.md).
+// epilogue, the blend takes constants (the bound of what moving the update gate off the chain can gain: design/gru_zgate.md),
+// 128 = chain waves without their share of the projection (no projection MFMAs, no outputs, no reads of the x operands: the bound of
+// what moving it to the service wave can gain), 256 / 512 = the service wave computes six / three of its tiles a second time, spread
+// over the intervals as a table for eighteen / fifteen tiles would spread them (whether it still reaches every barrier first:
+// design/gru_projection.md).
 #ifdef SLK_DIAG
 __device__ unsigned long long slk_dbg_bar16[4][16];
 extern "C" SLK_API int slk_debug_read_bar16(unsigned long long *host_out)
@@ -59,14 +64,27 @@ extern "C" SLK_API int slk_debug_read_bar16_wg(unsigned long long *host_out)
 #endif
 
 // first tile of interval k when a service wave has st tiles per group (k = 8: st)
-__host__ __device__ constexpr int tile_first(int st, int k)
+// table 0: lighter where the leader also splits x (intervals 1..4) and fetches operands (0).
+// table 1, a single service wave behind chain waves that project behind their write of r*h (gru_bar16_body.h: LATE): by the stamps
+// of table 0 (design/gru_projection.md) the wave reached the barrier behind interval 1 -- a tile and the scale of the coming
+// group's rows, in the shorter half of the step -- last of the four, and the one behind interval 4 -- two tiles, a K block of the
+// split, the loads of x -- 50 cycles ahead of the chain.  Interval 1 keeps no tile, interval 4 one; 0 and 2, in the longer half, two.
+__host__ __device__ constexpr int tile_first(int st, int k, int table = 0)
 {
-    // share per interval: lighter where the leader also splits x (intervals 1..4) and fetches operands (0)
-    constexpr int w[8] = {1, 1, 1, 1, 2, 2, 2, 2};
+    constexpr int w0[8] = {1, 1, 1, 1, 2, 2, 2, 2}, w1[8] = {2, 0, 2, 1, 1, 2, 2, 2};
+    const int *const w = table == 1 ? w1 : w0;
     int tot = 0, acc = 0;
     for (int i = 0; i < 8; i++) tot += w[i];
     for (int i = 0; i < k && i < 8; i++) acc += w[i];
     return k >= 8 ? st : (acc * st + tot / 2) / tot < st ? (acc * st + tot / 2) / tot : st;
+}
+
+// ABL bits 256 / 512: tiles an interval of the service wave computes a second time, on top of whatever table it has -- measured on
+// table 0 (design/gru_projection.md 1), where they made {2,2,2,2,2,2,3,3} and {1,2,2,2,2,2,2,2} tiles per interval of {1,1,1,1,2,2,2,2}
+__host__ __device__ constexpr int tile_extra(int abl, int k)
+{
+    constexpr int six[8] = {1, 1, 1, 1, 0, 0, 1, 1}, three[8] = {0, 1, 1, 1, 0, 0, 0, 0};
+    return (abl & 256) ? six[k] : (abl & 512) ? three[k] : 0;
 }
 
 template <int I, int N, bool SAVE, bool DIAG = false, int ABL = 0>
@@ -202,7 +220,9 @@ static int launch_bar16(const float *x, long ldx, const float *iW, const float *
         DIAG_LAUNCH(1, true, 0) DIAG_LAUNCH(2, false, 1) DIAG_LAUNCH(3, false, 2) DIAG_LAUNCH(4, false, 4) DIAG_LAUNCH(5, false, 8)
         DIAG_LAUNCH(6, false, 16) DIAG_LAUNCH(7, false, 9) DIAG_LAUNCH(8, false, 3) DIAG_LAUNCH(9, false, 11) DIAG_LAUNCH(10, false, 31)
         DIAG_LAUNCH(11, false, 32) DIAG_LAUNCH(12, false, 34) DIAG_LAUNCH(13, false, 40) DIAG_LAUNCH(14, false, 42) DIAG_LAUNCH(15, false, 36)
-        DIAG_LAUNCH(16, false, 64) DIAG_LAUNCH(17, true, 64)
+        DIAG_LAUNCH(16, false, 64) DIAG_LAUNCH(17, true, 64) DIAG_LAUNCH(18, false, 128) DIAG_LAUNCH(19, true, 128)
+        DIAG_LAUNCH(20, false, 256) DIAG_LAUNCH(21, true, 256) DIAG_LAUNCH(22, false, 512) DIAG_LAUNCH(23, true, 512)
+        DIAG_LAUNCH(24, false, 384) DIAG_LAUNCH(25, true, 384) DIAG_LAUNCH(26, false, 640) DIAG_LAUNCH(27, true, 640)
 #undef DIAG_LAUNCH
     }
 #endif

@@ -21,6 +21,13 @@
     // the service wave room for the tiles it keeps in ordinary registers next to the x rows it loads (128 -> 96 spilled)
     constexpr int CT = NCW == 3 ? (KBLK == 4 ? 3 : 2) : 0;
     constexpr int ST = (NT16 - NCW * CT) / NSW;                         // ... of a service wave
+    // Where a chain wave issues its share's MFMAs (design/gru_projection.md).  LATE: behind the write of r*h, in front of barrier B, with
+    // the x operands requested at the start of the same interval -- six MFMAs end under the write's own latency there, while in the LDS
+    // round trip at the start of interval A (the other place) they stand in front of the r products of the other blocks together with
+    // the own r and z blocks.  Four K blocks of input (128 -> 96: nine MFMAs in every step, the outputs right behind the last) keep the
+    // round trip.
+    constexpr bool LATE = CT > 0 && KBLK <= 3;
+    constexpr int TBL = (NSW == 1 && KBLK <= 3) ? 1 : 0;                // the service wave's tiles per interval: tile_first
     constexpr int NACAP = 240 / (8 * KBLK);                              // 256 accumulation registers, 2 * KBLK * 4 per tile
     constexpr int NA = ST < NACAP ? ST : NACAP;                               // of which this many keep their weights in accumulation registers
     static_assert(NCW * CT + NSW * ST == NT16, "tile assignment");
@@ -230,8 +237,10 @@
                 mfma_drain(pacc[t]);
                 proj_out(w * CT + t, pacc[t], 0);
             }
-            pxh = ldH(xop_hi, OPIMG + poff);             // step 0 projects K block 0 of group 1
-            pxl = ldH(xop_lo, OPIMG + poff);
+            if constexpr (!LATE) {
+                pxh = ldH(xop_hi, OPIMG + poff);         // step 0 projects K block 0 of group 1
+                pxl = ldH(xop_lo, OPIMG + poff);
+            }
         }
         lds_bar();                                       // vI of group 0 complete
 
@@ -248,11 +257,12 @@
         // One step = two intervals, each opened by a barrier; MFMAs are issued in an order that keeps the matrix pipe busy
         // through every LDS round trip and every stretch of gate arithmetic (an MFMA occupies the pipe for 16 cycles and
         // the issuing wave for 4):
-        //   A  [others' h(s-1) visible]  request the other K blocks, then vI(s); r products with my own block (already in
-        //      registers) and this step's share of the projection while they fly; r products with the others, tile 0 first;
-        //      sigmoid(r), r*h, split, write, own block read back; ALL z products somewhere in this interval (NB_S, NB_E below)
-        //   B  [others' r*h visible]     request the other K blocks, then the x operands of the next step's share of the
-        //      projection; candidate products with my own block, then sigmoid(z), 1 - z and z*h while they fly; candidate
+        //   A  [others' h(s-1) visible]  request the other K blocks, then vI(s), then the x operands of this step's share of the
+        //      projection; r products with my own block (already in registers) while they fly; r products with the others, tile 0
+        //      first; sigmoid(r), r*h, split, write, own block read back; ALL z products somewhere in this interval (NB_S, NB_E
+        //      below); this step's share of the projection behind the write (LATE; otherwise in the round trip at the start)
+        //   B  [others' r*h visible]     request the other K blocks (not LATE: then the x operands of the next step's share of the
+        //      projection); candidate products with my own block, then sigmoid(z), 1 - z and z*h while they fly; candidate
         //      products with the others (tile 0 first); tanh, blend, split, write, own block read back, store
         // The gate arithmetic reads the accumulators from inline asm (pick_sum_kept), where hipcc inserts no wait states, and the
         // hardware does not interlock a vector read of an MFMA result: seven wait states must lie between a
@@ -281,7 +291,7 @@
         constexpr int NB_S = KBS == 2 ? 0 : 1, NB_E = KBS == 2 ? 0 : KBS;
         auto step = [&](auto PHC, const int s, const int G) {
             constexpr int ph = decltype(PHC)::value;
-            constexpr bool PROJ = CT > 0 && ph < KBLK;
+            constexpr bool PROJ = CT > 0 && ph < KBLK && !(ABL & 128);
             // ------------------------------ interval A ------------------------------
             if constexpr (DIAG) lds_bar(); else lds_bar_1read<!(ABL & 1)>();
             BSTAMP(0)
@@ -309,17 +319,22 @@
                 vz[p] = vcur[64 * (2 * w + p)];
                 vc[p] = vcur[64 * (2 * NT + 2 * w + p)];
             }
+            if constexpr (LATE && PROJ) {                // x operands of my share, K block ph of group G+1 (split a group ago): behind h and vI
+                const int ob = ((G + 1) & 1) * OPIMG + poff + 64 * ph;
+                pxh = ldH(xop_hi, ob);
+                pxl = ldH(xop_lo, ob);
+            }
             __builtin_amdgcn_sched_barrier(0);
             f32x4 accR[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
             mfma2(wr_hi[0][0], wr_lo[0][0], bh[0], accR[0]);
             mfma2(wr_hi[1][0], wr_lo[1][0], bh[0], accR[1]);
-            if constexpr (PROJ) {                        // my tile of the projection, K block ph: inside the LDS round trip
+            if constexpr (PROJ && !LATE) {              // my tile of the projection, K block ph: inside the LDS round trip
                 if constexpr (!(ABL & 2)) {
 #pragma unroll
                     for (int t = 0; t < CT; t++) block_mfma_acc<ph == 0>(pacc[t], pw_hi[t][ph], pw_lo[t][ph], pxh, pxl);
                 }
             }
-            if constexpr (CT > 0 && ph == 3) {           // vI of group G+1 (its last MFMAs were issued a step ago unless KBLK = 4)
+            if constexpr (CT > 0 && ph == 3 && !(ABL & 128)) {   // vI of group G+1 (its last MFMAs were issued a step ago unless KBLK = 4)
 #pragma unroll
                 for (int t = 0; t < CT; t++) {
                     if constexpr (KBLK == 4) mfma_drain(pacc[t]);
@@ -389,6 +404,11 @@
                 }
                 asm volatile("" : "+v"(accZ[0]), "+v"(accZ[1]));
             }
+            // my share of the projection, K block ph: asm statements, so they stay behind the fence above and in front of the barrier
+            if constexpr (PROJ && LATE && !(ABL & 2)) {
+#pragma unroll
+                for (int t = 0; t < CT; t++) block_mfma_acc<ph == 0>(pacc[t], pw_hi[t][ph], pw_lo[t][ph], pxh, pxl);
+            }
             const bool store = live && s < Tc && !(ABL & 16);
             // ------------------------------ interval B ------------------------------
             if constexpr (DIAG) { BSTAMP(3) lds_bar(); } else lds_bar_1read<!(ABL & 1)>();
@@ -401,7 +421,7 @@
                 __builtin_amdgcn_sched_barrier(0);
             }
             constexpr int nph = (ph + 1) & 3;            // the next step projects K block nph of the group after ITS group
-            constexpr bool NPROJ = CT > 0 && nph < KBLK;
+            constexpr bool NPROJ = CT > 0 && nph < KBLK && !(ABL & 128) && !LATE;
             if constexpr (NPROJ) {
                 const int ob = ((G + (ph == 3 ? 2 : 1)) & 1) * OPIMG + poff + 64 * nph;
                 pxh = ldH(xop_hi, ob);
@@ -636,7 +656,7 @@
         // which tiles an interval computes: the leader's intervals 1-3 carry the x split, so they get fewer
         auto project_interval = [&](auto KC, int G1) {
             constexpr int k = decltype(KC)::value;
-            constexpr int lo = tile_first(ST, k), hi = tile_first(ST, k + 1);
+            constexpr int lo = tile_first(ST, k, TBL), hi = tile_first(ST, k + 1, TBL);
             static_assert(hi - lo <= 3, "at most three tiles per interval");
             if constexpr (hi - lo == 1) project_tiles(ic<lo>{}, ic<ST>{}, G1);
             if constexpr (hi - lo == 2) project_tiles(ic<lo>{}, ic<lo + 1>{}, G1);
@@ -656,6 +676,10 @@
             if constexpr (ABL & 8) return;
             if constexpr (k == 0) load_operands(G + 1);
             project_interval(KC, G + 1);
+            if constexpr (tile_extra(ABL, k) > 0) {      // ablation: one tile of this interval once more (same value, same place)
+                constexpr int lo = tile_first(ST, k, TBL);
+                project_tiles(ic<(lo < NA ? lo : NA - 1)>{}, ic<ST>{}, G + 1);
+            }
             if (leader) {
                 if constexpr (k == 1) split_scale(G + 2);
                 if constexpr (k >= 2 && k < 2 + KBLK) split_block(G + 2, k - 2);

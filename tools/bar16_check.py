@@ -49,13 +49,19 @@ for I, n in shapes:
     print("ablations (results garbage), cycles/step at 2.4 GHz; production %.0f" % (base * 1e6 / T * 2.4))
     for code, nm in ((2, "no s_barrier"), (3, "chain: no MFMAs"), (4, "cheap activations"), (5, "service waves idle"), (6, "no h_out stores"),
                      (7, "no s_barrier + service idle"), (8, "no s_barrier + no chain MFMAs"), (9, "no barrier, no chain MFMAs, service idle"), (10, "everything off"),
-                     (16, "chain: no z products, no z epilogue")):
+                     (16, "chain: no z products, no z epilogue"), (18, "chain: no projection share"),
+                     (20, "service: six tiles twice"), (22, "service: three tiles twice"),
+                     (24, "chain: no projection share + service: six tiles twice"),
+                     (26, "chain: no projection share + service: three tiles twice")):
         ms = timeit_code(code)
-        print("   %-44s %6.0f" % (nm, ms * 1e6 / T * 2.4))
+        print("   %-56s %6.0f" % (nm, ms * 1e6 / T * 2.4))
     L.slk_debug_read_bar16.argtypes = [ctypes.c_void_p]
-    names = ["barrier A", "reads + projection MFMAs + own z block + wait h", "r MFMAs", "z MFMAs + r epilogue + write", "barrier B",
+    names = ["barrier A", "reads + own z block + wait h", "r MFMAs", "z MFMAs + r epilogue + write + projection MFMAs", "barrier B",
              "reads + own c block + z epilogue + wait r*h", "c MFMAs", "tanh, blend, split, writes, stores"]
-    for code, what in ((1, "production"), (17, "no z products, no z epilogue (results garbage)")):
+    for code, what in ((1, "production"), (17, "no z products, no z epilogue (results garbage)"),
+                       (19, "chain: no projection share (results garbage)"), (21, "service: six tiles twice"),
+                       (23, "service: three tiles twice"), (25, "chain: no projection share + service: six tiles twice (results garbage)"),
+                       (27, "chain: no projection share + service: three tiles twice (results garbage)")):
         L.slk_gru_bar16_f32(x.data_ptr(), I, iW.data_ptr(), sW.data_ptr(), sW2.data_ptr(), bb.data_ptr(), y.data_ptr(), n, T, B, I, n, 2 * code, 1, 2, None, None, st)
         torch.cuda.synchronize()
         stp = (ctypes.c_ulonglong * 64)()
