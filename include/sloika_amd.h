@@ -761,6 +761,57 @@ SLK_API int slk_align_local_batch_u8(const uint8_t *q, long ldq, const int32_t *
                                      void *workspace, size_t workspace_bytes, slk_stream_t stream);
 SLK_API int slk_revcomp_u8(const uint8_t *seq, const int64_t *off, int B, long max_len, uint8_t *out, slk_stream_t stream);
 
+/* The columns of those alignments: what a SAM record's CIGAR and an error profile are made of (csrc/align_traceback.hip,
+ * design/align_traceback.md).  slk_align_local_batch_u8 keeps no traceback; its row gives the start cell and the numbers of
+ * insertions I and deletions D, and relative to its start the alignment never leaves the W = I + D + 1 diagonals i - j in [-D, +I].
+ * A second DP over that band alone, anchored at the start cell, under the same tie rules, walks back the same operations.
+ *   slk_align_traceback_max_band (host only): the widest band W the kernel accepts.
+ *   slk_align_traceback_workspace_bytes (host only): bytes of workspace of ONE pair whose row has the spans q_span = q_end - q_start,
+ *     r_span = r_end - r_start and the counts insertion, deletion: 4 bits per band cell, a multiple of 16.  0 for spans and counts
+ *     no row can have (negative, beyond 65535, q_span - insertion != r_span - deletion) and for W above the widest band.
+ *   slk_align_traceback_batch_u8: q, ldq, qlen, r, roff, B and the four scores as slk_align_local_batch_u8 took them; rows:[B][9]
+ *     int32, that call's output, in the coordinates of the `r` it ran against.  Pair b's columns go to ops[ops_off[b] ..
+ *     ops_off[b + 1]), one byte per column in query order (SLK_ALIGN_OP_*); ops_off:[B + 1] device int64 with ops_off[b + 1] -
+ *     ops_off[b] = match + mismatch + insertion + deletion of the row, ops_bytes (host) the size of `ops`.  Pair b's traceback
+ *     bits live in workspace[ws_off[b] .. ws_off[b + 1]) (ws_off:[B + 1] device int64, ws_off[b] a multiple of 16, the slice at
+ *     least slk_align_traceback_workspace_bytes of the row; `workspace` 16-byte aligned, workspace_bytes (host) its size).
+ *     status:[B] int32: SLK_ALIGN_TB_DONE, SLK_ALIGN_TB_EMPTY (score <= 0: no columns; nothing else of the pair is looked at) or
+ *     a negative SLK_ALIGN_TB_* code.  The row is device data and is not trusted: a pair whose spans leave [0, qlen] or
+ *     [0, rlen], whose counts are negative or do not add up to the spans, whose band is too wide, whose workspace slice is
+ *     misaligned, too short or outside the workspace, or whose ops slice disagrees with its column count is SKIPPED -- nothing
+ *     but its row, lengths and offsets is read, nothing but its status written.  SLK_ALIGN_TB_SCORE / _WALK: the band's DP did
+ *     not end on the row's score / the walk did not reach the start cell in exactly the announced number of columns (a row that
+ *     does not belong to these sequences and scores); the pair's own ops slice may then hold anything.  Nothing outside a
+ *     pair's own slices is ever written and no loop bound depends on a score.
+ *   slk_align_error_profile_u8: profile:[B][SLK_ALIGN_PROFILE_LEN] int32, every entry written (no zeroing needed; all 0 for a pair
+ *     whose status is not SLK_ALIGN_TB_DONE).  Letter classes A, C, G, T, other, gap = 0..5.  Entries 0..35: columns by
+ *     query class * 6 + reference class (an insertion has reference class 5, a deletion query class 5; entry 35 stays 0);
+ *     36..51: maximal runs of insertions of length 1..15 and >= 16; 52..67: the same for deletions.                              */
+#define SLK_ALIGN_OP_MATCH 0
+#define SLK_ALIGN_OP_MISMATCH 1
+#define SLK_ALIGN_OP_INSERTION 2 /* a query letter against a gap      */
+#define SLK_ALIGN_OP_DELETION 3  /* a reference letter against a gap  */
+#define SLK_ALIGN_PROFILE_LEN 68
+#define SLK_ALIGN_TB_DONE 0
+#define SLK_ALIGN_TB_EMPTY 1
+#define SLK_ALIGN_TB_BAD_SPAN (-1)  /* a span outside [0, qlen] / [0, rlen], or a length beyond 65535 or the row pitch  */
+#define SLK_ALIGN_TB_BAD_COUNT (-2) /* a negative count                                                                  */
+#define SLK_ALIGN_TB_BAD_SUM (-3)   /* the spans are not the sums of the counts                                          */
+#define SLK_ALIGN_TB_BAND (-4)      /* insertion + deletion + 1 > slk_align_traceback_max_band()                         */
+#define SLK_ALIGN_TB_WORKSPACE (-5) /* the pair's workspace slice is misaligned, too short or outside the workspace      */
+#define SLK_ALIGN_TB_OPS (-6)       /* the pair's ops slice is not its column count long, or outside `ops`               */
+#define SLK_ALIGN_TB_SCORE (-7)     /* the band's DP does not end on the row's score                                     */
+#define SLK_ALIGN_TB_WALK (-8)      /* the walk did not reach the start cell in the announced number of columns          */
+SLK_API int slk_align_traceback_max_band(void);
+SLK_API size_t slk_align_traceback_workspace_bytes(int q_span, int r_span, int insertion, int deletion);
+SLK_API int slk_align_traceback_batch_u8(const uint8_t *q, long ldq, const int32_t *qlen, const uint8_t *r, const int64_t *roff, int B,
+                                         int match, int mismatch, int gap_open, int gap_extend, const int32_t *rows, uint8_t *ops,
+                                         const int64_t *ops_off, size_t ops_bytes, void *workspace, const int64_t *ws_off,
+                                         size_t workspace_bytes, int32_t *status, slk_stream_t stream);
+SLK_API int slk_align_error_profile_u8(const uint8_t *q, long ldq, const uint8_t *r, const int64_t *roff, const int32_t *rows,
+                                       const uint8_t *ops, const int64_t *ops_off, const int32_t *status, int B, int32_t *profile,
+                                       slk_stream_t stream);
+
 /* f6. The forward (sum-product) score of a sequence under a transducer posterior: decode.score / decode.forwards
  * (sloika/decode.py:96-139), for `nread` (posterior, sequence) pairs in one launch, one workgroup per pair, in float64
  * (csrc/forward_score.hip, design/forward_score.md).  The score is the reference's up to rounding (it sums in another order and

@@ -148,6 +148,10 @@ PROTOTYPES = {
     "slk_align_local_workspace_bytes": (_sz, [_i, _i, _i]),
     "slk_align_local_batch_u8": (_i, [_vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "slk_revcomp_u8": (_i, [_vp, _vp, _i, _l, _vp, _vp]),
+    "slk_align_traceback_max_band": (_i, []),
+    "slk_align_traceback_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "slk_align_traceback_batch_u8": (_i, [_vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp]),
+    "slk_align_error_profile_u8": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "slk_forward_score_max_positions": (_i, []),
     "slk_forward_score_batch_f32": (_i, [_vp, _l, _vp, _l, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "slk_forward_score_batch_f64": (_i, [_vp, _l, _vp, _l, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),

@@ -70,9 +70,12 @@ def _pack_references(references):
     return packed, roff, rlens
 
 
-def _align_device(q, ldq, qlen, max_qlen, ref, roff, rlens, scores, both_strands):
+def _align_device(q, ldq, qlen, max_qlen, ref, roff, rlens, scores, both_strands, ops=False, workspace_limit=None, parts_out=None):
     """q:[B][ldq] uint8, qlen:[B] int32, ref packed uint8, roff:[B+1] int64 -- all on the device; rlens host int64.
-    -> (int32 [B, 9] host array, strand array of '+' / '-')."""
+    -> (int32 [B, 9] host array, strand array of '+' / '-'), and with `ops` the alignments' columns as an Ops (the traceback runs
+    right behind the forward launch, on the device rows as they are: in the coordinates of the buffer they were computed against).
+    parts_out: a list that receives (reference buffer, roff, device rows, host mask of the pairs it serves) per strand buffer, for a
+    caller that runs the traceback itself over several such calls (genome.Index._map_device)."""
     import torch
     from . import device as D
     L = _lib.lib()
@@ -93,22 +96,267 @@ def _align_device(q, ldq, qlen, max_qlen, ref, roff, rlens, scores, both_strands
         res = out.cpu().numpy()
         if (res[:, 0] < 0).any():
             raise ValueError("align: a sequence on the device is longer than the bound it was launched with")
-        return res
+        return res, out
 
-    fwd = run(ref)
+    fwd, fwd_d = run(ref)
     strand = np.full(B, '+', dtype='U1')
+    parts = [(ref, roff, fwd_d, np.ones(B, dtype=bool))]
+    buffer_rows = fwd.copy() if (ops or parts_out is not None) else None
     if both_strands and B:
-        rev = run(revcomp_packed(ref, roff, max_rlen))
+        rc = revcomp_packed(ref, roff, max_rlen)
+        rev, rev_d = run(rc)
         take = rev[:, 0] > fwd[:, 0]                       # a tie goes to '+'
+        if buffer_rows is not None:                        # which buffer serves which pair: settled BEFORE '-' rows change coordinates
+            buffer_rows[take] = rev[take]
+            parts = [(ref, roff, fwd_d, ~take), (rc, roff, rev_d, take.copy())]
         rs, re = rev[:, 3].copy(), rev[:, 4].copy()        # back to forward-strand coordinates, as a SAM record gives them
         rev[:, 3] = np.where(rev[:, 0] > 0, rlens - re, 0)
         rev[:, 4] = np.where(rev[:, 0] > 0, rlens - rs, 0)
         fwd[take] = rev[take]
         strand[take] = '-'
-    return fwd, strand
+    if parts_out is not None:
+        parts_out.extend(parts)
+    if not ops:
+        return fwd, strand
+    return fwd, strand, _traceback_device(q, ldq, qlen, parts, buffer_rows, scores, workspace_limit)
 
 
-def align_batch(queries, references, match=1, mismatch=2, gap_open=2, gap_extend=1, both_strands=False):
+# ---- the alignments' columns: traceback, CIGAR, error profile, SAM (csrc/align_traceback.hip, design/align_traceback.md) ------------
+
+#: codes of an alignment column (include/sloika_amd.h: SLK_ALIGN_OP_*)
+OP_MATCH, OP_MISMATCH, OP_INSERTION, OP_DELETION = 0, 1, 2, 3
+#: letter classes of the error profile; 'gap' is the side an insertion / a deletion has no letter on
+LETTER_CLASSES = ("A", "C", "G", "T", "other", "gap")
+#: names of the 68 entries of a profile row: "query class/reference class", then the run-length histograms
+PROFILE_FIELDS = tuple(["%s/%s" % (a, b) for a in LETTER_CLASSES for b in LETTER_CLASSES] +
+                       ["%s_run_%s" % (w, "%d" % k if k < 16 else "16+") for w in ("insertion", "deletion") for k in range(1, 17)])
+#: per-pair status of the traceback (include/sloika_amd.h: SLK_ALIGN_TB_*)
+TB_DONE, TB_EMPTY = 0, 1
+TB_REASONS = {
+    -1: "a span of its row lies outside the sequences",
+    -2: "its row has a negative count",
+    -3: "the spans of its row are not the sums of its counts",
+    -4: "insertions + deletions + 1 exceed the widest band the traceback kernel accepts",
+    -5: "its slice of the traceback workspace is misaligned, too short or outside the workspace",
+    -6: "its slice of the column codes does not have the length of its alignment",
+    -7: "the band's DP does not end on the row's score (the row does not belong to these sequences and scores)",
+    -8: "the walk did not reach the alignment's start in the announced number of columns",
+}
+
+
+def _traceback_runs(nbytes, limit):
+    """Consecutive runs [lo, hi) whose traceback workspace stays within `limit` bytes; a pair above the limit alone is a run of one."""
+    n = len(nbytes)
+    if limit is None or n == 0:
+        return [(0, n)]
+    runs, lo, tot = [], 0, 0
+    for b in range(n):
+        if b > lo and tot + int(nbytes[b]) > limit:
+            runs.append((lo, b))
+            lo, tot = b, 0
+        tot += int(nbytes[b])
+    runs.append((lo, n))
+    return runs
+
+
+def _traceback_device(q, ldq, qlen, parts, rows, scores, workspace_limit=None):
+    """The columns of the alignments `rows` describes -> Ops.  parts: [(reference buffer, roff, device rows, host mask)], one per
+    strand buffer; a buffer's launch sees a zeroed row for every pair it does not serve.  rows: host [B, 9], every pair's row in the
+    coordinates of ITS buffer.  Offsets come from the host rows; the launches are split at workspace_limit bytes of workspace, and a
+    pair's columns do not depend on the split."""
+    import torch
+    from . import device as D
+    L = _lib.lib()
+    B = len(rows)
+    dev = qlen.device
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    live = rows[:, 0] > 0
+    ncol = np.where(live, rows[:, 5:9].astype(np.int64).sum(axis=1), 0)
+    off = np.concatenate(([0], np.cumsum(ncol))).astype(np.int64)
+    need = np.array([L.slk_align_traceback_workspace_bytes(int(r[2] - r[1]), int(r[4] - r[3]), int(r[7]), int(r[8])) if r[0] > 0 else 0
+                     for r in rows], dtype=np.int64)
+    codes = torch.empty(max(int(off[-1]), 8), dtype=torch.uint8, device=dev)
+    off_d = torch.from_numpy(off).to(dev)
+    status = np.full(B, TB_EMPTY, dtype=np.int32)
+    kept = []
+    for ref, roff, rows_d, mask in parts:
+        if not B:
+            break
+        mask = np.asarray(mask, dtype=bool)
+        rows_m = rows_d if mask.all() else rows_d * torch.from_numpy(mask.astype(np.int32)).to(dev)[:, None]
+        rows_m = rows_m.contiguous()
+        st_d = torch.empty(B, dtype=torch.int32, device=dev)
+        want = np.where(mask, need, 0)
+        for lo, hi in _traceback_runs(want, workspace_limit):
+            wo = np.concatenate(([0], np.cumsum(want[lo:hi]))).astype(np.int64)
+            ws = torch.empty(max(int(wo[-1]), 16), dtype=torch.uint8, device=dev)
+            wo_d = torch.from_numpy(wo).to(dev)
+            _lib.check(L.slk_align_traceback_batch_u8(q[lo:hi].data_ptr(), ldq, qlen[lo:hi].data_ptr(), ref.data_ptr(),
+                                                      roff[lo:hi + 1].data_ptr(), hi - lo, scores[0], scores[1], scores[2], scores[3],
+                                                      rows_m[lo:hi].data_ptr(), codes.data_ptr(), off_d[lo:hi + 1].data_ptr(),
+                                                      codes.numel(), ws.data_ptr(), wo_d.data_ptr(), ws.numel(),
+                                                      st_d[lo:hi].data_ptr(), D.stream_ptr()), "align_traceback_batch")
+        status[mask] = st_d.cpu().numpy()[mask]
+        kept.append((ref, roff, rows_m, st_d))
+    return Ops(q, ldq, qlen, kept, rows, codes, off, off_d, status, int(need.sum()))
+
+
+class Ops(object):
+    """The columns of a batch of alignments, on the device.
+
+    codes_dev: uint8 device tensor, one byte per alignment column (OP_MATCH, OP_MISMATCH, OP_INSERTION: a query letter against a
+    gap, OP_DELETION: a reference letter against a gap), pair b's at offsets[b] .. offsets[b + 1] in query order (offsets: host
+    int64, offsets_dev: the same on the device).  status: host int32 per pair, TB_DONE, TB_EMPTY (no alignment, no columns) or a
+    negative code of TB_REASONS; touching such a pair raises a ValueError that names it.  rows: host [B, 9], every pair's row in
+    the coordinates of the buffer its columns index.  q, ldq, qlen: the query buffer; parts: per strand buffer (reference buffer --
+    for '-' the reverse-complemented one --, roff, the device rows that buffer's launch saw, its device status).
+    workspace_bytes: what the tracebacks needed in all."""
+
+    def __init__(self, q, ldq, qlen, parts, rows, codes, offsets, offsets_dev, status, workspace_bytes=0):
+        self.q, self.ldq, self.qlen, self.parts, self.rows = q, ldq, qlen, parts, rows
+        self.codes_dev, self.offsets, self.offsets_dev, self.status = codes, offsets, offsets_dev, status
+        self.workspace_bytes = workspace_bytes
+        self._host = None
+        self._qlen_host = None
+
+    def __len__(self):
+        return len(self.rows)
+
+    def check(self, b):
+        if self.status[b] < 0:
+            raise ValueError("align: no columns for pair %d: %s" % (b, TB_REASONS.get(int(self.status[b]), "status %d" % self.status[b])))
+
+    def codes(self, b):
+        """uint8 host array of pair b's columns in query order (empty for an empty alignment)."""
+        self.check(b)
+        if self._host is None:
+            self._host = self.codes_dev.cpu().numpy()
+        if self.status[b] != TB_DONE:
+            return np.zeros(0, dtype=np.uint8)
+        return self._host[self.offsets[b]:self.offsets[b + 1]]
+
+    def query_lengths(self):
+        if self._qlen_host is None:
+            self._qlen_host = self.qlen.cpu().numpy()
+        return self._qlen_host
+
+    def queries(self):
+        """The query letters as a list of bytes, fetched from the device buffer (for a SAM export of calls that never left it)."""
+        n = self.query_lengths()
+        host = self.q.cpu().numpy() if len(n) else np.zeros((0, 1), dtype=np.uint8)
+        return [host[b, :n[b]].tobytes() for b in range(len(n))]
+
+    def cigar(self, b, extended=True, clip=None, reverse=False):
+        """Pair b's CIGAR: '=' / 'X' / 'I' / 'D', or 'M' / 'I' / 'D' when not extended ('*' for an empty alignment).  clip: the
+        query's length; the unaligned letters in front of and behind the alignment then become soft clips.  reverse: the columns
+        back to front, as a SAM record of a '-' alignment gives them."""
+        codes = self.codes(b)
+        if self.status[b] != TB_DONE:
+            return "*"
+        front = back = 0
+        if clip is not None:
+            front, back = int(self.rows[b, 1]), int(clip) - int(self.rows[b, 2])
+        if reverse:
+            codes, front, back = codes[::-1], back, front
+        return cigar_string(codes, extended, front, back)
+
+    def profile(self):
+        """int32 host array [B, 68] (PROFILE_FIELDS) from slk_align_error_profile_u8; zeros for a pair without columns."""
+        import torch
+        from . import device as D
+        B = len(self)
+        total = np.zeros((B, len(PROFILE_FIELDS)), dtype=np.int32)
+        for b in np.flatnonzero(self.status < 0):
+            self.check(b)
+        for ref, roff, rows_d, st_d in self.parts:
+            out = torch.empty((B, len(PROFILE_FIELDS)), dtype=torch.int32, device=self.codes_dev.device)
+            _lib.check(_lib.lib().slk_align_error_profile_u8(self.q.data_ptr(), self.ldq, ref.data_ptr(), roff.data_ptr(),
+                                                             rows_d.data_ptr(), self.codes_dev.data_ptr(), self.offsets_dev.data_ptr(),
+                                                             st_d.data_ptr(), B, out.data_ptr(), D.stream_ptr()), "align_error_profile")
+            total += out.cpu().numpy()
+        return total
+
+
+def cigar_string(codes, extended=True, clip_front=0, clip_back=0):
+    """Run-length encoding of column codes (host, numpy)."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    letters = np.frombuffer(b"=XID" if extended else b"MMID", dtype=np.uint8)[codes] if len(codes) else codes
+    out = ["%dS" % clip_front] if clip_front > 0 else []
+    if len(letters):
+        cut = np.flatnonzero(letters[1:] != letters[:-1]) + 1
+        starts, ends = np.concatenate(([0], cut)), np.concatenate((cut, [len(letters)]))
+        out.extend("%d%s" % (e - s, chr(letters[s])) for s, e in zip(starts, ends))
+    if clip_back > 0:
+        out.append("%dS" % clip_back)
+    return "".join(out)
+
+
+def error_summary(profile):
+    """Figures over all pairs of a profile ([B, 68] or [68]) as a dict: `substitutions` (4 x 4 int array, query letter by reference
+    letter over A C G T; the diagonal are the matches), `insertions` / `deletions` by letter (A C G T other), `insertion_runs` /
+    `deletion_runs` (16 bins: lengths 1..15 and >= 16), `reference_letters` (aligned reference letters: match + mismatch + deletion)
+    and the rates per aligned reference letter: `mismatch_rate` (aligned pairs that are not a match of two of A C G T),
+    `insertion_rate`, `deletion_rate`."""
+    p = np.asarray(profile, dtype=np.int64).reshape(-1, len(PROFILE_FIELDS)).sum(axis=0)
+    m = p[:36].reshape(6, 6)
+    pairs, matches = int(m[:5, :5].sum()), int(np.trace(m[:4, :4]))
+    ins, dele = int(m[:5, 5].sum()), int(m[5, :5].sum())
+    ref = pairs + dele
+    rate = (lambda v: float(v) / ref) if ref else (lambda v: float('nan'))
+    return {'substitutions': m[:4, :4].copy(), 'insertions': m[:5, 5].copy(), 'deletions': m[5, :5].copy(),
+            'insertion_runs': p[36:52].copy(), 'deletion_runs': p[52:68].copy(), 'reference_letters': ref,
+            'mismatch_rate': rate(pairs - matches), 'insertion_rate': rate(ins), 'deletion_rate': rate(dele)}
+
+
+_COMPLEMENT = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+def sam_record(name, row, strand, codes, query_length, rname, seq=None):
+    """One SAM line (no newline) of an alignment: row = FIELDS with forward-strand r_start, codes = its columns in query order.
+    See sam_records for the field rules."""
+    score, qs, qe, rs = int(row[0]), int(row[1]), int(row[2]), int(row[3])
+    if seq is not None and not isinstance(seq, str):
+        seq = bytes(bytearray(_as_u8(seq))).decode('ascii')
+    if score <= 0:
+        return "\t".join([str(name), "4", "*", "0", "0", "*", "*", "0", "0", seq if seq else "*", "*"])
+    front, back = qs, int(query_length) - qe
+    if strand == '-':
+        codes, front, back = np.asarray(codes)[::-1], back, front
+        if seq is not None:
+            seq = seq.encode('ascii').translate(_COMPLEMENT)[::-1].decode('ascii')
+    nm = int(row[6]) + int(row[7]) + int(row[8])
+    return "\t".join([str(name), "16" if strand == '-' else "0", str(rname), str(rs + 1), "255",
+                      cigar_string(codes, False, front, back), "*", "0", "0", seq if seq else "*", "*", "NM:i:%d" % nm,
+                      "AS:i:%d" % score])
+
+
+def sam_records(res, strand, ops, names, ref_names, ref_lengths, queries=None):
+    """SAM lines of the alignments of align_batch / accuracy_of_paths (ops=True), one per pair (misc/align.py:46-67 leaves a SAM
+    file behind; this is its content for the optimal alignment).  ref_names[b] / ref_lengths[b]: pair b's reference.
+
+    FLAG 0 ('+'), 16 ('-') or 4 (no alignment: RNAME '*', POS 0, MAPQ 0, CIGAR '*'); POS = r_start + 1 on the forward strand; MAPQ
+    255, which the SAM specification reserves for "not available" (no mapping quality is computed); CIGAR with M / I / D and soft
+    clips for the unaligned ends of the query; tags NM:i = mismatch + insertion + deletion and AS:i = score.  For '-' the columns
+    are reversed and SEQ is the reverse complement of the query.  SEQ is '*' without `queries` (ops.queries() fetches calls that
+    never left the device); QUAL is '*'.  No secondary or supplementary records."""
+    n = ops.query_lengths()
+    out = []
+    for b in range(len(res)):
+        if res[b][0] > 0 and int(res[b][4]) > int(ref_lengths[b]):
+            raise ValueError("align: pair %d ends at %d on a reference of %d letters" % (b, res[b][4], ref_lengths[b]))
+        out.append(sam_record(names[b], res[b], str(strand[b]), ops.codes(b), n[b], ref_names[b],
+                              None if queries is None else queries[b]))
+    return out
+
+
+def sam_text(header_refs, records):
+    """A SAM file's text: @HD, one @SQ per (name, length) of header_refs, then the records."""
+    head = ["@HD\tVN:1.6\tSO:unknown"] + ["@SQ\tSN:%s\tLN:%d" % (name, int(length)) for name, length in header_refs]
+    return "\n".join(head + list(records)) + "\n"
+
+
+def align_batch(queries, references, match=1, mismatch=2, gap_open=2, gap_extend=1, both_strands=False, ops=False,
+                workspace_limit=None):
     """Optimal local alignment of queries[b] against references[b] with affine gaps (a gap of k letters costs
     gap_open + k * gap_extend; the defaults are bwa's -A 1 -B 2 -O 2 -E 1 of align.py:22).
 
@@ -116,7 +364,10 @@ def align_batch(queries, references, match=1, mismatch=2, gap_open=2, gap_extend
     with the columns FIELDS (0-based half-open coordinates; all 0 for an empty alignment), strand an array of '+' / '-'.
     With both_strands each query is also aligned against the reverse complement of its reference and the higher score kept
     (a tie goes to '+'; this is samacc's `strand` column, align.py:40-41, 120); r_start / r_end of a '-' row are forward-strand
-    coordinates, the counts are those of the alignment against the reverse complement."""
+    coordinates, the counts are those of the alignment against the reverse complement.
+
+    ops=True: one more value, the alignments' columns as an Ops (for a '-' pair: columns against the reverse complement of the
+    reference, in query order); workspace_limit: bytes of traceback workspace per launch (None: one launch)."""
     import torch
     queries, references = list(queries), list(references)
     if len(queries) != len(references):
@@ -129,7 +380,7 @@ def align_batch(queries, references, match=1, mismatch=2, gap_open=2, gap_extend
     packed, roff, rlens = _pack_references(references)
     _lib.require_gpu()
     from . import device as D
-    if B == 0:
+    if B == 0 and not ops:
         return np.zeros((0, 9), dtype=np.int32), np.zeros(0, dtype='U1')
     ldq = max(max_qlen, 1)
     qh = np.zeros((B, ldq), dtype=np.uint8)
@@ -140,17 +391,18 @@ def align_batch(queries, references, match=1, mismatch=2, gap_open=2, gap_extend
     qlen = torch.tensor([len(x) for x in qs], dtype=torch.int32).to(dev)
     ref = torch.from_numpy(packed.copy()).to(dev)
     return _align_device(q, ldq, qlen, max_qlen, ref, torch.from_numpy(roff).to(dev), rlens,
-                         (int(match), int(mismatch), int(gap_open), int(gap_extend)), both_strands)
+                         (int(match), int(mismatch), int(gap_open), int(gap_extend)), both_strands, ops, workspace_limit)
 
 
 def accuracy_of_paths(paths, lens, references, kmer_len, alphabet='ACGT', match=1, mismatch=2, gap_open=2, gap_extend=1,
-                      both_strands=False):
+                      both_strands=False, ops=False, workspace_limit=None):
     """Align decoded paths to their references without the called sequences leaving the device.
 
     paths:[B, T] int32 device tensor of k-mer states and lens:[B] int32 device tensor, as any `call_*` returns them.  The
     paths become bases on the device (slk_paths_to_bases, always_move=True, what bio.paths_to_bases runs) and that buffer is
     the kernel's query operand as it lies.  Returns (results, strand, query_lengths): as align_batch, plus the number of
-    bases called per read (the denominator of samacc's coverage)."""
+    bases called per read (the denominator of samacc's coverage).  ops=True: one more value, the alignments' columns as an Ops,
+    made from the same device buffer (workspace_limit as for align_batch)."""
     import torch
     from . import device as D
     references = list(references)
@@ -171,9 +423,9 @@ def accuracy_of_paths(paths, lens, references, kmer_len, alphabet='ACGT', match=
     counts = nb.cpu().numpy()                              # B integers: the lengths only, for the launch bounds and coverage
     max_qlen = int(counts.max()) if B else 0
     ref = torch.from_numpy(packed.copy()).to(paths.device)
-    res, strand = _align_device(bases, cap, nb, max_qlen, ref, torch.from_numpy(roff).to(paths.device), rlens,
-                                (int(match), int(mismatch), int(gap_open), int(gap_extend)), both_strands)
-    return res, strand, counts
+    got = _align_device(bases, cap, nb, max_qlen, ref, torch.from_numpy(roff).to(paths.device), rlens,
+                        (int(match), int(mismatch), int(gap_open), int(gap_extend)), both_strands, ops, workspace_limit)
+    return (got[0], got[1], counts) + tuple(got[2:])
 
 
 def samacc_rows(results, strand, query_lengths, names=None, min_coverage=0.6):

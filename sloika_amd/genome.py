@@ -184,7 +184,7 @@ class Index(object):
 
     # ---- map ---------------------------------------------------------------------------------------------------------------------
 
-    def _map_device(self, q, ldq, qlen, lens, max_qlen, names, drift, min_votes, scores, workspace_limit):
+    def _map_device(self, q, ldq, qlen, lens, max_qlen, names, drift, min_votes, scores, workspace_limit, ops=False):
         B = len(lens)
         seeds = self._seed_device(q, ldq, qlen, max_qlen)
         W = self.bin_width
@@ -208,10 +208,20 @@ class Index(object):
         wlens = we - ws
         ref, roff, roff_d = self.cut(ws, we, strand == '-')
         res = np.zeros((B, 9), dtype=np.int32)
+        device_rows = []
         for lo, hi in align_runs(lens, wlens, workspace_limit):
             if hi > lo:
+                parts = [] if ops else None
                 res[lo:hi], _ = align._align_device(q[lo:hi], ldq, qlen[lo:hi], int(lens[lo:hi].max()), ref, roff_d[lo:hi + 1],
-                                                    wlens[lo:hi], scores, False)
+                                                    wlens[lo:hi], scores, False, parts_out=parts)
+                if ops:
+                    device_rows.append(parts[0][2])
+        columns = None
+        if ops:                                                 # on the rows as the windows' launches left them: window coordinates
+            import torch
+            rows_d = torch.cat(device_rows) if device_rows else torch.zeros((0, 9), dtype=torch.int32, device=qlen.device)
+            columns = align._traceback_device(q, ldq, qlen, [(ref, roff_d, rows_d, np.ones(B, dtype=bool))], res.copy(), scores,
+                                              workspace_limit)
         edge = np.zeros(B, dtype=np.int32)
         for b in np.flatnonzero(res[:, 0] > 0):
             rs, re = int(res[b, 3]), int(res[b, 4])
@@ -226,10 +236,10 @@ class Index(object):
         strand[contig < 0] = '+'
         info = {'contig': contig, 'votes': pick[:, 1].astype(np.int32), 'second': pick[:, 2].astype(np.int32), 'edge': edge,
                 'window_start': ws, 'window_end': we, 'seeds': seeds}
-        return res, strand, info
+        return (res, strand, info, columns) if ops else (res, strand, info)
 
     def map(self, queries, drift=1.0 / 16, min_votes=3, match=1, mismatch=2, gap_open=2, gap_extend=1, workspace_limit=None,
-            names=None):
+            names=None, ops=False):
         """Place every query on the genome and align it there.  -> (res, strand, info).
 
         The strand with more votes wins (a tie goes to '+'); a query with fewer than min_votes is unmapped: its row of `res` is all
@@ -244,20 +254,24 @@ class Index(object):
         (index into Index.names, -1 unmapped), `votes`, `second` (the best count among bins further than 2 from the winner: a
         second locus), `edge` (1: the alignment touches a window end that is not a contig end while the query has unaligned letters
         on that side -- rerun with a larger drift; nothing is widened silently), `window_start` / `window_end` (packed-genome
-        coordinates) and `seeds`, the kernel's rows."""
+        coordinates) and `seeds`, the kernel's rows.
+
+        ops=True: one more value, the alignments' columns as an align.Ops (slk_align_traceback_batch_u8 on the windows: its rows
+        are in window coordinates, for '-' against the reverse-complemented window; workspace_limit bounds the traceback's
+        workspace per launch as well).  sam_records turns them into SAM lines."""
         align._check_scores(match, mismatch, gap_open, gap_extend)
         queries = list(queries)
         _lib.require_gpu()
         q, ldq, qlen, lens, max_qlen = self._upload(queries)
         return self._map_device(q, ldq, qlen, lens, max_qlen, names, drift, min_votes,
-                                (int(match), int(mismatch), int(gap_open), int(gap_extend)), workspace_limit)
+                                (int(match), int(mismatch), int(gap_open), int(gap_extend)), workspace_limit, ops)
 
     def map_paths(self, paths, lens, kmer_len, alphabet='ACGT', drift=1.0 / 16, min_votes=3, match=1, mismatch=2, gap_open=2,
-                  gap_extend=1, workspace_limit=None, names=None):
+                  gap_extend=1, workspace_limit=None, names=None, ops=False):
         """`map` of decoded paths without the called sequences leaving the device: paths:[B, T] int32 device tensor of k-mer states
         and lens:[B] int32 device tensor, as any `call_*` returns them, become bases through slk_paths_to_bases(always_move=True)
         and that buffer is the query operand of the seed stage and of the aligner as it lies.  Only the base counts come to the
-        host.  -> (res, strand, info, nbases)."""
+        host.  -> (res, strand, info, nbases), with ops=True one more value, the align.Ops of `map`."""
         import torch
         from . import device as D
         align._check_scores(match, mismatch, gap_open, gap_extend)
@@ -276,9 +290,24 @@ class Index(object):
         counts = nb.cpu().numpy()
         max_qlen = int(counts.max()) if B else 0
         align._check_len(max_qlen, "a query")
-        res, strand, info = self._map_device(bases, cap, nb, counts, max_qlen, names, drift, min_votes,
-                                             (int(match), int(mismatch), int(gap_open), int(gap_extend)), workspace_limit)
-        return res, strand, info, counts
+        got = self._map_device(bases, cap, nb, counts, max_qlen, names, drift, min_votes,
+                               (int(match), int(mismatch), int(gap_open), int(gap_extend)), workspace_limit, ops)
+        return got[:3] + (counts,) + got[3:]
+
+
+def sam_records(index, res, strand, info, ops, names, queries=None):
+    """SAM lines of the rows of Index.map / map_paths (ops=True), one per read, by align.sam_records' field rules: RNAME is the
+    contig's name and POS the 1-based forward-strand position WITHIN the contig; a read without a contig gets FLAG 4.
+    align.sam_text(zip(index.names, index.lengths), records) adds the header.  queries: the reads' letters, or None for SEQ '*'
+    (ops.queries() fetches calls that never left the device: that is what this export is for)."""
+    n = ops.query_lengths()
+    out = []
+    for b in range(len(res)):
+        c = int(info['contig'][b])
+        row = res[b] if c >= 0 else np.zeros(9, dtype=np.int32)
+        out.append(align.sam_record(names[b] if names is not None else b, row, str(strand[b]), ops.codes(b), n[b],
+                                    index.names[c] if c >= 0 else '*', None if queries is None else queries[b]))
+    return out
 
 
 def samacc_rows(index, res, strand, info, query_lengths, names=None, min_coverage=0.6):
