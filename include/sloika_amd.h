@@ -621,7 +621,9 @@ SLK_API int slk_event_remap_labels_i32(const int32_t *path, const int64_t *ev_of
  * slk_softmax_xent_grad_f32: loss terms and dL/dlogits of train_network.py:128-136, in place over the logits written by
  *   slk_linear_rowstats_* (stats:[M][2] = max, 1/sum).  loss_rows[m] and correct_rows[m] are already divided by the
  *   number of counted positions (T - 2 drop) * B, so their sums are the data term of the loss and the accuracy.
- *   Columns nstate..ld-1 of every row are set to zero.  labels must lie in [0, nstate).
+ *   Columns nstate..ld-1 of every row are set to zero.  labels must lie in [0, nstate).  At min_prob == 0 a label whose posterior
+ *   underflows in float32 gives that row an infinite loss and a non-finite gradient, as the reference does (the other rows are not
+ *   affected); train_network.py's own default is above 0.
  * slk_reduce_sum_f32: out[0] = sum x (square = 0) or sum x^2 (square = 1: updates.param_sqr), float64, fixed order.
  * slk_gemm_tn_f32: C[N1][N2] (rows ldc apart) = A^T B, A:[M][N1] rows lda apart, B:[M][N2] rows ldb apart; when colsum is
  *   given it also receives the column sums of A (A^T 1: the bias gradient) from the same pass.
