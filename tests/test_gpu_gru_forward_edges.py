@@ -22,61 +22,12 @@ import numpy as np
 import pytest
 
 from tests import ref_gru_forward as rg
-from tests.gpu_util import dev, need_gpu, stream
+from tests.gpu_util import Out, dev, need_gpu, padded_input as _padded_input, stream
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
-PATTERN = np.uint32(0x7FC0BEEF)                # a quiet NaN with a payload nobody computes
 SHARE_CU = 1 << 10                             # include/sloika_amd.h: bit 10 of `reverse`
 DIRECTIONS = [False, True]
-
-
-def _nan_filled(shape):
-    return np.full(shape, PATTERN, np.uint32).view(np.float32)
-
-
-class Out:
-    """rows x width floats, rows ld apart, `lead` floats past a 16-byte boundary, PATTERN everywhere, GUARD floats on either side."""
-
-    def __init__(self, T, B, width, ld=None, lead=0):
-        self.T, self.B, self.width, self.ld, self.lead = T, B, width, ld or width, lead
-        self.buf = dev(_nan_filled(GUARD + lead + T * B * self.ld + GUARD))
-        assert self.buf.data_ptr() % 16 == 0
-
-    def ptr(self):
-        return self.buf.data_ptr() + 4 * (GUARD + self.lead)
-
-    def fetch(self):
-        self.host = self.buf.cpu().numpy().view(np.uint32)
-        return self
-
-    def body(self):
-        a = GUARD + self.lead
-        return self.host[a:a + self.T * self.B * self.ld].reshape(self.T, self.B, self.ld)
-
-    def values(self):
-        return np.ascontiguousarray(self.body()[:, :, :self.width]).view(np.float32)
-
-    def assert_untouched_outside(self, lens, what):
-        """Guards, gaps between rows, and every row at t >= lens[b]."""
-        a = GUARD + self.lead
-        assert (self.host[:a] == PATTERN).all() and (self.host[a + self.T * self.B * self.ld:] == PATTERN).all(), what + ": guard written"
-        body = self.body()
-        assert (body[:, :, self.width:] == PATTERN).all(), what + ": gap between rows written"
-        if lens is not None:
-            past = np.arange(self.T)[:, None] >= np.asarray(lens)[None, :]
-            assert (body[past] == PATTERN).all(), what + ": row past a chunk's end written"
-
-
-def _padded_input(a, lens, ld):
-    """[T][B][w] -> device [T][B][ld] with NaN in the gaps and in every row past a chunk's end."""
-    T, B, w = a.shape
-    host = _nan_filled((T, B, ld))
-    host[:, :, :w] = a
-    if lens is not None:
-        host[np.arange(T)[:, None] >= np.asarray(lens)[None, :]] = PATTERN.view(np.float32)
-    return dev(host)
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,5 +1,6 @@
 """csrc/lstm_fused16.hip -- a whole Lstm layer (sloika/layers.py:677-697: projection + scan) in one kernel -- through the C ABI,
-against the oracle (float32 C port, itself pinned to the reference's layers.py by tests/test_oracle_reference_layers.py)."""
+against the oracle (float32 C port, itself pinned to the reference's layers.py by tests/test_oracle_reference_layers.py).
+Time, batch and ragged edges and the float64 bounds of this kernel: tests/test_gpu_lstm_forward_edges.py."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,7 @@
 """GPU parity: Gru (MFMA 4x4x1 kernel and portable kernel) and Lstm vs the oracle, through the C ABI.
 
 Tolerance: 1e-4 absolute on layer outputs (BASELINE.json north_star); observed errors are ~1e-6.
+Time, batch and ragged edges and the float64 bounds of the Lstm kernels: tests/test_gpu_lstm_forward_edges.py.
 """
 import numpy as np
 import pytest
