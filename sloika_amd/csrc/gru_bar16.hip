@@ -36,7 +36,9 @@
 // 128 = chain waves without their share of the projection (no projection MFMAs, no outputs, no reads of the x operands: the bound of
 // what moving it to the service wave can gain), 256 / 512 = the service wave computes six / three of its tiles a second time, spread
 // over the intervals as a table for eighteen / fifteen tiles would spread them (whether it still reaches every barrier first:
-// design/gru_projection.md).
+// design/gru_projection.md), 1024 = the z products stay, the z picks and sigmoid(z), 1 - z, z*h are bit 64's constants (the bound of what
+// placing the z epilogue can gain), 2048 = the head of interval A without the vI and x-operand requests and without the stores: the
+// gate terms are constants (the bound of what moving them behind the own-block products can gain: design/gru_step_order.md).
 #ifdef SLK_DIAG
 __device__ unsigned long long slk_dbg_bar16[4][16];
 extern "C" SLK_API int slk_debug_read_bar16(unsigned long long *host_out)
@@ -223,6 +225,8 @@ static int launch_bar16(const float *x, long ldx, const float *iW, const float *
         DIAG_LAUNCH(16, false, 64) DIAG_LAUNCH(17, true, 64) DIAG_LAUNCH(18, false, 128) DIAG_LAUNCH(19, true, 128)
         DIAG_LAUNCH(20, false, 256) DIAG_LAUNCH(21, true, 256) DIAG_LAUNCH(22, false, 512) DIAG_LAUNCH(23, true, 512)
         DIAG_LAUNCH(24, false, 384) DIAG_LAUNCH(25, true, 384) DIAG_LAUNCH(26, false, 640) DIAG_LAUNCH(27, true, 640)
+        DIAG_LAUNCH(28, false, 1024) DIAG_LAUNCH(29, true, 1024) DIAG_LAUNCH(30, false, 2048) DIAG_LAUNCH(31, true, 2048)
+        DIAG_LAUNCH(32, false, 3072)
 #undef DIAG_LAUNCH
     }
 #endif

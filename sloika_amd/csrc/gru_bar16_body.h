@@ -257,13 +257,16 @@
         // One step = two intervals, each opened by a barrier; MFMAs are issued in an order that keeps the matrix pipe busy
         // through every LDS round trip and every stretch of gate arithmetic (an MFMA occupies the pipe for 16 cycles and
         // the issuing wave for 4):
-        //   A  [others' h(s-1) visible]  request the other K blocks, then vI(s), then the x operands of this step's share of the
-        //      projection; r products with my own block (already in registers) while they fly; r products with the others, tile 0
-        //      first; sigmoid(r), r*h, split, write, own block read back; ALL z products somewhere in this interval (NB_S, NB_E
-        //      below); this step's share of the projection behind the write (LATE; otherwise in the round trip at the start)
+        //   A  [others' h(s-1) visible]  request the other K blocks; r and z products with my own block (already in registers: they
+        //      wait for nothing) while those fly, and in the products' shadow the store of h(s-1), the pointer bumps, the requests
+        //      of vI(s) and of the x operands of this step's share of the projection (HEAD below; HEAD 0: all of that in front of
+        //      the first product); r products with the others, tile 0 first; sigmoid(r), r*h, split, write, own block read back;
+        //      ALL z products somewhere in this interval (NB_S, NB_E below); this step's share of the projection behind the write
+        //      (LATE; otherwise in the round trip at the start)
         //   B  [others' r*h visible]     request the other K blocks (not LATE: then the x operands of the next step's share of the
-        //      projection); candidate products with my own block, then sigmoid(z), 1 - z and z*h while they fly; candidate
-        //      products with the others (tile 0 first); tanh, blend, split, write, own block read back, store
+        //      projection); candidate products with my own block; candidate products with the others (tile 0 first) with the
+        //      picks of z, sigmoid(z), 1 - z and z*h among them, one MFMA to two vector instructions (ZEPI below; ZEPI 0: as one
+        //      block in front of them, while the others' r*h flies); tanh, blend, split, write, own block read back, store
         // The gate arithmetic reads the accumulators from inline asm (pick_sum_kept), where hipcc inserts no wait states, and the
         // hardware does not interlock a vector read of an MFMA result: seven wait states must lie between a
         // v_mfma_f32_16x16x32_f16 and the read (tools/probes/mfma_read_hazard_probe.hip).  Every tile's last MFMA is therefore
@@ -289,6 +292,20 @@
         // Three K blocks: own block at the start, the others under the epilogue -- twelve MFMAs behind the write keep the matrix pipe
         // busy past barrier B.  Two K blocks (the 64-wide layers): all eight behind the write; the measured best of five placements each.
         constexpr int NB_S = KBS == 2 ? 0 : 1, NB_E = KBS == 2 ? 0 : KBS;
+        // What stands between barrier A and the first MFMA, and how the z epilogue shares interval B with the candidate's products
+        // (design/gru_step_order.md).  The own-block products wait for nothing but `oh`, which the wave read back before the barrier:
+        //   HEAD 0  state requests, store of h(s-1), pointer bumps, vI(s) and x-operand requests, THEN the own-block r and z products;
+        //   HEAD 1  state requests, own-block r and z products, then stores, bumps and requests in the products' shadow;
+        //   HEAD 2  state requests, vI(s) and x-operand requests, own-block products, then stores and bumps;
+        //   ZEPI 0  sigmoid(z), 1 - z, z*h as one block between the candidate's own-block products and those of the other blocks;
+        //   ZEPI 1  among the other blocks' products, one MFMA to two vector instructions.
+        // Measured per instantiation (the note's section 2; the variants not kept: tools/experiments/gru_step_order_variants.patch.txt):
+        // the layers whose chain waves project behind the write (LATE) take ZEPI 1, and HEAD 1 inside the stack kernel, HEAD 2 as a
+        // launch of their own.  The 64-wide layers have four other-block candidate MFMAs, too few to hide an epilogue under, and four K
+        // blocks of input keep the projection in the round trip the head would give to the own-block products: both stay at 0.
+        constexpr int HEAD = LATE ? (PACKED ? 1 : 2) : 0;
+        constexpr int ZEPI = LATE ? 1 : 0;
+        constexpr bool NOHEAD = (ABL & 2048) != 0;       // diagnostic: no stores, no vI or x-operand requests (constants instead)
         auto step = [&](auto PHC, const int s, const int G) {
             constexpr int ph = decltype(PHC)::value;
             constexpr bool PROJ = CT > 0 && ph < KBLK && !(ABL & 128);
@@ -300,31 +317,48 @@
 #pragma unroll
             for (int i = 1; i < KBS; i++) bh[i] = ldH(h_img, moff[i]);       // what the step waits for is requested first
             __builtin_amdgcn_sched_barrier(0);
-            if (s > 0) {                                 // h(s-1): still in `hold`
-                if (live && s - 1 < Tc && !(ABL & 16)) {
-                    hp[0] = hold[0];
-                    hp[16] = hold[1];
-                    if constexpr (SAVE) { zp[0] = zkeep[0]; zp[16] = zkeep[1]; }
-                }
-                hp += hstep;
-                if constexpr (SAVE) zp += zstep;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // vI(s): complete since the previous barrier at the latest (the service waves use every interval)
-            const float *vcur = vbuf + (s % R) * VSTEP + voff;
             float vz[2], vr[2], vc[2];
+            [[maybe_unused]] auto put_h = [&]() {        // h(s-1): still in `hold`
+                if (s > 0) {
+                    if (live && s - 1 < Tc && !(ABL & 16) && !NOHEAD) {
+                        hp[0] = hold[0];
+                        hp[16] = hold[1];
+                        if constexpr (SAVE) { zp[0] = zkeep[0]; zp[16] = zkeep[1]; }
+                    }
+                    hp += hstep;
+                    if constexpr (SAVE) zp += zstep;
+                }
+            };
+            // vI(s): complete since the previous barrier at the latest (the service waves use every interval); never asked for in
+            // front of barrier A -- vI(4G) is only complete there
+            [[maybe_unused]] auto ask_v = [&]() {
+                if constexpr (NOHEAD) {
+                    vz[0] = vz[1] = vr[0] = vr[1] = vc[0] = vc[1] = 0.125f;
+                } else {
+                    const float *vcur = vbuf + (s % R) * VSTEP + voff;
 #pragma unroll
-            for (int p = 0; p < 2; p++) {
-                vr[p] = vcur[64 * (NT + 2 * w + p)];
-                vz[p] = vcur[64 * (2 * w + p)];
-                vc[p] = vcur[64 * (2 * NT + 2 * w + p)];
+                    for (int p = 0; p < 2; p++) {
+                        vr[p] = vcur[64 * (NT + 2 * w + p)];
+                        vz[p] = vcur[64 * (2 * w + p)];
+                        vc[p] = vcur[64 * (2 * NT + 2 * w + p)];
+                    }
+                    if constexpr (LATE && PROJ) {        // x operands of my share, K block ph of group G+1 (split a group ago): behind h and vI
+                        const int ob = ((G + 1) & 1) * OPIMG + poff + 64 * ph;
+                        pxh = ldH(xop_hi, ob);
+                        pxl = ldH(xop_lo, ob);
+                    }
+                }
+            };
+            if constexpr (HEAD == 0) {
+                put_h();
+                __builtin_amdgcn_sched_barrier(0);
+                ask_v();
+                __builtin_amdgcn_sched_barrier(0);
+            } else if constexpr (HEAD == 2) {
+                ask_v();
+                __builtin_amdgcn_sched_barrier(0);
             }
-            if constexpr (LATE && PROJ) {                // x operands of my share, K block ph of group G+1 (split a group ago): behind h and vI
-                const int ob = ((G + 1) & 1) * OPIMG + poff + 64 * ph;
-                pxh = ldH(xop_hi, ob);
-                pxl = ldH(xop_lo, ob);
-            }
-            __builtin_amdgcn_sched_barrier(0);
+            BSTAMP(8)
             f32x4 accR[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
             mfma2(wr_hi[0][0], wr_lo[0][0], bh[0], accR[0]);
             mfma2(wr_hi[1][0], wr_lo[1][0], bh[0], accR[1]);
@@ -347,6 +381,17 @@
                 for (int i = 0; i < NB_S; i++) {
                     mfma2(wz_hi[0][i], wz_lo[0][i], bh[i], accZ[0]);
                     mfma2(wz_hi[1][i], wz_lo[1][i], bh[i], accZ[1]);
+                }
+            }
+            if constexpr (HEAD != 0) {
+                // the own-block products in front of everything below (the statements hand the accumulators on: see the r products)
+                asm volatile("" : "+v"(accR[0]), "+v"(accR[1]));
+                if constexpr (NB_S > 0 && !(ABL & 64)) asm volatile("" : "+v"(accZ[0]), "+v"(accZ[1]));
+                __builtin_amdgcn_sched_barrier(0);
+                put_h();
+                if constexpr (HEAD == 1) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    ask_v();
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -434,10 +479,20 @@
             // everything below -- sigmoid(z) and the other blocks' candidate products -- behind these four MFMAs
             asm volatile("" : "+v"(accC[0]), "+v"(accC[1]));
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (ZEPI != 0) { BSTAMP(5) }                            // (a stamp is a fence: not between the epilogue and its MFMAs)
             float zz[2], omz[2], zh[2];
-            if constexpr (ABL & 64) {                                         // no update gate: the blend takes constants
+            if constexpr (ABL & (64 | 1024)) {                              // no update gate (1024: its products stay): the blend takes constants
                 zz[0] = zz[1] = omz[0] = omz[1] = 0.5f;
                 zh[0] = zh[1] = 0.25f;
+            } else if constexpr (ZEPI != 0) {
+                // the same picks and the same two chains, side by side, but no fence behind them: they are spread among the other
+                // blocks' products below
+                pick_sum_kept<1>(accZ[0], pk0, accC[1][0]);
+                pick_sum_kept<1>(accZ[1], pk1, accC[1][0]);
+                zz[0] = (ABL & 4) ? fmaf(pk0, inv_z[0], vz[0]) * 0.01f : sigmoid4(fmaf(pk0, inv_z[0], vz[0]));
+                zz[1] = (ABL & 4) ? fmaf(pk1, inv_z[1], vz[1]) * 0.01f : sigmoid4(fmaf(pk1, inv_z[1], vz[1]));
+#pragma unroll
+                for (int p = 0; p < 2; p++) { omz[p] = 1.0f - zz[p]; zh[p] = zz[p] * hold[p]; }
             } else {
                 // sigmoid(z) while the other blocks of r*h are on their way from LDS.  `after` keeps the picks behind the candidate's four
                 // own-block MFMAs, and those behind barrier B.  The z MFMAs behind the write are pinned in front of the barrier; the
@@ -453,7 +508,7 @@
                 asm volatile("" : "+v"(zh[0]), "+v"(omz[0]), "+v"(zh[1]), "+v"(omz[1]), "+v"(pk0), "+v"(pk1));
                 __builtin_amdgcn_sched_barrier(0);
             }
-            BSTAMP(5)
+            if constexpr (ZEPI == 0) { BSTAMP(5) }
 #pragma unroll
             for (int i = 1; i < KBS; i++) mfma2(wc_hi[0][i], wc_lo[0][i], ch[i], accC[0]);
             asm volatile("" : "+v"(accC[0]));                                // as above: tile 0's sum before tile 1's
@@ -461,7 +516,21 @@
 #pragma unroll
             for (int i = 1; i < KBS; i++) mfma2(wc_hi[1][i], wc_lo[1][i], ch[i], accC[1]);
             asm volatile("" : "+v"(accC[1]));
+            if constexpr (ZEPI != 0 && !(ABL & (64 | 1024))) {
+                // one MFMA, then two of the z epilogue's vector instructions, for as long as both last: the wave issues for 4 of the 16
+                // cycles an MFMA keeps the pipe
+#pragma unroll
+                for (int i = 0; i < 4 * (KBS - 1); i++) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+                }
+            }
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (ZEPI != 0 && !(ABL & (64 | 1024))) {
+                // (behind the products: in front of them it would be a fence for the epilogue)
+                asm volatile("" : "+v"(zh[0]), "+v"(omz[0]), "+v"(zh[1]), "+v"(omz[1]), "+v"(pk0), "+v"(pk1));
+                __builtin_amdgcn_sched_barrier(0);
+            }
             BSTAMP(6)
             float hn[2];
             {

@@ -50,16 +50,19 @@ for I, n in shapes:
     for code, nm in ((2, "no s_barrier"), (3, "chain: no MFMAs"), (4, "cheap activations"), (5, "service waves idle"), (6, "no h_out stores"),
                      (7, "no s_barrier + service idle"), (8, "no s_barrier + no chain MFMAs"), (9, "no barrier, no chain MFMAs, service idle"), (10, "everything off"),
                      (16, "chain: no z products, no z epilogue"), (18, "chain: no projection share"),
+                     (28, "chain: z products, no z epilogue"), (30, "chain: head of A without requests and stores"),
+                     (32, "chain: no z epilogue + head without requests and stores"),
                      (20, "service: six tiles twice"), (22, "service: three tiles twice"),
                      (24, "chain: no projection share + service: six tiles twice"),
                      (26, "chain: no projection share + service: three tiles twice")):
         ms = timeit_code(code)
         print("   %-56s %6.0f" % (nm, ms * 1e6 / T * 2.4))
     L.slk_debug_read_bar16.argtypes = [ctypes.c_void_p]
-    names = ["barrier A", "reads + own z block + wait h", "r MFMAs", "z MFMAs + r epilogue + write + projection MFMAs", "barrier B",
-             "reads + own c block + z epilogue + wait r*h", "c MFMAs", "tanh, blend, split, writes, stores"]
+    names = ["barrier A", "head of A up to the first MFMA", "own r and z blocks (+ what the head defers) + wait h", "r MFMAs", "z MFMAs + r epilogue + write + projection MFMAs", "barrier B",
+             "reads + own c block + wait r*h (+ z epilogue where it is one block)", "c MFMAs (+ z epilogue where it is spread among them)", "tanh, blend, split, writes, stores"]
     for code, what in ((1, "production"), (17, "no z products, no z epilogue (results garbage)"),
-                       (19, "chain: no projection share (results garbage)"), (21, "service: six tiles twice"),
+                       (19, "chain: no projection share (results garbage)"),
+                       (29, "z products, no z epilogue (results garbage)"), (31, "head of A without requests and stores (results garbage)"), (21, "service: six tiles twice"),
                        (23, "service: three tiles twice"), (25, "chain: no projection share + service: six tiles twice (results garbage)"),
                        (27, "chain: no projection share + service: three tiles twice (results garbage)")):
         L.slk_gru_bar16_f32(x.data_ptr(), I, iW.data_ptr(), sW.data_ptr(), sW2.data_ptr(), bb.data_ptr(), y.data_ptr(), n, T, B, I, n, 2 * code, 1, 2, None, None, st)
@@ -70,9 +73,9 @@ for I, n in shapes:
         for wv in range(4):
             v = [stp[wv * 16 + i] / T for i in range(16)]
             if wv < n // 32:
-                print("chain wave %d: cycles per step, total %.0f" % (wv, sum(v[:8])))
-                for i, nm in enumerate(names):
-                    print("   %-48s %7.0f" % (nm, v[i]))
+                print("chain wave %d: cycles per step, total %.0f" % (wv, sum(v[:9])))
+                for i, nm in zip((0, 8, 1, 2, 3, 4, 5, 6, 7), names):       # stamp 8 splits section 1 at the first MFMA
+                    print("   %-72s %7.0f" % (nm, v[i]))
             else:
                 print("service wave %d: cycles per GROUP: work per interval %s   barrier wait per interval %s" % (
                     wv, " ".join("%5.0f" % (4 * a) for a in v[:8]), " ".join("%5.0f" % (4 * a) for a in v[8:])))
