@@ -676,11 +676,9 @@ def _remap_many_device(refs, evs, min_prob, kmer_len, prior, slip, network, name
     seqs = [q for _, q in refk]
     nev = [c.shape[1] for c in cols]
     ev_off = np.concatenate([[0], np.cumsum(nev)]).astype(np.int64)
-    # the features of all reads in one launch, straight into the zero-padded network input (pipeline.Basecaller._call_event_pass)
-    dcols, off = features.upload_tables([{"mean": c[0], "stdv": c[1], "length": c[2]} for c in cols], '')
-    x = torch.zeros((max(nev), n, 4), dtype=torch.float32, device=dcols.device)
-    features.launch(dcols, off[:-1], nev, nev, np.arange(n), x, 4 * n, normalise=True)
-    post, steps = pipeline.Basecaller(net, kmer_len=kmer_len, min_prob=min_prob)._ragged_posterior(lambda ctx: x, nev)
+    # the features of all reads in one launch, straight into the zero-padded network input
+    x = features.network_input([{"mean": c[0], "stdv": c[1], "length": c[2]} for c in cols], nev)
+    post, steps = pipeline.Basecaller(net, kmer_len=kmer_len, min_prob=min_prob)._ragged_run(x, nev)
     if post.dim() != 3 or post.shape[1] != n or steps.cpu().numpy().tolist() != nev:
         raise ValueError("remap needs one network step per event: this network changes the number of steps")
     if post.stride(2) != 1:

@@ -76,6 +76,17 @@ def launch(cols, seg_start, seg_len, seg_keep, out_row, out, ld_out, normalise=T
     return out
 
 
+def network_input(tables, nev, first=0, tag=''):
+    """The features of many event tables in one upload and one launch, studentised per table, straight into the zero-padded
+    [max(nev), B, 4] network input: table b's events first .. first + nev[b] - 1 become column b."""
+    import torch
+    from . import device as D
+    cols, off = upload_tables(tables, tag)
+    B = len(tables)
+    x = D.scratch((max(nev), B, 4), torch.float32, cols.device).zero_()
+    return launch(cols, off[:-1] + first, nev, nev, np.arange(B), x, 4 * B, normalise=True)
+
+
 def from_events(ev, tag='scaled_', normalise=True, nanonet=False, device=False):
     """Create a matrix of features from an event table (features.py:6-32).
 

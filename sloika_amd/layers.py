@@ -154,6 +154,29 @@ class _PlanHints(__import__("threading").local):
     #: of chunks called differently) -- so that what a chunk is called does not depend on batch size or batches in flight
     deterministic = False
 
+    def override(self, **fields):
+        """`with _HINTS.override(in_flight=2, ...):` sets the named fields for the block and puts back what they held when it ends,
+        exceptions included."""
+        return _HintOverride(self, fields)
+
+
+class _HintOverride(object):
+    """(a plain class, not a generator: it is entered once per forward pass, and a pass at batch 256 is short)"""
+    __slots__ = ("hints", "fields", "saved")
+
+    def __init__(self, hints, fields):
+        self.hints, self.fields = hints, fields
+
+    def __enter__(self):
+        self.saved = [(k, getattr(self.hints, k)) for k in self.fields]       # (a name that is no hint raises before anything is set)
+        for k, v in self.fields.items():
+            setattr(self.hints, k, v)
+
+    def __exit__(self, *exc):
+        for k, v in self.saved:
+            setattr(self.hints, k, v)
+        return False
+
 
 _HINTS = _PlanHints()
 
@@ -371,6 +394,19 @@ class _RaggedMeta(type):
         _RaggedMeta._tls.current = value
 
 
+def ragged_lengths(lengths):
+    """The step counts of a ragged batch as `ragged` keeps them, a contiguous int32 device tensor [B] -- for what needs them before
+    the network runs (the per-read normalisation); handing the result to `ragged` costs nothing more."""
+    import torch
+    from . import device as D
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        # lengths that were computed on the device (pipeline.Basecaller's streamed whole-read mode) stay there
+        if lengths.dtype != torch.int32 or lengths.dim() != 1:
+            raise ValueError("ragged lengths on the device must be a 1-D int32 tensor")
+        return lengths.contiguous()
+    return torch.as_tensor(np.ascontiguousarray(lengths, dtype=np.int32)).to(D.device())
+
+
 class ragged(object, metaclass=_RaggedMeta):
     """Context for a ragged batch: `with ragged(lengths): net.run(x)` runs a zero-padded batch [T, B, F] whose chunk b is
     only lengths[b] steps long (whole reads of different lengths).  Time-local layers are unaffected (they compute the
@@ -380,15 +416,7 @@ class ragged(object, metaclass=_RaggedMeta):
     the network on this host thread, or None."""
 
     def __init__(self, lengths):
-        import torch
-        from . import device as D
-        if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
-            # lengths that were computed on the device (pipeline.Basecaller's streamed whole-read mode) stay there
-            if lengths.dtype != torch.int32 or lengths.dim() != 1:
-                raise ValueError("ragged lengths on the device must be a 1-D int32 tensor")
-            self.lengths = lengths.contiguous()
-        else:
-            self.lengths = torch.as_tensor(np.ascontiguousarray(lengths, dtype=np.int32)).to(D.device())
+        self.lengths = ragged_lengths(lengths)
 
     def __enter__(self):
         self.saved, ragged.current = ragged.current, self.lengths
@@ -1267,9 +1295,7 @@ class Parallel(Layer):
             main = torch.cuda.current_stream(x.device)
             ready = torch.cuda.Event()
             ready.record(main)
-            keep = _HINTS.gru_side
-            _HINTS.gru_side = side
-            try:
+            with _HINTS.override(gru_side=side):
                 for i, layer in enumerate(self.layers):
                     st = main if i == 0 else streams[i - 1]
                     if st is not main:
@@ -1281,8 +1307,6 @@ class Parallel(Layer):
                         done.record(st)
                         main.wait_event(done)
                     off += layer.size
-            finally:
-                _HINTS.gru_side = keep
             return outs
         cat = torch.cat([layer._forward(x, None, reverse) for layer in self.layers], dim=2)
         if out is not None:

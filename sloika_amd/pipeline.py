@@ -7,12 +7,15 @@ This is the batched restatement of bin/basecall_network.py `raw` (sloika/basecal
 BASELINE.json's metric is quoted on.  All arithmetic happens in the HIP kernels behind include/sloika_amd.h;
 torch only owns the buffers and the stream.
 """
+import contextlib
 import os
 import sys
 
 import numpy as np
 
 from . import _lib, batch, decode, layers
+
+_NO_ARENA = contextlib.nullcontext()
 
 
 class Basecaller(object):
@@ -104,13 +107,52 @@ class Basecaller(object):
         else:
             x = batch.normalise_chunks(cd, self.normalisation, out_layout='network')
             rest = seq[:upto]
-        keep = layers._HINTS.in_flight, layers._HINTS.deterministic       # (thread local: one forward pass per host thread at a time)
-        layers._HINTS.in_flight, layers._HINTS.deterministic = self.in_flight, self.deterministic
-        try:
-            x = layers.run_layers(rest, x)
-        finally:
-            layers._HINTS.in_flight, layers._HINTS.deterministic = keep
-        return x
+        return self._forward(rest, x, self.in_flight)[0]
+
+    def _scope(self):
+        """What a pass runs inside: the arena its buffers come out of (borrow=True), or nothing.  Every public entry enters it ONCE per
+        pass and nothing below does: Arena.__enter__ begins a pass, which rotates the result generation."""
+        return _NO_ARENA if self._arena is None else self._arena
+
+    def _forward(self, seq, x, in_flight, lengths=None):
+        """The layers `seq` on the [T, B, features] device tensor x under this Basecaller's plan hints: -> (output, None).  With
+        `lengths`, the per-column step counts of a zero-padded batch (layers.ragged): -> (output, int32 device tensor of the columns'
+        output steps)."""
+        # (the hints are thread local: one forward pass per host thread at a time)
+        with layers._HINTS.override(in_flight=in_flight, deterministic=self.deterministic):
+            if lengths is None:
+                return layers.run_layers(seq, x), None
+            with layers.ragged(lengths):
+                x = layers.run_layers(seq, x)
+                return x, layers.ragged.current.contiguous()
+
+    def _ragged_run(self, x, lengths, upto=None):
+        """The network up to (not including) layer index `upto` -- None: all of it, Softmax.run included -- on the zero-padded
+        [T, B, features] input x with per-read step counts: -> (output [T', B, .], int32 device tensor of the reads' output steps)."""
+        # ragged batches side by side keep the four-chunk plan: their workgroups queue for the CUs and a batch of short reads hands its
+        # CUs on early, which a plan that packs more chunks into fewer, slower workgroups would not let it do
+        return self._forward(self.network.layers[:upto], x, 1, lengths)
+
+    def _call_ragged(self, x, lengths, fused=True):
+        """Network and decoder on the zero-padded [T, B, features] input x with per-read step counts -> (scores, paths, lens)."""
+        if not self.transducer:
+            return self._decode_profile(*self._ragged_run(x, lengths))
+        hid, steps = self._ragged_run(x, lengths, -1)
+        return self._decode(self.network.layers[-1], hid, steps, fused=fused)
+
+    def _decode(self, last, hid, lengths=None, lp_dump=None, fused=True):
+        """The transducer decoder behind the hidden state `hid` that the Softmax layer `last` takes: csrc/softmax_viterbi.hip where
+        it applies and `fused` lets it, else the layer's logits + row statistics.  lengths: None or the columns' steps (int32, device).
+        -> (scores, paths, lens)."""
+        packed = self._fused_pack(last, hid) if fused else None
+        if packed is not None:
+            return decode.viterbi_fused_batch(packed[1], packed[0], self.kmer_len, skip_pen=self.skip, nbase=self.nbase,
+                                              min_prob=self.min_prob, workspace=self._ws, lengths=lengths, lp_dump=lp_dump)
+        if lp_dump is not None:
+            raise ValueError("lp_dump needs the fused decoder (csrc/softmax_viterbi.hip does not cover this network)")
+        logits, stats, ld = last.logits_and_stats(hid)
+        return decode.viterbi_logits_batch(logits, stats, self.kmer_len, hid.shape[0], hid.shape[1], ld=ld, skip_pen=self.skip,
+                                           nbase=self.nbase, min_prob=self.min_prob, workspace=self._ws, lengths=lengths)
 
     def posteriors(self, chunks, scaling=None):
         """[B, chunk_len] device signal -> [T', B, nstate] posteriors (network layout).  `scaling`: as in call_chunks."""
@@ -160,53 +202,24 @@ class Basecaller(object):
         device tensor [T', B, nstate], then receives the log-posteriors the dynamic programme consumed (tests).  Otherwise
         (and with fused_decode=False) the decoder consumes the layer's logits + row statistics, bit-identical to decoding
         `posteriors()`."""
-        if self._arena is None:
-            return self._call_chunks(chunks, lp_dump, scaling)
-        with self._arena:
-            return self._call_chunks(chunks, lp_dump, scaling)
+        with self._scope():
+            if not self.transducer:
+                if lp_dump is not None:
+                    raise ValueError("lp_dump belongs to the fused transducer decoder")
+                return self._decode_profile(self.posteriors(chunks, scaling), None)
+            net = self.network
+            last = net.layers[-1] if isinstance(net, layers.Serial) else None
+            if type(last) is layers.Softmax and len(net.layers) > 1:
+                return self._decode(last, self._hidden(chunks, len(net.layers) - 1, scaling), lp_dump=lp_dump)
+            post = self.posteriors(chunks, scaling)
+            return decode.viterbi_batch(post, self.kmer_len, skip_pen=self.skip, nbase=self.nbase,
+                                        min_prob=self.min_prob, workspace=self._ws)
 
     def _decode_profile(self, post, lengths):
         """basecall.decode_post(transducer=False) over the batch axis of a materialised posterior [T, B, nstate]."""
         from . import olddecode
         return olddecode.decode_post_batch(post, self.kmer_len, bad=self.bad, min_prob=self.min_prob, trans=self.trans, lengths=lengths,
                                            nbase=self.nbase, workspace=self._ws)
-
-    def _ragged_posterior(self, first, lengths):
-        """The whole network, Softmax.run included, on the zero-padded [T, B, features] input `first(ragged context)` returns, with
-        per-read step counts (layers.ragged): -> (posterior [T', B, nstate], int32 device tensor of the reads' output steps)."""
-        keep = layers._HINTS.in_flight, layers._HINTS.deterministic
-        layers._HINTS.in_flight, layers._HINTS.deterministic = 1, self.deterministic
-        try:
-            with layers.ragged(lengths) as ctx:
-                x = first(ctx)
-                x = layers.run_layers(self.network.layers, x)
-                out_lengths = layers.ragged.current.contiguous()
-        finally:
-            layers._HINTS.in_flight, layers._HINTS.deterministic = keep
-        return x, out_lengths
-
-    def _call_chunks(self, chunks, lp_dump, scaling):
-        if not self.transducer:
-            if lp_dump is not None:
-                raise ValueError("lp_dump belongs to the fused transducer decoder")
-            return self._decode_profile(self.posteriors(chunks, scaling), None)
-        net = self.network
-        last = net.layers[-1] if isinstance(net, layers.Serial) else None
-        if type(last) is layers.Softmax and len(net.layers) > 1:
-            hid = self._hidden(chunks, len(net.layers) - 1, scaling)
-            packed = self._fused_pack(last, hid)
-            if packed is not None:
-                return decode.viterbi_fused_batch(packed[1], packed[0], self.kmer_len, skip_pen=self.skip, nbase=self.nbase,
-                                                  min_prob=self.min_prob, workspace=self._ws, lp_dump=lp_dump)
-            if lp_dump is not None:
-                raise ValueError("lp_dump needs the fused decoder (csrc/softmax_viterbi.hip does not cover this network)")
-            logits, stats, ld = last.logits_and_stats(hid)
-            T, B = hid.shape[0], hid.shape[1]
-            return decode.viterbi_logits_batch(logits, stats, self.kmer_len, T, B, ld=ld, skip_pen=self.skip,
-                                               nbase=self.nbase, min_prob=self.min_prob, workspace=self._ws)
-        post = self.posteriors(chunks, scaling)
-        return decode.viterbi_batch(post, self.kmer_len, skip_pen=self.skip, nbase=self.nbase,
-                                    min_prob=self.min_prob, workspace=self._ws)
 
     _BATCH_STREAMS = {}
 
@@ -346,51 +359,17 @@ class Basecaller(object):
                     raise ValueError("k-mer states must lie in 0 .. %d" % (self.nbase ** self.kmer_len - 1))
             cols.append(st + 1)                                 # column 0 is the blank (variables.nstate, transducer=True)
 
-        def run():
+        with self._scope():
             post = self.posteriors(chunks, scaling)
             return decode.forwards_batch(post, cols, full=full, blank=0, min_prob=self.min_prob)
-        if self._arena is None:
-            return run()
-        with self._arena:
-            return run()
 
     def _call_padded(self, padded, nsamp):
         """One padded batch of trimmed reads resident on the device ([B, Lmax], read b in its first nsamp[b] samples): per-read
         normalisation, network and decoder with per-read lengths.  -> (scores, paths, lens) on the device."""
-        if self._arena is None:
-            return self._call_padded_pass(padded, nsamp)
-        with self._arena:
-            return self._call_padded_pass(padded, nsamp)
-
-    def _call_padded_pass(self, padded, nsamp):
-        if not self.transducer:
-            # per-read normalisation (basecall.py:117-118), network, decoder with per-read lengths
-            return self._decode_profile(*self._ragged_posterior(lambda ctx: batch.normalise_reads_ragged(padded, ctx.lengths), nsamp))
-        net = self.network
-        B = padded.shape[0]
-        keep = layers._HINTS.in_flight, layers._HINTS.deterministic
-        # ragged batches side by side keep the four-chunk plan: their workgroups queue for the CUs and a batch of short reads hands its
-        # CUs on early, which a plan that packs more chunks into fewer, slower workgroups would not let it do
-        layers._HINTS.in_flight, layers._HINTS.deterministic = 1, self.deterministic
-        try:
-            with layers.ragged(nsamp) as ctx:
-                x = batch.normalise_reads_ragged(padded, ctx.lengths)      # per-read normalisation (basecall.py:117-118)
-                hid = layers.run_layers(net.layers[:-1], x)
-                lengths = layers.ragged.current
-                packed = self._fused_pack(net.layers[-1], hid)
-                pack = packed[0] if packed is not None else None
-                if pack is None:
-                    logits, stats, ld = net.layers[-1].logits_and_stats(hid)
-                else:
-                    hid = packed[1]
-        finally:
-            layers._HINTS.in_flight, layers._HINTS.deterministic = keep
-        T = hid.shape[0]
-        if pack is not None:
-            return decode.viterbi_fused_batch(hid, pack, self.kmer_len, skip_pen=self.skip, nbase=self.nbase,
-                                              min_prob=self.min_prob, workspace=self._ws, lengths=lengths.contiguous())
-        return decode.viterbi_logits_batch(logits, stats, self.kmer_len, T, B, ld=ld, skip_pen=self.skip, nbase=self.nbase,
-                                           min_prob=self.min_prob, workspace=self._ws, lengths=lengths.contiguous())
+        with self._scope():
+            lengths = layers.ragged_lengths(nsamp)
+            # per-read normalisation (basecall.py:117-118)
+            return self._call_ragged(batch.normalise_reads_ragged(padded, lengths), lengths)
 
     def call_reads(self, signals, trim=(0, 0), open_pore_fraction=0.0, scaling=None):
         """Whole reads of different lengths in ONE batch (the reference calls them one at a time, basecall.py:88-121):
@@ -447,8 +426,13 @@ class Basecaller(object):
             dev = D.device()
             return (torch.full((ntab,), float("nan"), device=dev), torch.full((ntab, 0), -1, dtype=torch.int32, device=dev),
                     torch.zeros((ntab,), dtype=torch.int32, device=dev), nev)
-        scores, paths, lens = self._call_event_batch([{"mean": cols[r][0], "stdv": cols[r][1], "length": cols[r][2]} for r in good],
-                                                     [nev[r] for r in good], int(trim[0]))
+        kept = [nev[r] for r in good]
+        with self._scope():
+            # table good[b]'s events trim[0] .. trim[0] + kept[b] - 1 become column b.  Never the fused kernel: the events' contract is
+            # the decoder that reads the Softmax layer's logits, which is bit for bit basecall.decode_post on the posterior
+            x = features.network_input([{"mean": cols[r][0], "stdv": cols[r][1], "length": cols[r][2]} for r in good], kept,
+                                       int(trim[0]))
+            scores, paths, lens = self._call_ragged(x, kept, fused=False)
         if len(good) == ntab:
             return scores, paths, lens, nev
         idx = torch.as_tensor(good, device=scores.device)
@@ -457,35 +441,6 @@ class Basecaller(object):
         all_lens = torch.zeros((ntab,), dtype=lens.dtype, device=scores.device)
         all_scores[idx], all_paths[idx], all_lens[idx] = scores, paths, lens
         return all_scores, all_paths, all_lens, nev
-
-    def _call_event_batch(self, tables, nev, skip_events):
-        if self._arena is None:
-            return self._call_event_pass(tables, nev, skip_events)
-        with self._arena:
-            return self._call_event_pass(tables, nev, skip_events)
-
-    def _call_event_pass(self, tables, nev, skip_events):
-        """call_events on tables that can be called: table b's events skip_events .. skip_events + nev[b] - 1 become column b."""
-        import torch
-        from . import device as D, features
-        net = self.network
-        B, tmax = len(tables), max(nev)
-        cols, off = features.upload_tables(tables, '')
-        x = D.scratch((tmax, B, 4), torch.float32, cols.device).zero_()
-        features.launch(cols, off[:-1] + skip_events, nev, nev, np.arange(B), x, 4 * B, normalise=True)
-        if not self.transducer:
-            return self._decode_profile(*self._ragged_posterior(lambda ctx: x, nev))
-        keep = layers._HINTS.in_flight, layers._HINTS.deterministic
-        layers._HINTS.in_flight, layers._HINTS.deterministic = 1, self.deterministic
-        try:
-            with layers.ragged(nev):
-                hid = layers.run_layers(net.layers[:-1], x)
-                lengths = layers.ragged.current
-                logits, stats, ld = net.layers[-1].logits_and_stats(hid)
-        finally:
-            layers._HINTS.in_flight, layers._HINTS.deterministic = keep
-        return decode.viterbi_logits_batch(logits, stats, self.kmer_len, hid.shape[0], B, ld=ld, skip_pen=self.skip, nbase=self.nbase,
-                                           min_prob=self.min_prob, workspace=self._ws, lengths=lengths.contiguous())
 
     @staticmethod
     def _transducer_only(kwargs, what):
@@ -587,11 +542,18 @@ class Basecaller(object):
                 ev = torch.cuda.Event()
                 ev.record(s)
             pending.append((idx, host, ev, res))
+        return cls._collect_reads(pending, nreads)
+
+    @staticmethod
+    def _collect_reads(pending, nreads):
+        """Waits for every queued batch -- (read indices, its results on their way to the host: scores, paths, lens first, the event
+        behind them, the device tensors they are copied from) -- and hands each read its own: -> (scores [nreads] float32, NaN for a
+        read in no batch; list of nreads int32 path arrays, None for such a read)."""
         scores = np.full(nreads, np.nan, dtype=np.float32)
         paths = [None] * nreads
-        for idx, host, ev, res in pending:
+        for idx, host, ev, _ in pending:
             ev.synchronize()
-            sc, pa, le = (h.numpy() for h in host)
+            sc, pa, le = (h.numpy() for h in host[:3])
             for j, i in enumerate(idx):
                 scores[i] = sc[j]
                 paths[i] = pa[j, :le[j]].copy()
@@ -676,7 +638,7 @@ class Basecaller(object):
         sigs = [signals[i] for i in order]
         strides, off = batch.read_layout([raw[i] for i in order], window_size)
         assert trim[0] >= 0 and trim[1] >= 0
-        pending, lo = [], 0
+        pending, widths, lo = [], [], 0
         with concurrent.futures.ThreadPoolExecutor(min(8, os.cpu_count() or 1)) as pool, \
                 batch.staging(int(off[-1]), dtype, up) as buf:
             hv = buf.numpy()
@@ -713,22 +675,22 @@ class Basecaller(object):
                     host = tuple(t.to("cpu", non_blocking=True) for t in res + (ln, fl))
                     ev = torch.cuda.Event()
                     ev.record(lane)
-                pending.append((idx, host, ev, res, lmax))
+                pending.append((idx, host, ev, res))
+                widths.append(lmax)
                 lo = hi
-        scores = np.full(nread, np.nan, dtype=np.float32)
-        paths = [None] * nread
+        scores, paths = cls._collect_reads(pending, nread)
+        # the trimmed lengths and the flags came down behind the results; a read that failed on the device has neither score nor path
         nsamp = [0] * nread
-        for idx, host, ev, res, lmax in pending:
-            ev.synchronize()
-            sc, pa, le, ns, fb = (h.numpy() for h in host)
+        for idx, host, _, _ in pending:
+            ns, fb = host[3].numpy(), host[4].numpy()
             for j, i in enumerate(idx):
                 flags[i] = int(fb[j])
-                if not flags[i]:
+                if flags[i]:
+                    scores[i], paths[i] = np.nan, None
+                else:
                     nsamp[i] = int(ns[j])
-                    scores[i] = sc[j]
-                    paths[i] = pa[j, :le[j]].copy()
         cls._report_failures(flags)
-        return scores, paths, nsamp, len(buckets), sum(lmax * len(idx) for idx, _, _, _, lmax in pending)
+        return scores, paths, nsamp, len(buckets), sum(w * len(p[0]) for w, p in zip(widths, pending))
 
     def call_chunks_host(self, chunks):
         scores, paths, lens = self.call_chunks(chunks)

@@ -75,3 +75,28 @@ def test_parallel_decides_its_side_plan_and_stores_nothing(table, narrow):
     finally:
         layers._HINTS.in_flight = keep
     assert layers._HINTS.gru_side is None
+
+
+def test_hint_overrides_are_scoped_and_unwind_in_order():
+    hints = layers._HINTS
+    before = hints.gru_side, hints.in_flight, hints.deterministic
+    with hints.override(in_flight=4, deterministic=True):
+        assert (hints.gru_side, hints.in_flight, hints.deterministic) == (before[0], 4, True)
+        side = layers.GruLaunch(8, False)
+        with hints.override(in_flight=2, gru_side=side):
+            assert (hints.gru_side, hints.in_flight, hints.deterministic) == (side, 2, True)
+            with hints.override(deterministic=False):
+                assert (hints.gru_side, hints.in_flight, hints.deterministic) == (side, 2, False)
+            assert (hints.gru_side, hints.in_flight, hints.deterministic) == (side, 2, True)
+        assert (hints.gru_side, hints.in_flight, hints.deterministic) == (before[0], 4, True)
+    assert (hints.gru_side, hints.in_flight, hints.deterministic) == before
+    with pytest.raises(RuntimeError):
+        with hints.override(in_flight=8, deterministic=True):
+            assert (hints.in_flight, hints.deterministic) == (8, True)
+            raise RuntimeError("inside the block")
+    assert (hints.gru_side, hints.in_flight, hints.deterministic) == before
+    # a name that is no hint is refused, and nothing is set on the way
+    with pytest.raises(AttributeError):
+        with hints.override(in_flight=8, in_fligth=2):
+            pass
+    assert (hints.gru_side, hints.in_flight, hints.deterministic) == before
