@@ -296,6 +296,10 @@ SLK_API int slk_gru_bar16_pack_f32(const float *iW, const float *bias, const flo
                            void *pack, slk_stream_t stream);
 SLK_API int slk_gru_bar16_stack_f32(int nlayer, const slk_gru_stack_layer *layers, int insize, int n, int T, int B,
                             const int32_t *lens, slk_stream_t stream);
+/* Host only: which instantiation a slk_gru_bar16_stack_f32 launch of batch B takes; `ragged` says whether any layer looks at lens
+ * (lens != NULL and a layer without SLK_GRU_STACK_NO_LENS).  1: the full-batch kernel -- every workgroup has four chunks of T steps,
+ * so its stores of h carry no predicate; taken when !ragged and B % 4 == 0.  0: the general kernel.  Same bits either way. */
+SLK_API int slk_gru_bar16_stack_path(int B, int ragged);
 /* Ragged batches (whole reads of different lengths, zero-padded to T steps; the reference calls reads one at a time,
  * sloika/basecall.py:88-121): lens[b] in [1, T] (int32, device) is the number of valid steps of chunk b.  Steps
  * t >= lens[b] of y / h_out are left untouched, and with reverse = 1 the scan of chunk b starts at ITS last step,

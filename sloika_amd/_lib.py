@@ -84,6 +84,7 @@ PROTOTYPES = {
     "slk_gru_bar16_pack_bytes": (_sz, [_i, _i]),
     "slk_gru_bar16_pack_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "slk_gru_bar16_stack_f32": (_i, [_i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "slk_gru_bar16_stack_path": (_i, [_i, _i]),
     "slk_gru_bar16_f32": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "slk_lstm_recurrent_f32": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _vp]),
     "slk_lstm_recurrent_ragged_f32": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _vp, _vp]),

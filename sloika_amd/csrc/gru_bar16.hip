@@ -39,6 +39,9 @@
 // design/gru_projection.md), 1024 = the z products stay, the z picks and sigmoid(z), 1 - z, z*h are bit 64's constants (the bound of what
 // placing the z epilogue can gain), 2048 = the head of interval A without the vI and x-operand requests and without the stores: the
 // gate terms are constants (the bound of what moving them behind the own-block products can gain: design/gru_step_order.md).
+// What bit 16 takes away, piece by piece (design/gru_store.md; meaningful on a full batch with B % 4 == 0 and lens = NULL only):
+// 4096 = the predicate of the h_out stores and its branch around an empty body, 8192 = both stores without the predicate,
+// 16384 = the first store of the two only, 32768 = the stores' row never moves (no pointer bump: everything lands on one row).
 #ifdef SLK_DIAG
 __device__ unsigned long long slk_dbg_bar16[4][16];
 extern "C" SLK_API int slk_debug_read_bar16(unsigned long long *host_out)
@@ -96,19 +99,20 @@ __global__ void __launch_bounds__(256, 1) gru_bar16_kernel(const float *__restri
                                                            int T, int B, int reverse, const int *__restrict__ lens,
                                                            float *__restrict__ zr_out)
 {
-    constexpr bool PACKED = false;
+    constexpr bool PACKED = false, FULL = false;
     [[maybe_unused]] const void *const pack = nullptr;
 #include "gru_bar16_body.h"
 }
 
 // The same layer with its weight images loaded from `pack`: the loop body of gru_bar16_stack_kernel.
-template <int I, int N>
+// FULLV: the full-batch stores of h (gru_bar16_body.h: FULL).  ABLV: diagnostic builds only.
+template <int I, int N, bool FULLV, int ABLV>
 __device__ __forceinline__ void gru_bar16_layer_packed(const float *__restrict__ x, long ldx, const void *__restrict__ pack,
                                                        float *__restrict__ h_out, long ldh, int T, int B, int reverse,
                                                        const int *__restrict__ lens)
 {
-    constexpr bool PACKED = true, SAVE = false, DIAG = false;
-    constexpr int ABL = 0;
+    constexpr bool PACKED = true, SAVE = false, DIAG = false, FULL = FULLV;
+    constexpr int ABL = ABLV;
     [[maybe_unused]] const float *const iW = nullptr, *const bias = nullptr, *const sW = nullptr, *const sW2 = nullptr;
     [[maybe_unused]] float *const zr_out = nullptr;
 #include "gru_bar16_body.h"
@@ -164,14 +168,14 @@ __global__ void __launch_bounds__(64) gru_bar16_pack_kernel(const float *__restr
 struct Bar16StackArgs {
     slk_gru_stack_layer l[SLK_GRU_STACK_MAX];
 };
-template <int I, int N>
+template <int I, int N, bool FULLV = false, int ABLV = 0>
 __global__ void __launch_bounds__(256, 1) gru_bar16_stack_kernel(const Bar16StackArgs a, int nlayer, int T, int B,
                                                                  const int *__restrict__ lens)
 {
     for (int k = 0; k < nlayer; k++) {
         const slk_gru_stack_layer &d = a.l[k];
-        gru_bar16_layer_packed<I, N>(d.x, d.ldx, d.pack, d.h_out, d.ldh, T, B, d.reverse & 1,
-                                     (d.reverse & SLK_GRU_STACK_NO_LENS) ? nullptr : lens);
+        gru_bar16_layer_packed<I, N, FULLV, ABLV>(d.x, d.ldx, d.pack, d.h_out, d.ldh, T, B, d.reverse & 1,
+                                                  (FULLV || (d.reverse & SLK_GRU_STACK_NO_LENS)) ? nullptr : lens);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __syncthreads();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -227,6 +231,9 @@ static int launch_bar16(const float *x, long ldx, const float *iW, const float *
         DIAG_LAUNCH(24, false, 384) DIAG_LAUNCH(25, true, 384) DIAG_LAUNCH(26, false, 640) DIAG_LAUNCH(27, true, 640)
         DIAG_LAUNCH(28, false, 1024) DIAG_LAUNCH(29, true, 1024) DIAG_LAUNCH(30, false, 2048) DIAG_LAUNCH(31, true, 2048)
         DIAG_LAUNCH(32, false, 3072)
+        DIAG_LAUNCH(33, false, 4096) DIAG_LAUNCH(34, false, 8192) DIAG_LAUNCH(35, false, 16384) DIAG_LAUNCH(36, false, 32768)
+        DIAG_LAUNCH(37, true, 4096) DIAG_LAUNCH(38, true, 8192) DIAG_LAUNCH(39, true, 16384) DIAG_LAUNCH(40, true, 32768)
+        DIAG_LAUNCH(41, true, 16)
 #undef DIAG_LAUNCH
     }
 #endif
@@ -327,26 +334,56 @@ extern "C" int slk_gru_bar16_pack_f32(const float *iW, const float *bias, const 
     return SLK_ERR_UNSUPPORTED;
 }
 
+// Which kernel a stack launch takes (include/sloika_amd.h): 1 = the full-batch instantiation (gru_bar16_body.h: FULL), whose chain
+// waves store h without a predicate, 0 = the general one.
+extern "C" int slk_gru_bar16_stack_path(int B, int ragged) { return !ragged && B >= 4 && !(B & 3) ? 1 : 0; }
+
+#ifdef SLK_DIAG
+// (tools/bar16_check.py) the 96 -> 96 stack launches of the process take <FULL, ABL> of the pairs below
+static int dbg_stack_full = -1, dbg_stack_abl = 0;
+extern "C" SLK_API void slk_debug_bar16_stack_variant(int full, int abl) { dbg_stack_full = full; dbg_stack_abl = abl; }
+#endif
+
+template <int I, int N, bool FULLV, int ABLV = 0>
+static int launch_bar16_stack(const Bar16StackArgs &a, int nlayer, int T, int B, const int *lens, hipStream_t s)
+{
+    const size_t dyn = SLK_PER_DEVICE(size_t, exclusive_cu_lds_bar(gru_bar16_stack_kernel<I, N, FULLV, ABLV>));
+    hipLaunchKernelGGL((gru_bar16_stack_kernel<I, N, FULLV, ABLV>), dim3((B + 3) / 4), dim3(256), dyn, s, a, nlayer, T, B, lens);
+    return slk_launch_status();
+}
+
 extern "C" int slk_gru_bar16_stack_f32(int nlayer, const slk_gru_stack_layer *layers, int insize, int n, int T, int B,
                                        const int32_t *lens, slk_stream_t stream)
 {
     if (!layers || nlayer < 1 || nlayer > SLK_GRU_STACK_MAX || T < 1 || B < 1 || insize < 1 || n < 1) return SLK_ERR_INVALID_ARG;
     if (nlayer > 1 && insize != n) return SLK_ERR_INVALID_ARG;                // a layer's output is the next layer's input
     Bar16StackArgs a = {};
+    bool ragged = false;                                                      // does any layer look at lens
     for (int k = 0; k < nlayer; k++) {
         const slk_gru_stack_layer &d = layers[k];
         if (!d.x || !d.h_out || !d.pack || d.ldx < insize || d.ldh < n || d.x == d.h_out) return SLK_ERR_INVALID_ARG;
         if ((d.ldx & 3) || (reinterpret_cast<uintptr_t>(d.x) & 15) || (reinterpret_cast<uintptr_t>(d.pack) & 15))
             return SLK_ERR_UNSUPPORTED;                                       // 16-byte pieces, as slk_gru_bar16_f32
         a.l[k] = d;
+        ragged = ragged || (lens && !(d.reverse & SLK_GRU_STACK_NO_LENS));
     }
     hipStream_t s = slk_stream(stream);
-#define BAR16(II, NN)                                                                                                      \
-    if (insize == II && n == NN) {                                                                                         \
-        const size_t dyn = SLK_PER_DEVICE(size_t, exclusive_cu_lds_bar(gru_bar16_stack_kernel<II, NN>));                    \
-        hipLaunchKernelGGL((gru_bar16_stack_kernel<II, NN>), dim3((B + 3) / 4), dim3(256), dyn, s, a, nlayer, T, B, lens);  \
-        return slk_launch_status();                                                                                        \
+    const bool full = slk_gru_bar16_stack_path(B, ragged) == 1;
+#ifdef SLK_DIAG
+    if (insize == 96 && n == 96 && dbg_stack_full >= 0) {
+        // (the caller's business: FULL on a full batch without lens only)
+#define DIAG_STACK(FULLV, ABLV) \
+        if (dbg_stack_full == FULLV && dbg_stack_abl == ABLV) return launch_bar16_stack<96, 96, FULLV != 0, ABLV>(a, nlayer, T, B, lens, s);
+        DIAG_STACK(0, 0) DIAG_STACK(0, 16) DIAG_STACK(0, 4096) DIAG_STACK(0, 8192) DIAG_STACK(0, 16384) DIAG_STACK(0, 32768)
+        DIAG_STACK(1, 0) DIAG_STACK(1, 16) DIAG_STACK(1, 16384)
+#undef DIAG_STACK
+        return SLK_ERR_UNSUPPORTED;
     }
+#endif
+#define BAR16(II, NN)                                                                                                      \
+    if (insize == II && n == NN)                                                                                           \
+        return full ? launch_bar16_stack<II, NN, true>(a, nlayer, T, B, lens, s)                                            \
+                    : launch_bar16_stack<II, NN, false>(a, nlayer, T, B, lens, s);
     BAR16_PACKED_SHAPES(BAR16)
 #undef BAR16
     return SLK_ERR_UNSUPPORTED;

@@ -3,9 +3,12 @@
 // and inside gru_bar16_layer_packed (the loop body of gru_bar16_stack_kernel; PACKED = true: the images, their inverse scales and the
 // bias come from `pack`, which gru_bar16_pack_kernel wrote with bar16_common.h's restatement of the prologue's arithmetic).  Text, not a function: as a
 // function inlined into both, the per-layer kernels came out of the compiler with another register assignment and 1.6 % slower.
-// In scope where it is included: I, N, SAVE, DIAG, ABL, PACKED (constants) and x, ldx, iW, bias, sW, sW2, pack, h_out, ldh, T, B,
-// reverse, lens, zr_out.
+// In scope where it is included: I, N, SAVE, DIAG, ABL, PACKED, FULL (constants) and x, ldx, iW, bias, sW, sW2, pack, h_out, ldh, T,
+// B, reverse, lens, zr_out.
+// FULL (design/gru_store.md): the launcher saw that no layer looks at lens and that B % 4 == 0, so every chunk slot of every workgroup
+// is a chunk of T steps: no lane computes, tests or branches on a predicate for its stores of h.  Only the packed stack kernels take it.
     static_assert(!PACKED || !SAVE, "the training pass changes its weights every step: no pack");
+    static_assert(!FULL || (PACKED && !SAVE), "the full-batch stores are the packed stack kernel's");
     using PK = Bar16Pack<I, N>;
     [[maybe_unused]] const half8 *const pk8 = static_cast<const half8 *>(pack);
     static_assert(I % 16 == 0 && N % 32 == 0 && N <= 96, "unsupported size for the barrier-stepped GRU kernel");
@@ -215,8 +218,8 @@
         const int voff = 4 * slot(nn >> 2, cn) + (nn & 3);                                      // my element of a vI tile
         // my chunk's rows of h_out (ragged batch: chunk bc is Tc <= T steps long; a reversed scan starts at ITS last step)
         const int bc = b0 + cn;
-        const bool live = bc < B;
-        const int Tc = (lens && live) ? min(max(lens[bc], 1), T) : T;
+        const bool live = FULL || bc < B;
+        const int Tc = FULL ? T : (lens && live) ? min(max(lens[bc], 1), T) : T;
         const long hstep = (reverse ? -1L : 1L) * (long)B * ldh;
         float *hp = h_out + ((size_t)(reverse ? Tc - 1 : 0) * B + (live ? bc : 0)) * ldh + n0;
         const long zstep = (reverse ? -1L : 1L) * (long)B * 2 * N;
@@ -248,6 +251,10 @@
         if constexpr (DIAG) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev)::"memory"); }
         float hold[2] = {0.0f, 0.0f};
         [[maybe_unused]] float zkeep[2] = {0.0f, 0.0f};  // SAVE: the update gate of the step before, stored with its h
+        auto store_h = [&]() {                           // `hold` to its row (ABL 16384: the first of the two stores only)
+            hp[0] = hold[0];
+            if constexpr (!(ABL & 16384)) hp[16] = hold[1];
+        };
         // carried from step to step: my own K block of h(s-1) as A operand, read back right after I wrote it
         half8 oh = {0, 0, 0, 0, 0, 0, 0, 0};
         settle(oh);
@@ -319,13 +326,16 @@
             __builtin_amdgcn_sched_barrier(0);
             float vz[2], vr[2], vc[2];
             [[maybe_unused]] auto put_h = [&]() {        // h(s-1): still in `hold`
-                if (s > 0) {
-                    if (live && s - 1 < Tc && !(ABL & 16) && !NOHEAD) {
-                        hp[0] = hold[0];
-                        hp[16] = hold[1];
+                if (FULL ? (ph > 0 || s > 0) : s > 0) {  // (FULL: a fact in phases 1 to 3, a test of the group counter in phase 0)
+                    if constexpr (FULL) {
+                        if constexpr (!(ABL & 16) && !NOHEAD) store_h();
+                    } else if constexpr (ABL & 4096) {   // diagnostic: the predicate and its branch around nothing
+                        if (live && s - 1 < Tc) asm volatile("" ::"v"(hold[0]), "v"(hold[1]), "v"(hp));
+                    } else if ((ABL & 8192) || (live && s - 1 < Tc && !(ABL & 16) && !NOHEAD)) {
+                        store_h();
                         if constexpr (SAVE) { zp[0] = zkeep[0]; zp[16] = zkeep[1]; }
                     }
-                    hp += hstep;
+                    if constexpr (!(ABL & 32768)) hp += hstep;           // (diagnostic: a row that never moves)
                     if constexpr (SAVE) zp += zstep;
                 }
             };
@@ -565,9 +575,8 @@
             if (s + 2 < T) step(ic<2>{}, s + 2, G);
             if (s + 3 < T) step(ic<3>{}, s + 3, G);
         }
-        if (live && T - 1 < Tc && !(ABL & 16)) {         // h (and z) of the last step
-            hp[0] = hold[0];
-            hp[16] = hold[1];
+        if (!(ABL & 16) && (FULL || (live && T - 1 < Tc))) {         // h (and z) of the last step
+            store_h();
             if constexpr (SAVE) { zp[0] = zkeep[0]; zp[16] = zkeep[1]; }
         }
 #ifdef SLK_DIAG
@@ -618,8 +627,8 @@
         // into registers (the four lanes of a row and K block cover one 128-byte line) a group ahead of the split -- no staging
         // in LDS, no LDS-DMA (a 1-KiB request kept the issuing wave ~150 cycles, twelve of sixteen intervals carried one).
         // Ordinary loads: the compiler waits for them where the split first uses them, a group later.
-        const int xbc = min(b0 + pc, B - 1);
-        const int xTc = lens ? min(max(lens[xbc], 1), T) : T;
+        const int xbc = FULL ? b0 + pc : min(b0 + pc, B - 1);
+        const int xTc = FULL ? T : lens ? min(max(lens[xbc], 1), T) : T;
         f32x4 xr[KBLK][2];
         auto load_x = [&](int G2) {
             // steps past the chunk's end re-read its last valid row (their results are never stored)
