@@ -1,7 +1,10 @@
 // bar16_common.h -- helpers shared by the barrier-stepped Gru kernels (gru_bar16.hip: four chunks per workgroup,
 // gru_bar16d.hip: eight, gru_bar16q.hip: sixteen): barriers that wait for LDS the cheap way, the five-instruction tanh, 3-term split
-// MFMA sequences and the projection's MFMAs with weights named in accumulation registers; at the end the host side the three files
-// share: the table of shapes, the entry points they call across files and the launcher of the eight- and sixteen-chunk kernels.
+// MFMA sequences and the projection's MFMAs with weights named in accumulation registers; then what the three plans derive alike from
+// (insize, n) (Bar16Dims), the interval function of their service waves, the weight images (their statements are bar16_proj_image.h
+// and bar16_rec_image.h, included by the kernels' prologues and by the pack kernel's functions here) and the layout of a pack; at the
+// end the host side the three files share: the table of shapes, the entry points they call across files and THE launch of one of two
+// instantiations of a kernel, which every launcher of the family goes through.
 #pragma once
 #include <type_traits>
 
@@ -286,81 +289,58 @@ __device__ __forceinline__ void tile2_mfma_acc(f32x4 &a0, f32x4 &a1, const half8
     });
 }
 
-// ---- the weight images of the four-chunk kernel (gru_bar16.hip) -----------------------------------------------------------------------
-// Every workgroup of gru_bar16_kernel makes them in its prologue (gru_bar16_body.h: load_tile, and the chain waves' loop over their
-// two tiles); gru_bar16_pack_kernel makes them once per set of weights with the two functions below, which repeat that arithmetic
-// statement for statement -- same loads, same pow2_scale(kgroup_max(.)), same conversions -- so that a pack holds the bits the
-// prologue makes (tests/test_gpu_gru_stack.py compares results bit for bit).  Change one, change the other.  All 64 lanes of the
-// wave call these (kgroup_max swaps across lanes).
-// One iW tile -> A operands (lane: row pcol of the tile, k = 32 kb + 8 kg + 0..7); returns the row's inverse scale.
-template <int I, int KBLK_>
+// ---- what the three plans derive from (insize, n) alike ---------------------------------------------------------------------------------
+// Per plan, and therefore in the kernels: GS, R, CT, ST, NA, the LDS layouts (OPSTEP / OPIMG, VSTEP, IMG) and the check that CT tiles per
+// chain wave and ST per service wave make up NT16.
+template <int I, int N>
+struct Bar16Dims {
+    static constexpr int NCW = N / 32;                   // chain waves = 32-wide K blocks of the recurrent products
+    static constexpr int KBS = N / 32;
+    static constexpr int NSW = 4 - NCW;                  // service waves
+    static constexpr int NT = N / 16;                    // tiles per gate
+    static constexpr int NT16 = 3 * NT;                  // tiles of vI rows (z | r | c)
+    static constexpr int KBLK = (I + 31) / 32;
+    static constexpr int NACAP = 240 / (8 * KBLK);       // 256 accumulation registers, 2 * KBLK * 4 per tile
+    static_assert(I % 16 == 0 && N % 32 == 0 && N <= 96, "unsupported size for the barrier-stepped GRU kernel");
+    static_assert(KBLK <= 4, "interval plan");
+};
+
+// First tile of interval k of a service wave with st tiles per group (and set) when the n intervals of a group take tiles in the
+// proportions w[0 .. n-1] (k = n: st).  The tables stand next to the kernels that own them.
+__host__ __device__ constexpr int bar16_tile_first(int st, int k, const int *w, int n)
+{
+    int tot = 0, acc = 0;
+    for (int i = 0; i < n; i++) tot += w[i];
+    for (int i = 0; i < k && i < n; i++) acc += w[i];
+    return k >= n ? st : (acc * st + tot / 2) / tot < st ? (acc * st + tot / 2) / tot : st;
+}
+
+// ---- the weight images -------------------------------------------------------------------------------------------------------------------
+// Every workgroup of the per-layer kernels makes its images in its prologue; gru_bar16_pack_kernel (gru_bar16.hip) makes the four-chunk
+// kernel's once per set of weights with the two functions below.  The arithmetic is ONE text, bar16_proj_image.h and bar16_rec_image.h,
+// included here and in the prologues (what it expects in scope: there): a pack holds the bits a prologue makes.  All 64 lanes of the
+// wave call these.
+// One iW tile -> A operands; returns the row's inverse scale.
+template <int I, int KBLK>
 __device__ __forceinline__ float bar16_proj_tile(const float *iW, int tile, int pcol, int kg, half8 *hi, half8 *lo)
 {
-    const int row = 16 * tile + pcol;
-    float u[KBLK_][8];
-    float m = 0.0f;
-#pragma unroll
-    for (int kb = 0; kb < KBLK_; kb++) {
-        const int k0 = 32 * kb + 8 * kg;
-        const bool kok = (I % 32 == 0) || k0 < I;
-        const float *src = iW + (size_t)row * I + (kok ? k0 : 0);
-        const float4 u0 = *reinterpret_cast<const float4 *>(src), u1 = *reinterpret_cast<const float4 *>(src + 4);
-        const float t[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            u[kb][j] = kok ? t[j] : 0.0f;
-            m = fmaxf(m, fabsf(u[kb][j]));
-        }
-    }
-    float inv;
-    const float ws = pow2_scale(kgroup_max(m), inv);
-#pragma unroll
-    for (int kb = 0; kb < KBLK_; kb++) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const float v = u[kb][j] * ws;
-            const _Float16 h = (_Float16)v;
-            hi[kb][j] = h;
-            lo[kb][j] = (_Float16)(v - (float)h);
-        }
-    }
+#define BAR16_PROJ_INV(row, inv)
+#include "bar16_proj_image.h"
+#undef BAR16_PROJ_INV
     return inv;
 }
-// Recurrent weights of chain wave w, tile p of its two: B operands (column lane & 15 = neuron, k group g = lane >> 4), K blocks in the
-// rotated order w, w+1, ... (element (g, j) of block kb is neuron 32 kb + 16 (j&1) + 4 g + (j>>1), the order the owners' packed writes
-// create), rows scaled to [1, 2); iz / ir / ic: the rows' inverse scales (every lane of a row has the row's, and its neuron IS its row).
-template <int N, int KBS_>
+// Recurrent weights of chain wave w, tile p of its two -> B operands; inv_z / inv_r / inv_c: the rows' inverse scales.
+template <int N, int KBS>
 __device__ __forceinline__ void bar16_rec_tile(const float *sW, const float *sW2, int w, int p, int lane, half8 *wz_hi, half8 *wz_lo,
-                                               half8 *wr_hi, half8 *wr_lo, half8 *wc_hi, half8 *wc_lo, float &iz, float &ir, float &ic_)
+                                               half8 *wr_hi, half8 *wr_lo, half8 *wc_hi, half8 *wc_lo, float &inv_z, float &inv_r,
+                                               float &inv_c)
 {
     const int g = lane >> 4;
-    const int row = 32 * w + 16 * p + (lane & 15);
-    float vz[KBS_][8], vr[KBS_][8], vc[KBS_][8];
-    float mz = 0.0f, mr = 0.0f, mc = 0.0f;
-#pragma unroll
-    for (int i = 0; i < KBS_; i++) {
-        const int kb = (w + i) % KBS_;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const int k = 32 * kb + 16 * (j & 1) + 4 * g + (j >> 1);
-            vz[i][j] = sW[(size_t)row * N + k];
-            vr[i][j] = sW[(size_t)(N + row) * N + k];
-            vc[i][j] = sW2[(size_t)row * N + k];
-            mz = fmaxf(mz, fabsf(vz[i][j])); mr = fmaxf(mr, fabsf(vr[i][j])); mc = fmaxf(mc, fabsf(vc[i][j]));
-        }
-    }
-    const float sz = pow2_scale(kgroup_max(mz), iz), sr = pow2_scale(kgroup_max(mr), ir), sc = pow2_scale(kgroup_max(mc), ic_);
-#pragma unroll
-    for (int i = 0; i < KBS_; i++) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const float az = vz[i][j] * sz, ar = vr[i][j] * sr, ac = vc[i][j] * sc;
-            const _Float16 hz = (_Float16)az, hr = (_Float16)ar, hc = (_Float16)ac;
-            wz_hi[i][j] = hz; wz_lo[i][j] = (_Float16)(az - (float)hz);
-            wr_hi[i][j] = hr; wr_lo[i][j] = (_Float16)(ar - (float)hr);
-            wc_hi[i][j] = hc; wc_lo[i][j] = (_Float16)(ac - (float)hc);
-        }
-    }
+#define BAR16_REC_INV(iz, ir, ic_) inv_z = iz; inv_r = ir; inv_c = ic_;
+#define BAR16_REC_W(a) a
+#include "bar16_rec_image.h"
+#undef BAR16_REC_W
+#undef BAR16_REC_INV
 }
 // Where the pack keeps them, in 16-byte pieces: every image is 64 consecutive pieces, one per lane, so a wave's prologue is a run of
 // 1-KiB loads.  Per chain wave the images of its two tiles -- item(p, gate z / r / c, K block i in ITS rotated order, hi / lo) -- and
@@ -368,7 +348,8 @@ __device__ __forceinline__ void bar16_rec_tile(const float *sW, const float *sW2
 // of ANY wave holds them (which wave takes which tile is the kernel's business); then invw[3N] and bias[3N] as floats.
 template <int I, int N>
 struct Bar16Pack {
-    static constexpr int NCW = N / 32, KBS = N / 32, NT16 = 3 * N / 16, KBLK = (I + 31) / 32;
+    using D = Bar16Dims<I, N>;
+    static constexpr int NCW = D::NCW, KBS = D::KBS, NT16 = D::NT16, KBLK = D::KBLK;
     static constexpr int REC_ITEMS = 12 * KBS + 2;
     static constexpr size_t PROJ0 = (size_t)NCW * REC_ITEMS * 64;
     static constexpr size_t FLT0 = PROJ0 + (size_t)NT16 * KBLK * 2 * 64;
@@ -398,17 +379,22 @@ extern "C" int slk_gru_bar16q_launch(const float *x, long ldx, const float *iW, 
                                      float *y, long ldy, int T, int B, int insize, int n, int reverse, const int32_t *lens,
                                      float *zr_out, hipStream_t s);
 
-// One workgroup per CHUNKS chunks of the batch; K_SAVE / K_PLAIN: the kernel's instantiations that do / do not write the gates (zr_out).
-// The kernels are template arguments, not run-time pointers: whatever a launcher keeps per device (SLK_PER_DEVICE) it then keeps per kernel.
+// THE launch of one of two instantiations of a kernel (the one that writes the gates or the plain one; the full-batch stack kernel or the
+// general one): nwg workgroups of four waves, dyn bytes of dynamic LDS.  The kernels are template arguments, not run-time pointers:
+// whatever a launcher keeps per device (SLK_PER_DEVICE) it then keeps per kernel.
+template <auto K_FIRST, auto K_SECOND, class... Args>
+static int launch_bar16_either(bool first, int nwg, size_t dyn, hipStream_t s, Args... args)
+{
+    if (first) hipLaunchKernelGGL(K_FIRST, dim3(nwg), dim3(256), dyn, s, args...);
+    else hipLaunchKernelGGL(K_SECOND, dim3(nwg), dim3(256), dyn, s, args...);
+    return slk_launch_status();
+}
+// A layer: one workgroup per CHUNKS chunks of the batch; K_SAVE / K_PLAIN: the kernel's instantiations that do / do not write the gates.
 template <int CHUNKS, auto K_SAVE, auto K_PLAIN>
 static int launch_bar16_chunks(const float *x, long ldx, const float *iW, const float *bias, const float *sW, const float *sW2,
-                               float *y, long ldy, int T, int B, int reverse, const int *lens, float *zr_out, hipStream_t s)
+                               float *y, long ldy, int T, int B, int reverse, const int *lens, float *zr_out, hipStream_t s,
+                               size_t dyn = 0)
 {
-    if (zr_out)
-        hipLaunchKernelGGL(K_SAVE, dim3((B + CHUNKS - 1) / CHUNKS), dim3(256), 0, s, x, ldx, iW, bias, sW, sW2, y, ldy, T, B,
-                           reverse & 1, lens, zr_out);
-    else
-        hipLaunchKernelGGL(K_PLAIN, dim3((B + CHUNKS - 1) / CHUNKS), dim3(256), 0, s, x, ldx, iW, bias, sW, sW2, y, ldy, T, B,
-                           reverse & 1, lens, zr_out);
-    return slk_launch_status();
+    return launch_bar16_either<K_SAVE, K_PLAIN>(zr_out != nullptr, (B + CHUNKS - 1) / CHUNKS, dyn, s, x, ldx, iW, bias, sW, sW2, y, ldy, T,
+                                                B, reverse & 1, lens, zr_out);
 }

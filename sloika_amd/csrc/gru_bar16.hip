@@ -20,7 +20,10 @@
 // 4c + j carries chunk c -- j = 0: its hi half, j = 2: its lo half; rows j = 1, 3 are not used and fetch the neighbouring chunk so
 // that a ds_read_b128 touches every bank once -- and a B column is a neuron of the tile, so lane (chunk c = lane >> 4, neuron
 // n = lane & 15) finds hi.W in register 0 and lo.W in register 2 of its accumulator: a gate's pre-activation is one v_add_f32
-// (bar16_common.h: pick_sum_kept).  The K order of the packed operand images: bar16_rec_tile there.
+// (bar16_common.h: pick_sum_kept).  The K order of the packed operand images: bar16_rec_image.h.
+// Shared with gru_bar16d.hip and gru_bar16q.hip (design/gru_prologue.md): the statements that make the weight images
+// (bar16_proj_image.h, bar16_rec_image.h), the shape constants (bar16_common.h: Bar16Dims), the interval function (bar16_tile_first;
+// the tables stay with their kernels) and the launch (launch_bar16_either).
 #include <limits.h>
 #include <stdlib.h>
 
@@ -68,24 +71,16 @@ extern "C" SLK_API int slk_debug_read_bar16_wg(unsigned long long *host_out)
 #define BSTAMP(i)
 #endif
 
-// first tile of interval k when a service wave has st tiles per group (k = 8: st)
-// table 0: lighter where the leader also splits x (intervals 1..4) and fetches operands (0).
-// table 1, a single service wave behind chain waves that project behind their write of r*h (gru_bar16_body.h: LATE): by the stamps
-// of table 0 (design/gru_projection.md) the wave reached the barrier behind interval 1 -- a tile and the scale of the coming
+// The service wave's tiles per interval, as proportions for bar16_tile_first (bar16_common.h); row = TBL of gru_bar16_body.h.
+// row 0: lighter where the leader also splits x (intervals 1..4) and fetches operands (0).
+// row 1, a single service wave behind chain waves that project behind their write of r*h (gru_bar16_body.h: LATE): by the stamps
+// of row 0 (design/gru_projection.md) the wave reached the barrier behind interval 1 -- a tile and the scale of the coming
 // group's rows, in the shorter half of the step -- last of the four, and the one behind interval 4 -- two tiles, a K block of the
 // split, the loads of x -- 50 cycles ahead of the chain.  Interval 1 keeps no tile, interval 4 one; 0 and 2, in the longer half, two.
-__host__ __device__ constexpr int tile_first(int st, int k, int table = 0)
-{
-    constexpr int w0[8] = {1, 1, 1, 1, 2, 2, 2, 2}, w1[8] = {2, 0, 2, 1, 1, 2, 2, 2};
-    const int *const w = table == 1 ? w1 : w0;
-    int tot = 0, acc = 0;
-    for (int i = 0; i < 8; i++) tot += w[i];
-    for (int i = 0; i < k && i < 8; i++) acc += w[i];
-    return k >= 8 ? st : (acc * st + tot / 2) / tot < st ? (acc * st + tot / 2) / tot : st;
-}
+constexpr int BAR16_TILE_W[2][8] = {{1, 1, 1, 1, 2, 2, 2, 2}, {2, 0, 2, 1, 1, 2, 2, 2}};
 
-// ABL bits 256 / 512: tiles an interval of the service wave computes a second time, on top of whatever table it has -- measured on
-// table 0 (design/gru_projection.md 1), where they made {2,2,2,2,2,2,3,3} and {1,2,2,2,2,2,2,2} tiles per interval of {1,1,1,1,2,2,2,2}
+// ABL bits 256 / 512: tiles an interval of the service wave computes a second time, on top of whatever row of the table it has -- measured on
+// row 0 (design/gru_projection.md 1), where they made {2,2,2,2,2,2,3,3} and {1,2,2,2,2,2,2,2} tiles per interval of {1,1,1,1,2,2,2,2}
 __host__ __device__ constexpr int tile_extra(int abl, int k)
 {
     constexpr int six[8] = {1, 1, 1, 1, 0, 0, 1, 1}, three[8] = {0, 1, 1, 1, 0, 0, 0, 0};
@@ -182,18 +177,20 @@ __global__ void __launch_bounds__(256, 1) gru_bar16_stack_kernel(const Bar16Stac
     }
 }
 
-// One workgroup per CU: ask for enough dynamic LDS that two cannot share a CU.
-template <typename K>
-static size_t exclusive_cu_lds_bar(K kernel)
+// One workgroup per CU: the dynamic LDS to ask for so that two cannot share a CU (asked once per kernel and device).
+template <auto KERNEL>
+static size_t exclusive_cu_lds_bar()
 {
-    hipFuncAttributes attr;
-    if (hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kernel)) != hipSuccess) return 0;
-    const size_t half_cu = 80 * 1024 + 512;                         // 160 KB of LDS per CU
-    const size_t dyn = attr.sharedSizeBytes >= half_cu ? 0 : half_cu - attr.sharedSizeBytes;
-    if (dyn && hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)dyn) != hipSuccess)
-        return 0;
-    return dyn;
+    return SLK_PER_DEVICE(size_t, ([] {
+        hipFuncAttributes attr;
+        if (hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(KERNEL)) != hipSuccess) return (size_t)0;
+        const size_t half_cu = 80 * 1024 + 512;                     // 160 KB of LDS per CU
+        const size_t dyn = attr.sharedSizeBytes >= half_cu ? 0 : half_cu - attr.sharedSizeBytes;
+        if (dyn && hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)dyn) != hipSuccess)
+            return (size_t)0;
+        return dyn;
+    }()));
 }
 
 template <typename K>
@@ -218,10 +215,9 @@ static int launch_bar16(const float *x, long ldx, const float *iW, const float *
         const int dv = forced ? forced : reverse >> 1;
 #define DIAG_LAUNCH(CODE, STAMPS, ABLV)                                                                                   \
         if (dv == CODE) {                                                                                                 \
-            const size_t dyn = SLK_PER_DEVICE(size_t, exclusive_cu_lds_bar(gru_bar16_kernel<I, N, false, STAMPS, ABLV>));                  \
-            hipLaunchKernelGGL((gru_bar16_kernel<I, N, false, STAMPS, ABLV>), dim3((B + 3) / 4), dim3(256), dyn, s, x, ldx, \
-                               iW, bias, sW, sW2, y, ldy, T, B, reverse & 1, lens, zr_out);                                \
-            return slk_launch_status();                                                                                    \
+            constexpr auto K = gru_bar16_kernel<I, N, false, STAMPS, ABLV>;                                               \
+            return launch_bar16_chunks<4, K, K>(x, ldx, iW, bias, sW, sW2, y, ldy, T, B, reverse, lens, zr_out, s,       \
+                                                exclusive_cu_lds_bar<K>());                                               \
         }
         DIAG_LAUNCH(1, true, 0) DIAG_LAUNCH(2, false, 1) DIAG_LAUNCH(3, false, 2) DIAG_LAUNCH(4, false, 4) DIAG_LAUNCH(5, false, 8)
         DIAG_LAUNCH(6, false, 16) DIAG_LAUNCH(7, false, 9) DIAG_LAUNCH(8, false, 3) DIAG_LAUNCH(9, false, 11) DIAG_LAUNCH(10, false, 31)
@@ -245,16 +241,11 @@ static int launch_bar16(const float *x, long ldx, const float *iW, const float *
                                : SLK_PER_DEVICE(int, bar16_blocks_per_cu(gru_bar16_kernel<I, N, false>));
         if (fit < 2) return SLK_ERR_UNSUPPORTED;         // -> slk_gru_bar16_f32 takes the eight-chunk plan
     }
-    if (zr_out) {
-        const size_t dyn = shared ? 0 : SLK_PER_DEVICE(size_t, exclusive_cu_lds_bar(gru_bar16_kernel<I, N, true>));
-        hipLaunchKernelGGL((gru_bar16_kernel<I, N, true>), dim3((B + 3) / 4), dim3(256), dyn, s, x, ldx, iW, bias, sW, sW2, y,
-                           ldy, T, B, reverse & 1, lens, zr_out);
-    } else {
-        const size_t dyn = shared ? 0 : SLK_PER_DEVICE(size_t, exclusive_cu_lds_bar(gru_bar16_kernel<I, N, false>));
-        hipLaunchKernelGGL((gru_bar16_kernel<I, N, false>), dim3((B + 3) / 4), dim3(256), dyn, s, x, ldx, iW, bias, sW, sW2, y,
-                           ldy, T, B, reverse & 1, lens, zr_out);
-    }
-    return slk_launch_status();
+    const size_t dyn = shared ? 0
+                       : zr_out ? exclusive_cu_lds_bar<gru_bar16_kernel<I, N, true>>()
+                                : exclusive_cu_lds_bar<gru_bar16_kernel<I, N, false>>();
+    return launch_bar16_chunks<4, gru_bar16_kernel<I, N, true>, gru_bar16_kernel<I, N, false>>(x, ldx, iW, bias, sW, sW2, y, ldy, T, B,
+                                                                                              reverse, lens, zr_out, s, dyn);
 }
 
 // More workgroups of four chunks than CUs would run one after the other: such batches take the eight-chunk plan of
@@ -344,12 +335,14 @@ static int dbg_stack_full = -1, dbg_stack_abl = 0;
 extern "C" SLK_API void slk_debug_bar16_stack_variant(int full, int abl) { dbg_stack_full = full; dbg_stack_abl = abl; }
 #endif
 
-template <int I, int N, bool FULLV, int ABLV = 0>
-static int launch_bar16_stack(const Bar16StackArgs &a, int nlayer, int T, int B, const int *lens, hipStream_t s)
+// full: the full-batch instantiation (ABLV: diagnostic builds only)
+template <int I, int N, int ABLV = 0>
+static int launch_bar16_stack(bool full, const Bar16StackArgs &a, int nlayer, int T, int B, const int *lens, hipStream_t s)
 {
-    const size_t dyn = SLK_PER_DEVICE(size_t, exclusive_cu_lds_bar(gru_bar16_stack_kernel<I, N, FULLV, ABLV>));
-    hipLaunchKernelGGL((gru_bar16_stack_kernel<I, N, FULLV, ABLV>), dim3((B + 3) / 4), dim3(256), dyn, s, a, nlayer, T, B, lens);
-    return slk_launch_status();
+    const size_t dyn = full ? exclusive_cu_lds_bar<gru_bar16_stack_kernel<I, N, true, ABLV>>()
+                            : exclusive_cu_lds_bar<gru_bar16_stack_kernel<I, N, false, ABLV>>();
+    return launch_bar16_either<gru_bar16_stack_kernel<I, N, true, ABLV>, gru_bar16_stack_kernel<I, N, false, ABLV>>(
+        full, (B + 3) / 4, dyn, s, a, nlayer, T, B, lens);
 }
 
 extern "C" int slk_gru_bar16_stack_f32(int nlayer, const slk_gru_stack_layer *layers, int insize, int n, int T, int B,
@@ -373,7 +366,7 @@ extern "C" int slk_gru_bar16_stack_f32(int nlayer, const slk_gru_stack_layer *la
     if (insize == 96 && n == 96 && dbg_stack_full >= 0) {
         // (the caller's business: FULL on a full batch without lens only)
 #define DIAG_STACK(FULLV, ABLV) \
-        if (dbg_stack_full == FULLV && dbg_stack_abl == ABLV) return launch_bar16_stack<96, 96, FULLV != 0, ABLV>(a, nlayer, T, B, lens, s);
+        if (dbg_stack_full == FULLV && dbg_stack_abl == ABLV) return launch_bar16_stack<96, 96, ABLV>(FULLV != 0, a, nlayer, T, B, lens, s);
         DIAG_STACK(0, 0) DIAG_STACK(0, 16) DIAG_STACK(0, 4096) DIAG_STACK(0, 8192) DIAG_STACK(0, 16384) DIAG_STACK(0, 32768)
         DIAG_STACK(1, 0) DIAG_STACK(1, 16) DIAG_STACK(1, 16384)
 #undef DIAG_STACK
@@ -381,9 +374,7 @@ extern "C" int slk_gru_bar16_stack_f32(int nlayer, const slk_gru_stack_layer *la
     }
 #endif
 #define BAR16(II, NN)                                                                                                      \
-    if (insize == II && n == NN)                                                                                           \
-        return full ? launch_bar16_stack<II, NN, true>(a, nlayer, T, B, lens, s)                                            \
-                    : launch_bar16_stack<II, NN, false>(a, nlayer, T, B, lens, s);
+    if (insize == II && n == NN) return launch_bar16_stack<II, NN>(full, a, nlayer, T, B, lens, s);
     BAR16_PACKED_SHAPES(BAR16)
 #undef BAR16
     return SLK_ERR_UNSUPPORTED;

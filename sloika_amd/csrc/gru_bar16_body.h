@@ -1,8 +1,9 @@
 // gru_bar16_body.h -- the body of one layer of the four-chunk Gru kernel, all four waves of the workgroup.  Included by
-// gru_bar16.hip inside gru_bar16_kernel (a launch per layer; PACKED = false: the prologue makes the weight images from iW, sW, sW2)
-// and inside gru_bar16_layer_packed (the loop body of gru_bar16_stack_kernel; PACKED = true: the images, their inverse scales and the
-// bias come from `pack`, which gru_bar16_pack_kernel wrote with bar16_common.h's restatement of the prologue's arithmetic).  Text, not a function: as a
-// function inlined into both, the per-layer kernels came out of the compiler with another register assignment and 1.6 % slower.
+// gru_bar16.hip inside gru_bar16_kernel (a launch per layer; PACKED = false: the prologue makes the weight images from iW, sW, sW2
+// with the statements of bar16_proj_image.h and bar16_rec_image.h) and inside gru_bar16_layer_packed (the loop body of
+// gru_bar16_stack_kernel; PACKED = true: the images, their inverse scales and the bias come from `pack`, which gru_bar16_pack_kernel
+// wrote with the same statements).  Text, not a function: as a function inlined into both, the per-layer kernels came out of the
+// compiler with another register assignment and 1.6 % slower (design/gru_prologue.md: the same holds for the image statements).
 // In scope where it is included: I, N, SAVE, DIAG, ABL, PACKED, FULL (constants) and x, ldx, iW, bias, sW, sW2, pack, h_out, ldh, T,
 // B, reverse, lens, zr_out.
 // FULL (design/gru_store.md): the launcher saw that no layer looks at lens and that B % 4 == 0, so every chunk slot of every workgroup
@@ -11,13 +12,8 @@
     static_assert(!FULL || (PACKED && !SAVE), "the full-batch stores are the packed stack kernel's");
     using PK = Bar16Pack<I, N>;
     [[maybe_unused]] const half8 *const pk8 = static_cast<const half8 *>(pack);
-    static_assert(I % 16 == 0 && N % 32 == 0 && N <= 96, "unsupported size for the barrier-stepped GRU kernel");
-    constexpr int NCW = N / 32;                          // chain waves = 32-wide K blocks of the recurrent products
-    constexpr int KBS = N / 32;
-    constexpr int NSW = 4 - NCW;                         // service waves
-    constexpr int NT = N / 16;                           // tiles per gate
-    constexpr int NT16 = 3 * NT;                         // tiles of vI rows (z | r | c)
-    constexpr int KBLK = (I + 31) / 32;
+    using DM = Bar16Dims<I, N>;                          // bar16_common.h: what (I, N) alone decide
+    constexpr int NCW = DM::NCW, KBS = DM::KBS, NSW = DM::NSW, NT = DM::NT, NT16 = DM::NT16, KBLK = DM::KBLK, NACAP = DM::NACAP;
     constexpr int GS = 4;                                // steps per projection group (16 MFMA columns = 4 steps x 4 chunks)
     constexpr int R = 2 * GS;                            // vI ring: group G+1 is written while group G is consumed
     // projection tiles of a chain wave (weights in accumulation registers); three where four K blocks of the input would not leave
@@ -30,11 +26,9 @@
     // the own r and z blocks.  Four K blocks of input (128 -> 96: nine MFMAs in every step, the outputs right behind the last) keep the
     // round trip.
     constexpr bool LATE = CT > 0 && KBLK <= 3;
-    constexpr int TBL = (NSW == 1 && KBLK <= 3) ? 1 : 0;                // the service wave's tiles per interval: tile_first
-    constexpr int NACAP = 240 / (8 * KBLK);                              // 256 accumulation registers, 2 * KBLK * 4 per tile
+    constexpr int TBL = (NSW == 1 && KBLK <= 3) ? 1 : 0;                // the service wave's tiles per interval: row of BAR16_TILE_W
     constexpr int NA = ST < NACAP ? ST : NACAP;                               // of which this many keep their weights in accumulation registers
-    static_assert(NCW * CT + NSW * ST == NT16, "tile assignment");
-    static_assert(KBLK <= 4 && ST <= 21, "interval plan");
+    static_assert(NCW * CT + NSW * ST == NT16 && ST <= 21, "tile assignment");
     // dwords of one operand image: [step][k block][slot(k group, chunk)][8 halves]; the steps lie 32 banks apart so that the 16-lane
     // groups of a ds_read_b128 (lanes of two k groups and two steps each) find their pieces on different banks
     constexpr int OPSTEP = KBLK * 64 + 32;
@@ -89,35 +83,9 @@
 #pragma unroll
             for (int kb = 0; kb < KBLK; kb++) { hi[kb] = src[PK::proj(0, kb, 0) - PK::PROJ0 + lane]; lo[kb] = src[PK::proj(0, kb, 1) - PK::PROJ0 + lane]; }
         } else {
-            const int row = 16 * tile + pcol;
-            float u[KBLK][8];
-            float m = 0.0f;
-#pragma unroll
-            for (int kb = 0; kb < KBLK; kb++) {
-                const int k0 = 32 * kb + 8 * kg;
-                const bool kok = (I % 32 == 0) || k0 < I;
-                const float *src = iW + (size_t)row * I + (kok ? k0 : 0);
-                const float4 u0 = *reinterpret_cast<const float4 *>(src), u1 = *reinterpret_cast<const float4 *>(src + 4);
-                const float t[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    u[kb][j] = kok ? t[j] : 0.0f;
-                    m = fmaxf(m, fabsf(u[kb][j]));
-                }
-            }
-            float inv;
-            const float ws = pow2_scale(kgroup_max(m), inv);
-            if (kg == 0) invw_lds[row] = inv;
-#pragma unroll
-            for (int kb = 0; kb < KBLK; kb++) {
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const float v = u[kb][j] * ws;
-                    const _Float16 h = (_Float16)v;
-                    hi[kb][j] = h;
-                    lo[kb][j] = (_Float16)(v - (float)h);
-                }
-            }
+#define BAR16_PROJ_INV(row, inv) if (kg == 0) invw_lds[row] = inv;
+#include "bar16_proj_image.h"
+#undef BAR16_PROJ_INV
         }
     };
     // accumulator of a tile for group G1 -> vI ring: lane holds rows 4 kg + r of column (pstep, pc)
@@ -161,35 +129,12 @@
         } else {
 #pragma unroll
             for (int p = 0; p < 2; p++) {
-                const int row = 32 * w + 16 * p + (lane & 15);
-                float vz[KBS][8], vr[KBS][8], vc[KBS][8];
-                float mz = 0.0f, mr = 0.0f, mc = 0.0f;
-#pragma unroll
-                for (int i = 0; i < KBS; i++) {
-                    const int kb = (w + i) % KBS;
-#pragma unroll
-                    for (int j = 0; j < 8; j++) {
-                        const int k = 32 * kb + 16 * (j & 1) + 4 * g + (j >> 1);
-                        vz[i][j] = sW[(size_t)row * N + k];
-                        vr[i][j] = sW[(size_t)(N + row) * N + k];
-                        vc[i][j] = sW2[(size_t)row * N + k];
-                        mz = fmaxf(mz, fabsf(vz[i][j])); mr = fmaxf(mr, fabsf(vr[i][j])); mc = fmaxf(mc, fabsf(vc[i][j]));
-                    }
-                }
-                float iz, ir, ic_;
-                const float sz = pow2_scale(kgroup_max(mz), iz), sr = pow2_scale(kgroup_max(mr), ir), sc = pow2_scale(kgroup_max(mc), ic_);
-                inv_z[p] = iz; inv_r[p] = ir; inv_c[p] = ic_;   // (kgroup_max: every lane of a row has the row's scale, and its neuron IS its row)
-#pragma unroll
-                for (int i = 0; i < KBS; i++) {
-#pragma unroll
-                    for (int j = 0; j < 8; j++) {
-                        const float az = vz[i][j] * sz, ar = vr[i][j] * sr, ac = vc[i][j] * sc;
-                        const _Float16 hz = (_Float16)az, hr = (_Float16)ar, hc = (_Float16)ac;
-                        wz_hi[p][i][j] = hz; wz_lo[p][i][j] = (_Float16)(az - (float)hz);
-                        wr_hi[p][i][j] = hr; wr_lo[p][i][j] = (_Float16)(ar - (float)hr);
-                        wc_hi[p][i][j] = hc; wc_lo[p][i][j] = (_Float16)(ac - (float)hc);
-                    }
-                }
+                // (kgroup_max: every lane of a row has the row's scale, and its neuron IS its row)
+#define BAR16_REC_INV(iz, ir, ic_) inv_z[p] = iz; inv_r[p] = ir; inv_c[p] = ic_;
+#define BAR16_REC_W(a) a[p]
+#include "bar16_rec_image.h"
+#undef BAR16_REC_W
+#undef BAR16_REC_INV
                 // (one tile's rows at a time: interleaved, the two conversions are where the kernel needs the most registers, and the
                 //  64-wide instantiations must stay within the 256 that let two workgroups share a CU)
                 __builtin_amdgcn_sched_barrier(0);
@@ -734,7 +679,7 @@
         // which tiles an interval computes: the leader's intervals 1-3 carry the x split, so they get fewer
         auto project_interval = [&](auto KC, int G1) {
             constexpr int k = decltype(KC)::value;
-            constexpr int lo = tile_first(ST, k, TBL), hi = tile_first(ST, k + 1, TBL);
+            constexpr int lo = bar16_tile_first(ST, k, BAR16_TILE_W[TBL], 8), hi = bar16_tile_first(ST, k + 1, BAR16_TILE_W[TBL], 8);
             static_assert(hi - lo <= 3, "at most three tiles per interval");
             if constexpr (hi - lo == 1) project_tiles(ic<lo>{}, ic<ST>{}, G1);
             if constexpr (hi - lo == 2) project_tiles(ic<lo>{}, ic<lo + 1>{}, G1);
@@ -755,7 +700,7 @@
             if constexpr (k == 0) load_operands(G + 1);
             project_interval(KC, G + 1);
             if constexpr (tile_extra(ABL, k) > 0) {      // ablation: one tile of this interval once more (same value, same place)
-                constexpr int lo = tile_first(ST, k, TBL);
+                constexpr int lo = bar16_tile_first(ST, k, BAR16_TILE_W[TBL], 8);
                 project_tiles(ic<(lo < NA ? lo : NA - 1)>{}, ic<ST>{}, G + 1);
             }
             if (leader) {

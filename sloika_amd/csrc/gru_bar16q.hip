@@ -13,21 +13,16 @@
 //     in front of their epilogue anyway); the update gate's stay in ordinary registers, its MFMAs are the compiler's to interleave
 //     with the reset gate's epilogue, all in interval A, and its own epilogue covers the LDS round trip of interval B.
 // The recurrent products here are three-term splits where the other two plans take two MFMAs: results agree with theirs to float32 rounding.
+// The weight images are made by the statements all three plans include (bar16_proj_image.h, bar16_rec_image.h); the shape constants
+// are bar16_common.h's Bar16Dims.
 #include <limits.h>
 #include <stdlib.h>
 
 #include "bar16_common.h"
 
-// first tile of interval k (of four) when a service wave has st tiles per group and set; the leader splits set 0 in interval 0 and
-// set 1 in interval 2
-__host__ __device__ constexpr int tile_first_q(int st, int k)
-{
-    constexpr int w[4] = {2, 2, 2, 3};
-    int tot = 0, acc = 0;
-    for (int i = 0; i < 4; i++) tot += w[i];
-    for (int i = 0; i < k && i < 4; i++) acc += w[i];
-    return k >= 4 ? st : (acc * st + tot / 2) / tot < st ? (acc * st + tot / 2) / tot : st;
-}
+// a service wave's tiles per interval (of four), as proportions for bar16_tile_first (bar16_common.h); the leader splits set 0 in
+// interval 0 and set 1 in interval 2
+constexpr int BAR16Q_TILE_W[4] = {2, 2, 2, 3};
 
 template <int I, int N, bool SAVE>
 __global__ void __launch_bounds__(256, 1) gru_bar16q_kernel(const float *__restrict__ x, long ldx, const float *__restrict__ iW,
@@ -36,21 +31,14 @@ __global__ void __launch_bounds__(256, 1) gru_bar16q_kernel(const float *__restr
                                                             int T, int B, int reverse, const int *__restrict__ lens,
                                                             float *__restrict__ zr_out)
 {
-    static_assert(I % 16 == 0 && N % 32 == 0 && N <= 96, "unsupported size for the barrier-stepped GRU kernel");
-    constexpr int NCW = N / 32;                          // chain waves = 32-wide K blocks of the recurrent products
-    constexpr int KBS = N / 32;
-    constexpr int NSW = 4 - NCW;                         // service waves
-    constexpr int NT = N / 16;                           // tiles per gate
-    constexpr int NT16 = 3 * NT;                         // tiles of vI rows (z | r | c)
-    constexpr int KBLK = (I + 31) / 32;
+    using DM = Bar16Dims<I, N>;                          // bar16_common.h: what (I, N) alone decide
+    constexpr int NCW = DM::NCW, KBS = DM::KBS, NSW = DM::NSW, NT = DM::NT, NT16 = DM::NT16, KBLK = DM::KBLK, NACAP = DM::NACAP;
     constexpr int GS = 2;                                // steps per projection group (16 MFMA columns = 2 steps x 8 chunks of a set)
     constexpr int R = 2 * GS;                            // vI ring: group G+1 is written while group G is consumed
     constexpr int CT = NCW == 3 ? 3 : 0;                 // projection tiles of a chain wave (weights in accumulation registers)
     constexpr int ST = (NT16 - NCW * CT) / NSW;          // ... of a service wave
-    constexpr int NACAP = 240 / (8 * KBLK);              // 256 accumulation registers, 2 * KBLK * 4 per tile
     constexpr int NA = ST < NACAP ? ST : NACAP;
-    static_assert(NCW * CT + NSW * ST == NT16, "tile assignment");
-    static_assert(KBLK <= 4 && ST <= 21, "interval plan");
+    static_assert(NCW * CT + NSW * ST == NT16 && ST <= 21, "tile assignment");
     constexpr int OPIMG = GS * KBLK * 128;               // dwords of one operand image: [step][k block][k group][chunk of 8][8 halves]
     constexpr int VSTEP = NT16 * 128;                    // floats of one step's vI of a set: [tile][g][chunk of 8][r]
     constexpr int IMG = KBS * 4 * 16 * 4;                // dwords of a state image: [k block][g][chunk of 16][4 packed pairs]
@@ -75,35 +63,9 @@ __global__ void __launch_bounds__(256, 1) gru_bar16q_kernel(const float *__restr
     auto opimg = [&](int grp, int set) { return ((grp & 1) * 2 + set) * OPIMG + poff; };
     // iW tile -> A operands (lane: row pcol of the tile, k = 32 kb + 8 kg + 0..7), row scale remembered in invw_lds
     auto load_tile = [&](int tile, half8 *hi, half8 *lo) {
-        const int row = 16 * tile + pcol;
-        float u[KBLK][8];
-        float m = 0.0f;
-#pragma unroll
-        for (int kb = 0; kb < KBLK; kb++) {
-            const int k0 = 32 * kb + 8 * kg;
-            const bool kok = (I % 32 == 0) || k0 < I;
-            const float *src = iW + (size_t)row * I + (kok ? k0 : 0);
-            const float4 u0 = *reinterpret_cast<const float4 *>(src), u1 = *reinterpret_cast<const float4 *>(src + 4);
-            const float t[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                u[kb][j] = kok ? t[j] : 0.0f;
-                m = fmaxf(m, fabsf(u[kb][j]));
-            }
-        }
-        float inv;
-        const float ws = pow2_scale(kgroup_max(m), inv);
-        if (kg == 0) invw_lds[row] = inv;
-#pragma unroll
-        for (int kb = 0; kb < KBLK; kb++) {
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const float v = u[kb][j] * ws;
-                const _Float16 h = (_Float16)v;
-                hi[kb][j] = h;
-                lo[kb][j] = (_Float16)(v - (float)h);
-            }
-        }
+#define BAR16_PROJ_INV(row, inv) if (kg == 0) invw_lds[row] = inv;
+#include "bar16_proj_image.h"
+#undef BAR16_PROJ_INV
     };
     // accumulator of a tile for group G1 of a set -> vI ring: lane holds rows 4 kg + r of column (pstep, pc)
     auto proj_out = [&](int tile, const f32x4 &acc, int G1, int set) {
@@ -131,38 +93,15 @@ __global__ void __launch_bounds__(256, 1) gru_bar16q_kernel(const float *__restr
         float inv_z[2][4], inv_r[2][4], inv_c[2][4];
 #pragma unroll
         for (int p = 0; p < 2; p++) {
-            const int row = 32 * w + 16 * p + (lane & 15);
-            float vz[KBS][8], vr[KBS][8], vc[KBS][8];
-            float mz = 0.0f, mr = 0.0f, mc = 0.0f;
-#pragma unroll
-            for (int i = 0; i < KBS; i++) {
-                const int kb = (w + i) % KBS;
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const int k = 32 * kb + 16 * (j & 1) + 4 * g + (j >> 1);
-                    vz[i][j] = sW[(size_t)row * N + k];
-                    vr[i][j] = sW[(size_t)(N + row) * N + k];
-                    vc[i][j] = sW2[(size_t)row * N + k];
-                    mz = fmaxf(mz, fabsf(vz[i][j])); mr = fmaxf(mr, fabsf(vr[i][j])); mc = fmaxf(mc, fabsf(vc[i][j]));
-                }
-            }
-            float iz, ir, ic_;
-            const float sz = pow2_scale(kgroup_max(mz), iz), sr = pow2_scale(kgroup_max(mr), ir), sc = pow2_scale(kgroup_max(mc), ic_);
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                inv_z[p][j] = __shfl(iz, 4 * g + j); inv_r[p][j] = __shfl(ir, 4 * g + j); inv_c[p][j] = __shfl(ic_, 4 * g + j);
-            }
-#pragma unroll
-            for (int i = 0; i < KBS; i++) {
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const float az = vz[i][j] * sz, ar = vr[i][j] * sr, ac = vc[i][j] * sc;
-                    const _Float16 hz = (_Float16)az, hr = (_Float16)ar, hc = (_Float16)ac;
-                    wz_hi[p][i][j] = hz; wz_lo[p][i][j] = (_Float16)(az - (float)hz);
-                    wr_hi[p][i][j] = hr; wr_lo[p][i][j] = (_Float16)(ar - (float)hr);
-                    wc_hi[p][i][j] = hc; wc_lo[p][i][j] = (_Float16)(ac - (float)hc);
-                }
-            }
+            // (every lane of a row has the row's scale: the owner of rows 4g + j takes it from a lane of that row)
+#define BAR16_REC_INV(iz, ir, ic_)                                                                                             \
+    _Pragma("unroll") for (int j = 0; j < 4; j++) {                                                                            \
+        inv_z[p][j] = __shfl(iz, 4 * g + j); inv_r[p][j] = __shfl(ir, 4 * g + j); inv_c[p][j] = __shfl(ic_, 4 * g + j);       \
+    }
+#define BAR16_REC_W(a) a[p]
+#include "bar16_rec_image.h"
+#undef BAR16_REC_W
+#undef BAR16_REC_INV
         }
 #pragma unroll
         for (int p = 0; p < 2; p++) {
@@ -590,7 +529,7 @@ __global__ void __launch_bounds__(256, 1) gru_bar16q_kernel(const float *__restr
         // intervals 2 and 3, and requests the same set of group G + 3 right behind
         auto project_interval = [&](auto KC, int G1) {
             constexpr int k = decltype(KC)::value;
-            constexpr int lo = tile_first_q(ST, k), hi = tile_first_q(ST, k + 1);
+            constexpr int lo = bar16_tile_first(ST, k, BAR16Q_TILE_W, 4), hi = bar16_tile_first(ST, k + 1, BAR16Q_TILE_W, 4);
             static_for<lo, hi>([&](auto TC) { project_tile(TC, G1); });
             if (leader && G1 > 0) {
                 constexpr int sset = k / 2;
