@@ -842,6 +842,39 @@ SLK_API int slk_forward_score_batch_f64(const double *post, long ld, const int64
                                         int nstate, const int32_t *seq, const int64_t *pos_off, int nread, int max_npos, int blank,
                                         int full, double *score_out, slk_stream_t stream);
 
+/* f6b. Forward-backward over the same recursion: with what probability each row of a pair emits each symbol, summed over all
+ * alignments (csrc/forward_backward.hip, design/forward_backward.md).  With f the forward variables of f6 and b their mirror image
+ * (b_T = 1, full: e_L; b_{t-1}[j] = b_t[j] p_t[blank] + b_t[j+1] p_t[seq[j]]), row t has stay_t[j] = f_{t-1}[j] p_t[blank] b_t[j],
+ * move_t[j] = f_{t-1}[j-1] p_t[seq[j-1]] b_t[j] and z_t their total; occ[t, blank] = sum_j stay_t[j] / z_t and occ[t, c] = the sum
+ * of move_t[j] / z_t over the positions that carry c (a symbol equal to `blank` adds to that column).  occ[t, c] = p_t[c] times the
+ * derivative of the score by p_t[c]; every row of occ sums to 1.  A pair's results have the same bits alone, in any batch, in either
+ * layout, with any ld / occ_ld and in any launch.
+ *   post .. min_prob: as for slk_forward_score_batch_*, which refuses what these refuse; in addition nstate <= 8192
+ *     (SLK_ERR_UNSUPPORTED: one 64-bit slot per column and row parity lives in LDS).
+ *   score:[nread] float64, the bits slk_forward_score_batch_* returns for the same pair.
+ *   occ: row t of pair b is row row_off[b] + t * row_step of occ, rows occ_ld >= nstate values apart; float32 for _f32 (the float64
+ *     value rounded once), float64 for _f64.  The entry zero-fills columns 0 .. nstate - 1 of the nrow[b] rows of every accepted pair
+ *     and writes nothing else; a row whose z_t is 0 or not finite (full with more positions than rows, an end state that underflowed)
+ *     stays 0.  May be null.
+ *   emit_row:[sum npos] int32, emit_prob:[sum npos] float64, behind pos_off like seq: per position the largest move_t[j] / z_t and the
+ *     lowest row that attains it; -1 and 0 for a position that never had a positive value (a pair of no rows among them).  Either may
+ *     be null.
+ *   A refused pair (longer than max_npos, or a symbol that is no column) gets a NaN score; its occ, emit_row and emit_prob are left
+ *     untouched and nothing is read out of bounds.
+ *   workspace: 16-byte aligned, slk_forward_backward_workspace_bytes(nread, nrow, pos_off) bytes -- the exact requirement, computed
+ *     from HOST copies of nrow and pos_off: the pairs' offsets, then 256 * ppt float64 per row of a pair.  A smaller workspace_bytes
+ *     returns SLK_ERR_WORKSPACE and nothing is written.  The entry copies nrow and pos_off to the host to check this, so it
+ *     synchronises with `stream` once. */
+SLK_API size_t slk_forward_backward_workspace_bytes(int nread, const int32_t *nrow, const int64_t *pos_off);
+SLK_API int slk_forward_backward_batch_f32(const float *post, long ld, const int64_t *row_off, long row_step, const int32_t *nrow,
+                                           int nstate, const int32_t *seq, const int64_t *pos_off, int nread, int max_npos, int blank,
+                                           int full, float min_prob, double *score, float *occ, long occ_ld, int32_t *emit_row,
+                                           double *emit_prob, void *workspace, size_t workspace_bytes, slk_stream_t stream);
+SLK_API int slk_forward_backward_batch_f64(const double *post, long ld, const int64_t *row_off, long row_step, const int32_t *nrow,
+                                           int nstate, const int32_t *seq, const int64_t *pos_off, int nread, int max_npos, int blank,
+                                           int full, double *score, double *occ, long occ_ld, int32_t *emit_row, double *emit_prob,
+                                           void *workspace, size_t workspace_bytes, slk_stream_t stream);
+
 /* f7. Where on a genome a call lies, and the reference of each read cut from it: the locating half of what misc/align.py gets from
  * `bwa mem -k14 -W20 -r10 ... genome.fa calls.fa` (align.py:46-67) and the cut of misc/get_refs_from_sam.py:40-68, on the device
  * (csrc/genome_map.hip, design/genome_map.md).  A seed-and-vote stage chooses, per query and strand, a band of diagonals; the

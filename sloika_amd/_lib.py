@@ -156,6 +156,10 @@ PROTOTYPES = {
     "slk_forward_score_max_positions": (_i, []),
     "slk_forward_score_batch_f32": (_i, [_vp, _l, _vp, _l, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "slk_forward_score_batch_f64": (_i, [_vp, _l, _vp, _l, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "slk_forward_backward_workspace_bytes": (_sz, [_i, _vp, _vp]),
+    "slk_forward_backward_batch_f32": (_i, [_vp, _l, _vp, _l, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _l, _vp, _vp, _vp, _sz,
+                                            _vp]),
+    "slk_forward_backward_batch_f64": (_i, [_vp, _l, _vp, _l, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
     "slk_genome_kmer_keys_u8": (_i, [_vp, _vp, _i, _l, _i, _vp, _vp, _vp]),
     "slk_genome_seed_workspace_bytes": (_sz, [_i, _i, _l, _i]),
     "slk_genome_seed_votes_u8": (_i, [_vp, _l, _vp, _i, _i, _vp, _i, _l, _i, _i, _i, _vp, _vp, _sz, _vp]),

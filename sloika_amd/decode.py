@@ -7,6 +7,8 @@
     score(post, seq, full=False)                           decode.py:96-105
     forwards(post, seq, full=False)                        decode.py:108-139    -> float64 (csrc/forward_score.hip)
     forwards_batch(post[T,B,S] | rows + row_off, seqs)     batched extension    -> scores[B] float64, on the device
+    forwards_backwards(post, seq, full=False)              the backward half    -> (score, occ, emit_row, emit_prob)
+    forwards_backwards_batch(post | rows + row_off, seqs)  (csrc/forward_backward.hip, design/forward_backward.md)
 
 Inputs may be numpy arrays or device tensors; float32 arithmetic (the network's dtype).  float64 input is
 converted to float32 first -- unlike numpy, which would then decode in float64.  The forward score is the exception:
@@ -223,21 +225,9 @@ def _forward_post(post):
     return torch.from_numpy(np.ascontiguousarray(a)).to(D.device())
 
 
-def forwards_batch(post, seqs, lengths=None, full=False, blank=-1, min_prob=None, row_off=None):
-    """decode.forwards (decode.py:108-139) for a batch of (posterior, sequence) pairs in one launch (csrc/forward_score.hip): the
-    log-likelihood of each sequence under its posterior, summed over all alignments.
-
-    post: float32 or float64, numpy or device tensor, either
-      * [T, B, S], the network layout, read where it lies (the state axis contiguous, rows evenly spaced: a [:, :, :S] view of wider
-        rows is fine); pair b runs over its first lengths[b] rows (all T when lengths is None; host integers, or an int32
-        device tensor whose values the caller keeps within 0 .. T), or
-      * [R, S] packed rows with row_off [B] or [B + 1] (host integers): pair b owns rows row_off[b] .. row_off[b] + lengths[b] - 1;
-        lengths defaults to the differences of a [B + 1] row_off.
-    seqs: one sequence of column indices per pair (a pair may have none).  blank: the column of the stay emission, -1 = the last, as
-    in the reference.  min_prob: if given (float32 only), every value goes through decode.prepare_post's transform first, i.e. `post`
-    is the raw network output.  full: force full length mapping.
-
-    Returns a device float64 tensor [B].  A sequence longer than forward_max_positions() raises ValueError."""
+def _forward_pairs(post, seqs, lengths, blank, min_prob, row_off, who):
+    """The arguments of forwards_batch / forwards_backwards_batch, checked, laid out as the kernels read them and uploaded."""
+    import types
     import torch
     shape = tuple(post.shape)
     if len(shape) == 3 and row_off is None:
@@ -256,9 +246,9 @@ def forwards_batch(post, seqs, lengths=None, full=False, blank=-1, min_prob=None
         row_off = row_off[:B]
         packed = True
     else:
-        raise ValueError("forwards_batch expects a [time, batch, state] posterior, or [rows, state] with row_off")
+        raise ValueError("%s expects a [time, batch, state] posterior, or [rows, state] with row_off" % who)
     if len(seqs) != B or B < 1:
-        raise ValueError("forwards_batch needs one sequence per pair (%d sequences for %d pairs)" % (len(seqs), B))
+        raise ValueError("%s needs one sequence per pair (%d sequences for %d pairs)" % (who, len(seqs), B))
     if S < 1:
         raise ValueError("posterior has no states")
     blank = int(blank)
@@ -276,7 +266,7 @@ def forwards_batch(post, seqs, lengths=None, full=False, blank=-1, min_prob=None
         raise ValueError("sequence symbols must be columns 0 .. %d of the posterior" % (S - 1))
     if min_prob is not None and not 0.0 <= float(min_prob) < 1.0:
         raise ValueError("min_prob must lie in [0, 1)")
-    lens_dev = None
+    lens = lens_dev = None
     if isinstance(lengths, torch.Tensor):
         if lengths.dtype != torch.int32 or lengths.numel() != B or not lengths.is_cuda or packed:
             raise ValueError("device lengths must be int32 with one entry per chunk of a [time, batch, state] posterior")
@@ -292,27 +282,50 @@ def forwards_batch(post, seqs, lengths=None, full=False, blank=-1, min_prob=None
             raise ValueError("a pair cannot have more than the posterior's %d rows" % T)
     if min_prob is not None and float(min_prob) > 0.0 and not str(post.dtype).endswith("float32"):
         raise ValueError("min_prob applies to float32 posteriors (decode.prepare_post is float32 arithmetic)")
-    from . import device as D
     pd = _forward_post(post)
     if pd.stride(-1) != 1 or (not packed and pd.stride(0) != B * pd.stride(1)) or pd.stride(-2) < S:
         pd = pd.contiguous()
-    ld = pd.stride(-2)
-    dev = pd.device
+    q = types.SimpleNamespace()
+    q.pd, q.ld, q.B, q.S, q.packed, q.blank, q.npos, q.lens = pd, pd.stride(-2), B, S, packed, blank, npos, lens
+    q.nrows = None if packed else T
     if packed:
-        roff, step = row_off, 1
+        q.roff, q.step = row_off, 1
     else:
-        roff, step = np.arange(B, dtype=np.int64), B
-    pos_off = np.concatenate([[0], np.cumsum(npos)]).astype(np.int64)
+        q.roff, q.step = np.arange(B, dtype=np.int64), B
+    q.pos_off = np.concatenate([[0], np.cumsum(npos)]).astype(np.int64)
     # one upload for the offsets; the sequences and (host) lengths as int32 behind them
-    offs = torch.as_tensor(np.concatenate([roff, pos_off])).to(dev)
+    q.offs = torch.as_tensor(np.concatenate([q.roff, q.pos_off])).to(pd.device)
     tail = lens.astype(np.int32) if lens_dev is None else np.zeros(1, np.int32)      # (never an empty upload)
-    ints_d = torch.as_tensor(np.concatenate([cat.astype(np.int32), tail])).to(dev)
-    nrow_ptr = lens_dev.data_ptr() if lens_dev is not None else ints_d.data_ptr() + 4 * cat.size
-    score = D.scratch(B, torch.float64, dev, result=True)
+    q.ints = torch.as_tensor(np.concatenate([cat.astype(np.int32), tail])).to(pd.device)
+    q.lens_dev = lens_dev
+    q.nrow_ptr = lens_dev.data_ptr() if lens_dev is not None else q.ints.data_ptr() + 4 * cat.size
+    return q
+
+
+def forwards_batch(post, seqs, lengths=None, full=False, blank=-1, min_prob=None, row_off=None):
+    """decode.forwards (decode.py:108-139) for a batch of (posterior, sequence) pairs in one launch (csrc/forward_score.hip): the
+    log-likelihood of each sequence under its posterior, summed over all alignments.
+
+    post: float32 or float64, numpy or device tensor, either
+      * [T, B, S], the network layout, read where it lies (the state axis contiguous, rows evenly spaced: a [:, :, :S] view of wider
+        rows is fine); pair b runs over its first lengths[b] rows (all T when lengths is None; host integers, or an int32
+        device tensor whose values the caller keeps within 0 .. T), or
+      * [R, S] packed rows with row_off [B] or [B + 1] (host integers): pair b owns rows row_off[b] .. row_off[b] + lengths[b] - 1;
+        lengths defaults to the differences of a [B + 1] row_off.
+    seqs: one sequence of column indices per pair (a pair may have none).  blank: the column of the stay emission, -1 = the last, as
+    in the reference.  min_prob: if given (float32 only), every value goes through decode.prepare_post's transform first, i.e. `post`
+    is the raw network output.  full: force full length mapping.
+
+    Returns a device float64 tensor [B].  A sequence longer than forward_max_positions() raises ValueError."""
+    import torch
+    from . import device as D
+    q = _forward_pairs(post, seqs, lengths, blank, min_prob, row_off, "forwards_batch")
+    pd, B = q.pd, q.B
+    score = D.scratch(B, torch.float64, pd.device, result=True)
     L = _lib.lib()
-    common = (pd.data_ptr(), ld, offs.data_ptr(), step, nrow_ptr, S, ints_d.data_ptr(), offs.data_ptr() + 8 * B, B, max(npos), blank,
-              int(bool(full)))
-    rows = float(sum(npos) + B) * (float(T) if not packed else float(np.mean(lens)))
+    common = (pd.data_ptr(), q.ld, q.offs.data_ptr(), q.step, q.nrow_ptr, q.S, q.ints.data_ptr(), q.offs.data_ptr() + 8 * B, B,
+              max(q.npos), q.blank, int(bool(full)))
+    rows = float(sum(q.npos) + B) * (float(q.nrows) if not q.packed else float(np.mean(q.lens)))
     with profiler.region("forward_score", 3.0 * rows, rows * pd.element_size()):
         if pd.dtype == torch.float32:
             rc = L.slk_forward_score_batch_f32(*common, float(min_prob or 0.0), score.data_ptr(), D.stream_ptr())
@@ -320,6 +333,96 @@ def forwards_batch(post, seqs, lengths=None, full=False, blank=-1, min_prob=None
             rc = L.slk_forward_score_batch_f64(*common, score.data_ptr(), D.stream_ptr())
     _lib.check(rc, "decode.forwards_batch")
     return score
+
+
+#: most positions of a posterior row (csrc/forward_backward.hip: one 64-bit slot per column and row parity in LDS)
+FORWARD_BACKWARD_MAX_STATES = 8192
+
+
+def forwards_backwards_batch(post, seqs, lengths=None, full=False, blank=-1, min_prob=None, row_off=None, occupancy=True,
+                             positions=True, workspace_limit=None):
+    """Forward-backward over decode.forwards' recursion for a batch of (posterior, sequence) pairs (csrc/forward_backward.hip,
+    design/forward_backward.md): with what probability each row emits each symbol, summed over all alignments.
+
+    post, seqs, lengths, full, blank, min_prob, row_off: as in forwards_batch (with min_prob the occupancies refer to the transformed
+    values).  At most FORWARD_BACKWARD_MAX_STATES columns.
+
+    -> (score, occ, emit_row, emit_prob):
+      score     device float64 [B], the bits forwards_batch returns;
+      occ       device tensor with the shape and dtype of `post` (None unless `occupancy`): occ[t, b, c], or occ[row, c] for packed
+                rows, is the probability that row t of pair b emits column c -- p[t, c] times the derivative of the score by p[t, c],
+                so occ - p is the score's gradient by the logits of a softmax.  Every row of a pair with a finite score sums to 1;
+                rows a pair does not own, and the rows of a `full` pair whose score is -inf, are 0;
+      emit_row  list of B device int32 views (None unless `positions`): per position the row that most probably emits it (the lowest
+                such row), -1 if no row can;
+      emit_prob list of B device float64 views: that probability.
+    The forward variables of a launch live in a workspace of 8 * 256 * ppt bytes per row of a pair (ppt = 1, 2, .. 32, the smallest
+    with 256 * ppt > len(seq)); the batch runs as consecutive launches whose workspace stays within `workspace_limit` bytes (default
+    transducer.WORKSPACE_LIMIT; the results do not depend on the split).  A pair that needs more on its own raises ValueError."""
+    import ctypes
+    import torch
+    from . import device as D
+    from . import transducer
+    q = _forward_pairs(post, seqs, lengths, blank, min_prob, row_off, "forwards_backwards_batch")
+    pd, B, S = q.pd, q.B, q.S
+    if S > FORWARD_BACKWARD_MAX_STATES:
+        raise ValueError("a posterior of %d states is above forward-backward's limit of %d" % (S, FORWARD_BACKWARD_MAX_STATES))
+    limit = transducer.WORKSPACE_LIMIT if workspace_limit is None else int(workspace_limit)
+    lens = (q.lens if q.lens is not None else q.lens_dev.cpu().numpy()).astype(np.int32)
+    L = _lib.lib()
+
+    def need(lo, hi):
+        nrow = np.ascontiguousarray(lens[lo:hi])
+        pos = np.ascontiguousarray(q.pos_off[lo:hi + 1])
+        return int(L.slk_forward_backward_workspace_bytes(hi - lo, nrow.ctypes.data_as(ctypes.c_void_p), pos.ctypes.data_as(ctypes.c_void_p)))
+
+    # a pair adds its rows and the 8 bytes of its offset to a launch's workspace; the table of offsets of n pairs takes less than
+    # 8 n + 512 bytes (alone, a pair's takes 256)
+    alone = [need(b, b + 1) for b in range(B)]
+    if max(alone) > limit:
+        b = int(np.argmax(alone))
+        raise ValueError("pair %d needs %d bytes of workspace, above the workspace_limit of %d" % (b, alone[b], limit))
+    runs = transducer.workspace_runs([n - 256 + 8 for n in alone], max(limit - 512, 0))
+    dev = pd.device
+    score = D.scratch(B, torch.float64, dev, result=True)
+    occ = None
+    if occupancy:
+        # (rows no pair owns are not written by the kernel: zeros, unless every row is owned)
+        whole = not q.packed and q.lens is not None and int(lens.min()) == q.nrows
+        shape = tuple(pd.shape[:-1]) + (q.ld,)
+        occ = (torch.empty if whole else torch.zeros)(shape, dtype=pd.dtype, device=dev)[..., :S]
+    npos_all = int(q.pos_off[-1])
+    erow = torch.full((max(npos_all, 1),), -1, dtype=torch.int32, device=dev) if positions else None
+    eprob = torch.zeros((max(npos_all, 1),), dtype=torch.float64, device=dev) if positions else None
+    ws = torch.empty(max(need(lo, hi) for lo, hi in runs), dtype=torch.uint8, device=dev)
+    rows = float(sum(q.npos) + B) * (float(q.nrows) if not q.packed else float(np.mean(lens)))
+    with profiler.region("forward_backward", 12.0 * rows, rows * (pd.element_size() + 16)):
+        for lo, hi in runs:
+            head = (pd.data_ptr(), q.ld, q.offs.data_ptr() + 8 * lo, q.step, q.nrow_ptr + 4 * lo, S, q.ints.data_ptr(),
+                    q.offs.data_ptr() + 8 * (B + lo), hi - lo, max(q.npos[lo:hi]), q.blank, int(bool(full)))
+            tail = (score.data_ptr() + 8 * lo, D.ptr(occ), q.ld, D.ptr(erow), D.ptr(eprob), ws.data_ptr(), need(lo, hi), D.stream_ptr())
+            if pd.dtype == torch.float32:
+                rc = L.slk_forward_backward_batch_f32(*head, float(min_prob or 0.0), *tail)
+            else:
+                rc = L.slk_forward_backward_batch_f64(*head, *tail)
+            _lib.check(rc, "decode.forwards_backwards_batch")
+    if positions:
+        emit_row = [erow[q.pos_off[b]:q.pos_off[b + 1]] for b in range(B)]
+        emit_prob = [eprob[q.pos_off[b]:q.pos_off[b + 1]] for b in range(B)]
+    else:
+        emit_row = emit_prob = None
+    return score, occ, emit_row, emit_prob
+
+
+def forwards_backwards(post, seq, full=False):
+    """Forward-backward for one pair with the reference's conventions (a 2-D posterior, the blank in the last column, as
+    decode.forwards): -> numpy (score float64, occ [time, nstate] with the dtype of `post`, emit_row int32 [len(seq)], emit_prob
+    float64 [len(seq)]); see forwards_backwards_batch."""
+    if len(post.shape) != 2:
+        raise ValueError("forwards_backwards expects a [time, state] posterior")
+    T, S = post.shape
+    score, occ, emit_row, emit_prob = forwards_backwards_batch(post, [seq], full=full, row_off=[0, T])
+    return np.float64(score[0].item()), occ.cpu().numpy(), emit_row[0].cpu().numpy(), emit_prob[0].cpu().numpy()
 
 
 def forwards(post, seq, full=False):

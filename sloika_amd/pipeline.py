@@ -334,12 +334,32 @@ class Basecaller(object):
         call_chunks holds, so a call can be scored against its own chunk -- or a base string, cut into its k-mers (bio.seq_to_kmers)
         and numbered by bio.kmer_mapping.  full, scaling: as decode.forwards / call_chunks.
         -> device float64 [B], natural-log likelihoods."""
+        cols = self._sequence_columns(chunks, sequences, "score_chunks", "forward score")
+        with self._scope():
+            post = self.posteriors(chunks, scaling)
+            return decode.forwards_batch(post, cols, full=full, blank=0, min_prob=self.min_prob)
+
+    def occupancy_chunks(self, chunks, sequences, full=True, scaling=None):
+        """With what probability each row of a chunk's posterior emits each state under a sequence, summed over all alignments
+        (decode.forwards_backwards_batch, design/forward_backward.md): the soft counterpart of the remap's one best alignment.
+        chunks, sequences, full, scaling: as score_chunks, on the same prepared posterior.
+        -> (ll device float64 [B], the bits score_chunks returns; occ device float32 [T', B, nstate]: occ - posterior is the gradient of
+        ll by the logits; emit_row, emit_prob: lists of B device views, per position the row that most probably emits it and that
+        probability)."""
+        cols = self._sequence_columns(chunks, sequences, "occupancy_chunks", "occupancy")
+        with self._scope():
+            post = self.posteriors(chunks, scaling)
+            return decode.forwards_backwards_batch(post, cols, full=full, blank=0, min_prob=self.min_prob)
+
+    def _sequence_columns(self, chunks, sequences, who, what):
+        """The posterior columns of one sequence per chunk, each k-mer states or a base string (score_chunks): state + 1, column 0 is
+        the blank (variables.nstate, transducer=True)."""
         import numpy as np
         from . import bio
         if not self.transducer:
-            raise NotImplementedError("score_chunks needs a transducer model: without a blank state there is no forward score")
+            raise NotImplementedError("%s needs a transducer model: without a blank state there is no %s" % (who, what))
         if len(sequences) != len(chunks):
-            raise ValueError("score_chunks needs one sequence per chunk (%d for %d)" % (len(sequences), len(chunks)))
+            raise ValueError("%s needs one sequence per chunk (%d for %d)" % (who, len(sequences), len(chunks)))
         mapping = None
         cols = []
         for q in sequences:
@@ -357,11 +377,8 @@ class Basecaller(object):
                 st = np.asarray(q.cpu() if hasattr(q, "cpu") else q).astype(np.int64).reshape(-1)
                 if st.size and (st.min() < 0 or st.max() >= self.nbase ** self.kmer_len):
                     raise ValueError("k-mer states must lie in 0 .. %d" % (self.nbase ** self.kmer_len - 1))
-            cols.append(st + 1)                                 # column 0 is the blank (variables.nstate, transducer=True)
-
-        with self._scope():
-            post = self.posteriors(chunks, scaling)
-            return decode.forwards_batch(post, cols, full=full, blank=0, min_prob=self.min_prob)
+            cols.append(st + 1)
+        return cols
 
     def _call_padded(self, padded, nsamp):
         """One padded batch of trimmed reads resident on the device ([B, Lmax], read b in its first nsamp[b] samples): per-read
