@@ -678,6 +678,21 @@ SLK_API int slk_lstm_backward16_f32(const float *dy, long lddy, const float *gat
 SLK_API int slk_softmax_xent_grad_f32(float *logits, long ld, const float *stats, const int32_t *labels, const float *weights, int T,
                               int B, int nstate, int drop, float min_prob, float *loss_rows, float *correct_rows,
                               slk_stream_t stream);
+/* The sequence loss in the same place (csrc/seq_loss.hip, design/sequence_loss.md): dL/dlogits of L = -sum_b chunk_scale[b] * ll_b,
+ * ll_b the forward score of chunk b's sequence under min_prob + (1 - min_prob) softmax(logits), in place over the logits written by
+ * slk_linear_rowstats_* (stats:[M][2] = max, 1/sum).  occ:[T][B] rows of occ_ld floats and score:[B] are what
+ * slk_forward_backward_batch_f32 wrote for that posterior in the network layout (row_step = B) with the same min_prob.  Per row
+ * m = t*B + b:  p = exp(l - max) / sum, p' = min_prob + (1 - min_prob) p, w = occ (1 - min_prob) p / p' (0 where occ is 0),
+ * l_k <- -chunk_scale[b] (w_k - p_k sum_j w_j) for k < nstate; columns nstate..ld-1 are set to zero and nothing else is written.
+ * Every row of a chunk whose score is not finite (NaN: refused, its occ was never written and is not read here; -inf: no alignment)
+ * becomes exact zeros, columns 0..ld-1.  A row's result depends on that row, score[b] and chunk_scale[b] only: the sum over j runs
+ * in a fixed order (per lane ascending columns, then the wave's xor tree), the same at every alignment and batch size.
+ * nstate >= 2, ld >= nstate, occ_ld >= nstate, 0 <= min_prob < 1, else SLK_ERR_INVALID_ARG; rows of more than SLK_SEQ_GRAD_MAX_LD
+ * floats (or more than 2^33 rows): SLK_ERR_UNSUPPORTED.  16-byte accesses where ld (occ_ld) is a multiple of 4 and the base is
+ * 16-byte aligned; rows of up to 2048 floats are read once. */
+#define SLK_SEQ_GRAD_MAX_LD (1L << 24)
+SLK_API int slk_softmax_seq_grad_f32(float *logits, long ld, const float *stats, const float *occ, long occ_ld, const double *score,
+                             const float *chunk_scale, int T, int B, int nstate, float min_prob, slk_stream_t stream);
 /* The softmax layer of a training step WITHOUT a logits tensor: the layer's products (pre-split weights, as for
  * slk_linear_rowstats_f16x3) are computed twice -- a statistics pass that stores nothing but, per row, the loss term, the accuracy
  * term and four floats in xrow:[M][4], and a gradient pass that stores grad:[M][ld] = dL/dlogits (columns N..ld-1 zero) -- instead

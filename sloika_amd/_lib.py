@@ -127,6 +127,7 @@ PROTOTYPES = {
     "slk_lstm_backward_f32": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "slk_lstm_backward16_f32": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "slk_softmax_xent_grad_f32": (_i, [_vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "slk_softmax_seq_grad_f32": (_i, [_vp, _l, _vp, _vp, _l, _vp, _vp, _i, _i, _i, _f, _vp]),
     "slk_linear_xent_grad_f16x3": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "slk_reduce_sum_f32": (_i, [_vp, _sz, _i, _vp, _vp]),
     "slk_reduce_rows_sum_f32": (_i, [_vp, _i, _sz, _vp, _vp, _vp]),

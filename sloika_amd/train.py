@@ -361,15 +361,8 @@ class TrainingStep(object):
         from . import device as D
         L = _lib.lib()
         st = layers._stream
-        x = D.to_dev(x)
-        if x.dim() != 3 or x.shape[2] != self.network.insize:
-            raise ValueError("x must be [T, B, %d]" % self.network.insize)
-        T, B = int(x.shape[0]), int(x.shape[1])
-        # ---- forward: the inference kernels, keeping every layer's output -------------------------------------------
-        h_top, tapes = x, []
-        for sub in self.body:
-            h_top, tp = self._forward(sub, h_top, False)
-            tapes.append(tp)
+        x, h_top, tapes = self._forward_tapes(x)
+        B = int(x.shape[1])
         sm = self.softmax
         To = int(h_top.shape[0])
         M = To * B
@@ -403,6 +396,36 @@ class TrainingStep(object):
             _lib.check(L.slk_reduce_rows_sum_f32(rows.data_ptr(), 2, M, sc.data_ptr(), self._sum_scratch.data_ptr(), st()), "reduce")
             if self.l2 != 0.0:
                 _lib.check(L.slk_reduce_sum_f32(self.flat.data_ptr(), self.flat.numel(), 1, sc[2:].data_ptr(), st()), "reduce")
+        box = [logits]
+        del logits
+        self._backward_from_logits(box, ld, h_top, tapes)
+        allreduce_step_scalars_(sc)
+
+    def _forward_tapes(self, x, keep=True):
+        """(x on the device, the softmax layer's input, the layers' tapes): the forward pass on the inference kernels, keeping every
+        layer's output -- or none of them (keep=False: the same kernels and bits, each tape dropped as soon as its layer has run)."""
+        from . import device as D
+        x = D.to_dev(x)
+        if x.dim() != 3 or x.shape[2] != self.network.insize:
+            raise ValueError("x must be [T, B, %d]" % self.network.insize)
+        h_top, tapes = x, []
+        for sub in self.body:
+            h_top, tp = self._forward(sub, h_top, False)
+            if keep:
+                tapes.append(tp)
+            del tp
+        return x, h_top, tapes
+
+    def _backward_from_logits(self, box, ld, h_top, tapes):
+        """From d loss / d logits [M][ld] (columns past the states zero) down: the softmax layer's weight gradient and dL/dx, the layers
+        in front of it top down, then the data-parallel sum of self.grad (self.gscale turns it into the mean).  `box` is a list holding
+        that matrix and nothing else refers to it: it is taken out and released before the layers' reverse passes allocate; `tapes` is
+        consumed likewise."""
+        import torch
+        logits = box.pop()
+        sm = self.softmax
+        To, B = int(h_top.shape[0]), int(h_top.shape[1])
+        M = To * B
         # ---- softmax layer ---------------------------------------------------------------------------------------------
         n_in = sm.insize
         with profiler.region("train_wgrad", 2.0 * M * sm.size * n_in, 4.0 * M * (ld + n_in)):
@@ -410,9 +433,9 @@ class TrainingStep(object):
                      M, sm.size, n_in, colsum=self._grad_of(sm.b).data_ptr() if sm.has_bias else None)
         dy = None
         if self.body:
-            wt = torch.zeros((n_in, ld), dtype=torch.float32, device=x.device)          # W^T, rows padded like the logits
+            wt = torch.zeros((n_in, ld), dtype=torch.float32, device=h_top.device)     # W^T, rows padded like the logits
             wt[:, :sm.size] = sm.W.dev().t()
-            dy = torch.empty((To, B, n_in), dtype=torch.float32, device=x.device)
+            dy = torch.empty((To, B, n_in), dtype=torch.float32, device=h_top.device)
             with profiler.region("train_dx", 2.0 * M * sm.size * n_in, 4.0 * M * (ld + n_in)):
                 _dx_gemm(logits.data_ptr(), ld, wt, dy.data_ptr(), n_in, M, "softmax dx")
         del logits
@@ -435,7 +458,6 @@ class TrainingStep(object):
             tapes[k] = None
         # ---- data-parallel average --------------------------------------------------------------------------------------
         self.gscale = allreduce_mean_(self.grad)
-        allreduce_step_scalars_(sc)
 
     def _softmax_grad_two_pass(self, h_top, labels, weights, rows):
         """(d loss / d logits [M][ld], ld) with the rows' loss and accuracy terms in rows[0], rows[1] -- or (None, None) where the
@@ -895,9 +917,174 @@ class TrainingStep(object):
         return [g[a:b].reshape(p.shape) for p, a, b in zip(self.shared, self.offsets[:-1], self.offsets[1:])]
 
 
+class SequenceTrainingStep(TrainingStep):
+    """fg(x, sequences, weights, rate) -> (loss, accepted): the step of TrainingStep with a sequence loss in place of the cross-entropy
+    of one label per output row (design/sequence_loss.md; not in the reference).  Chunk b is scored by the log-likelihood ll_b of its
+    called sequence under post = min_prob + (1 - min_prob) * network.run(x), summed over ALL alignments (decode.forwards_batch), and
+
+        loss = l2 * param_sqr(network) + sum_{b in A} w_b * (-ll_b) / (T' * B)        accepted = |A| / B
+
+    with A the chunks whose ll_b is finite: a chunk outside it (its sequence cannot be aligned, or forward-backward refuses it) adds
+    nothing to the loss or to the gradient.  The divisor does not depend on A, so every rank scales alike and the loss is in nats per
+    output row, like TrainingStep's.  The gradient comes from the occupancies of forward-backward (decode.forwards_backwards_batch)
+    through slk_softmax_seq_grad_f32 (csrc/seq_loss.hip); everything below d loss / d logits, the optimiser and the data-parallel
+    average are TrainingStep's.
+
+    x         : [T, B, nfeature] float32 (numpy or device tensor)
+    sequences : a [T', B] int32 label matrix as train.training_batches yields it -- chunk b's sequence is its non-zero labels in row
+                order (column 0 of the posterior is the blank: a position zeroed as bad simply drops out) -- or a list of B
+                one-dimensional integer arrays of posterior columns in 1 .. nstate - 1
+    weights   : None, [B], or [T', B] (reduced to its column means: the loop's per-label weights become one weight per chunk)
+    full      : force full-length mapping (decode.forwards)
+
+    The network must end in a transducer Softmax whose column 0 is the blank (variables.nstate, transducer=True), which is what
+    pipeline.Basecaller._sequence_columns assumes as well.  The sequences are cut on the host: the forward-backward entry sizes its
+    workspace from their lengths there."""
+
+    _bad_labels_text = "sequence columns must lie in [0, %d), those of a list entry in [1, %d)"
+
+    def __init__(self, network, min_prob=0.0, l2=0.0, full=True, workspace_limit=None, decay=(0.9, 0.999), epsilon=1e-8, clip=5.0,
+                 mrate=0.0005, optimiser="adam", momentum=0.9):
+        TrainingStep.__init__(self, network, min_prob=min_prob, l2=l2, drop=0, decay=decay, epsilon=epsilon, clip=clip, mrate=mrate,
+                              optimiser=optimiser, momentum=momentum)
+        if not 0.0 <= self.min_prob < 1.0:
+            raise ValueError("min_prob must lie in [0, 1)")
+        if self.softmax.size < 2:
+            raise NotImplementedError("the sequence loss needs a blank and at least one symbol")
+        self.full, self.workspace_limit = bool(full), workspace_limit
+
+    def _columns(self, sequences, To, B):
+        """(one int64 array of posterior columns per chunk, whether any column was outside its range -- then clipped into it)."""
+        import torch
+        nstate = self.softmax.size
+        if isinstance(sequences, (list, tuple)):
+            if len(sequences) != B:
+                raise ValueError("one sequence per chunk: %d sequences for %d chunks" % (len(sequences), B))
+            cols = [(q.cpu().numpy() if isinstance(q, torch.Tensor) else np.asarray(q)).reshape(-1).astype(np.int64) for q in sequences]
+            cat = np.concatenate(cols) if cols else np.zeros(0, np.int64)
+            bad = bool(cat.size and (cat.min() < 1 or cat.max() >= nstate))
+            if bad:
+                cols = [np.clip(q, 1, nstate - 1) for q in cols]
+            return cols, bad
+        lab = sequences.cpu().numpy() if isinstance(sequences, torch.Tensor) else np.asarray(sequences)
+        if lab.ndim != 2 or tuple(lab.shape) != (To, B):
+            raise ValueError("sequences must be a [%d, %d] label matrix (the network's output length x batch) or a list of %d sequences"
+                             % (To, B, B))
+        bad = bool(lab.size and (lab.min() < 0 or lab.max() >= nstate))
+        by_chunk = np.ascontiguousarray(lab.T).astype(np.int64)
+        if bad:
+            by_chunk = np.clip(by_chunk, 0, nstate - 1)
+        keep = by_chunk != 0
+        return np.split(by_chunk[keep], np.cumsum(keep.sum(axis=1))[:-1]), bad
+
+    def _chunk_scale(self, weights, To, B, dev):
+        """c_b = w_b / (T' * B) as a float32 device tensor [B]."""
+        import torch
+        if weights is None:
+            w = np.ones(B, dtype=np.float64)
+        else:
+            w = (weights.cpu().numpy() if isinstance(weights, torch.Tensor) else np.asarray(weights)).astype(np.float64)
+            if w.shape == (To, B):
+                w = w.mean(axis=0)
+            elif w.shape != (B,):
+                raise ValueError("weights must be None, [%d] or [%d, %d]" % (B, To, B))
+        return torch.from_numpy((w / (float(To) * float(B))).astype(np.float32)).to(dev)
+
+    def _posterior(self, h_top):
+        """(logits [M][ld], stats, ld, posterior [T', B, nstate] as a view of rows ld apart in a buffer of its own)."""
+        import torch
+        sm = self.softmax
+        To, B = int(h_top.shape[0]), int(h_top.shape[1])
+        M = To * B
+        logits, stats, ld = sm.logits_and_stats(h_top)
+        post = torch.empty((To, B, ld), dtype=torch.float32, device=h_top.device)
+        with profiler.region("train_seq_post", 0.0, 4.0 * M * (ld + sm.size)):
+            _lib.check(_lib.lib().slk_softmax_from_stats_f32(logits.data_ptr(), ld, stats.data_ptr(), post.data_ptr(), ld, M, sm.size,
+                                                             layers._stream()), "softmax_from_stats")
+        return logits, stats, ld, post[:, :, :sm.size]
+
+    def _data_terms(self, sc, score, scale, bad):
+        """sc[0] = sum over the accepted chunks of c_b * -ll_b, sc[1] = how many were accepted (divided by the batch size on the host:
+        an exact 1 when all were), sc[2] = param_sqr when l2 is on, sc[3] = bad."""
+        import torch
+        ok = torch.isfinite(score)
+        sc[0] = -(torch.where(ok, score, torch.zeros_like(score)) * scale.double()).sum()
+        sc[1] = ok.sum()
+        self._nchunk = int(score.numel())
+        sc[3] = float(bad)
+        if self.l2 != 0.0:
+            _lib.check(_lib.lib().slk_reduce_sum_f32(self.flat.data_ptr(), self.flat.numel(), 1, sc[2:].data_ptr(), layers._stream()),
+                       "reduce")
+
+    def _read_loss(self):
+        try:
+            loss, count = TrainingStep._read_loss(self)          # (the ranks' mean count: every rank holds as many chunks)
+        except ValueError:
+            raise ValueError(self._bad_labels_text % (self.softmax.size, self.softmax.size))
+        return loss, count / self._nchunk
+
+    def forward_backward(self, x, sequences, weights=None):
+        """(loss, accepted) of the (global) batch; the gradient is left as TrainingStep.forward_backward leaves it."""
+        return TrainingStep.forward_backward(self, x, sequences, weights)
+
+    def _queue_forward_backward(self, x, sequences, weights):
+        from . import decode
+        L, sm = _lib.lib(), self.softmax
+        x, h_top, tapes = self._forward_tapes(x)
+        To, B = int(h_top.shape[0]), int(h_top.shape[1])
+        M = To * B
+        cols, bad = self._columns(sequences, To, B)
+        # (with several ranks the others learn of it through the flag: this rank must not leave the step's collectives to them)
+        if bad and rank_and_world()[1] == 1:
+            raise ValueError(self._bad_labels_text % (sm.size, sm.size))
+        scale = self._chunk_scale(weights, To, B, x.device)
+        logits, stats, ld, post = self._posterior(h_top)
+        score, occ, _, _ = decode.forwards_backwards_batch(post, cols, full=self.full, blank=0, min_prob=self.min_prob, positions=False,
+                                                           workspace_limit=self.workspace_limit)
+        del post                                          # (the layers' reverse passes allocate: the posterior is gone by then)
+        with profiler.region("train_seq_grad", 0.0, 4.0 * M * (2 * ld + sm.size)):
+            _lib.check(L.slk_softmax_seq_grad_f32(logits.data_ptr(), ld, stats.data_ptr(), occ.data_ptr(), layers._row_stride(occ),
+                                                  score.data_ptr(), scale.data_ptr(), To, B, sm.size, self.min_prob, layers._stream()),
+                       "softmax_seq_grad")
+        del occ
+        sc = self._scalars
+        self._data_terms(sc, score, scale, bad)
+        box = [logits]
+        del logits
+        self._backward_from_logits(box, ld, h_top, tapes)
+        allreduce_step_scalars_(sc)
+
+    def evaluate(self, x, sequences, weights=None):
+        """(loss, accepted) of the batch, forward only (decode.forwards_batch: the score bits of forward-backward, so the value is
+        forward_backward's): no tapes are kept and the gradient of the last forward_backward stays as it is."""
+        import torch
+        from . import decode
+        sm = self.softmax
+        x, h_top, _ = self._forward_tapes(x, keep=False)
+        To, B = int(h_top.shape[0]), int(h_top.shape[1])
+        cols, bad = self._columns(sequences, To, B)
+        if bad and rank_and_world()[1] == 1:
+            raise ValueError(self._bad_labels_text % (sm.size, sm.size))
+        scale = self._chunk_scale(weights, To, B, x.device)
+        post = self._posterior(h_top)[3]
+        score = decode.forwards_batch(post, cols, full=self.full, blank=0, min_prob=self.min_prob)
+        sc = torch.zeros(4, dtype=torch.float64, device=x.device)
+        self._data_terms(sc, score, scale, bad)
+        s = allreduce_step_scalars_(sc).cpu().numpy()
+        if s[3] != 0.0:
+            raise ValueError(self._bad_labels_text % (sm.size, sm.size))
+        gscale = 1.0 / rank_and_world()[1]
+        return float(s[0]) * gscale + (self.l2 * float(s[2]) if self.l2 != 0.0 else 0.0), float(s[1]) * gscale / B
+
+
 def wrap_network(network, min_prob=0.0, l2=0.0, drop=0, adam=(0.9, 0.999)):
     """train_network.py:124-142.  `adam` = (decay1, decay2), the reference's `args.adam.decay1/2`."""
     return TrainingStep(network, min_prob=min_prob, l2=l2, drop=drop, decay=tuple(adam))
+
+
+def wrap_sequence_network(network, min_prob=0.0, l2=0.0, full=True, adam=(0.9, 0.999)):
+    """wrap_network for the sequence loss: fg(x, sequences, weights, rate) -> (loss, accepted), see SequenceTrainingStep."""
+    return SequenceTrainingStep(network, min_prob=min_prob, l2=l2, full=full, decay=tuple(adam))
 
 
 def save_model(network, output, index=None, step=None):
@@ -1016,16 +1203,28 @@ def training_batches(all_chunks, all_labels, all_weights, label_weights, niterat
 
 def train_loop(network, data, output, niteration=50000, batch_size=100, chunk_len_range=(0.5, 1.0), drop=20,
                adam=(1e-3, 0.9, 0.999), lrdecay=5000.0, min_prob=1e-30, l2=0.0, save_every=5000, smooth=0.45, seed=None,
-               transducer=True, bad=True, ilf=False, quiet=False, validation=None, validate_every=None):
+               transducer=True, bad=True, ilf=False, quiet=False, validation=None, validate_every=None, loss="labels"):
     """train_network.py:180-330 for an already built network and loaded data (`load_chunk_file`): writes model.log,
     model_checkpoint_NNNNN.pkl every `save_every` iterations and model_final.pkl into `output`; returns the step.
 
     validation, validate_every (both or neither; not in the reference, whose validation is a script of its own): held-out chunks
     as a data dict like `data`, scored with validate.validate_network (same `transducer` / `bad`, batches of up to `batch_size`
     chunks) every `validate_every` iterations on the parameters as they then stand; one `* Validation` line per scoring goes to the
-    log.  Without them the loop's output is what it was."""
+    log.  Without them the loop's output is what it was.
+
+    loss: "labels" (the default: the cross-entropy of one label per output row, everything as it was) or "sequence": the step is
+    wrap_sequence_network's (SequenceTrainingStep, full=True) -- each chunk is scored by the likelihood of its non-blank labels as a
+    sequence, summed over all alignments, and the per-label weights reach it as their mean per chunk.  It needs transducer=True and
+    drop=0 (a sequence has no rows to leave out; give chunk_len_range a minimum).  The accuracy column of the log then holds
+    `accepted`, the fraction of the batch's chunks whose sequence could be aligned."""
     import os
     import time
+    if loss not in ("labels", "sequence"):
+        raise ValueError("loss must be 'labels' or 'sequence', not %r" % (loss,))
+    if loss == "sequence" and not transducer:
+        raise ValueError("loss='sequence' needs transducer=True: without a blank state there is no sequence likelihood")
+    if loss == "sequence" and drop != 0:
+        raise ValueError("loss='sequence' needs drop=0 (got drop=%r): a sequence has no rows to leave out" % (drop,))
     rank, world = rank_and_world()
     if world > 1:
         # every rank must draw the same batches: one seed for all (rank 0's when none was given)
@@ -1045,7 +1244,10 @@ def train_loop(network, data, output, niteration=50000, batch_size=100, chunk_le
     # in the gradient all-reduce
     if all_labels.min() < 0 or all_labels.max() >= network.size:
         raise ValueError("labels must lie in [0, %d)" % network.size)
-    fg = wrap_network(network, min_prob=min_prob, l2=l2, drop=drop, adam=adam[1:])
+    if loss == "sequence":
+        fg = wrap_sequence_network(network, min_prob=min_prob, l2=l2, full=True, adam=adam[1:])
+    else:
+        fg = wrap_network(network, min_prob=min_prob, l2=l2, drop=drop, adam=adam[1:])
     fv = None
     if validation is not None and validate_every is not None:
         from . import validate
