@@ -240,6 +240,10 @@ SLK_API int slk_softmax_rowstats_f32(const float *logits, long M, int N, float *
  *   over t = 0..T-1 (reverse=0) or t = T-1..0 (reverse=1, implements Reverse(Gru) without copies).
  *   sW:[2n][n]  sW2:[n][n]  (reference shapes, [out][in]);  h_out element (t,b,j) at
  *   h_out[(t*B + b)*ldh + j]  (ldh >= n).
+ *   vI is dense (rows 3n floats apart: the scan entries take no ldv) and must be 16-byte aligned: at n = 16, 32, ..., 144 the scan
+ *   (gru_mfma_kernel of csrc/recurrent.hip) stages it into LDS with 16-byte LDS-DMA loads.  h_out may lie anywhere: with
+ *   ldh % 4 == 0 and a 16-byte aligned h_out it is stored 16 bytes at a time, otherwise float by float (the same bits).
+ *   lens (slk_gru_recurrent_ragged_f32): an entry outside [1, T] is clamped into it.
  * slk_gru_f32 = projection + recurrence; workspace >= slk_gru_workspace_bytes(T,B,n).
  * ------------------------------------------------------------------------------------------------------- */
 SLK_API int slk_gru_recurrent_f32(const float *vI, const float *sW, const float *sW2, float *h_out, long ldh, int T, int B,

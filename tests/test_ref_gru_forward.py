@@ -174,6 +174,171 @@ def test_every_listed_scan_and_stack_case_is_admitted():
             assert c["yard"]["h"] <= rg.ADMIT and c["cap"] == rg.CAP * nlayer
 
 
+# ------------------------------------------------------------------- the float32 scan of csrc/recurrent.hip: recursion, cases, tables
+@pytest.mark.parametrize("reverse", [False, True])
+@pytest.mark.parametrize("act,gate", rg.OTHER_PAIRS)
+def test_float64_recursion_with_other_activations_equals_the_oracles(oracle, act, gate, reverse):
+    """act / gate of gru_forward against oracle_np.gru and the C oracle for every pair the float32 scan is run with; the ids are those
+    of include/sloika_amd.h as sloika_amd.activation numbers them."""
+    from sloika_amd import activation
+    x, iW, sW, sW2, b = _small(21 + reverse)
+    sW, sW2 = 0.5 * sW, 0.5 * sW2                       # (a candidate that is not squashed: keep the map from expanding)
+    h = rg.gru_forward(x, iW, sW, sW2, b, reverse, act=act, gate=gate)[0]
+    assert np.abs(h - oracle_np.gru(x, iW, sW, sW2, b, act=act, gate=gate, reverse=reverse)).max() <= 1e-12
+    assert not np.array_equal(h, rg.gru_forward(x, iW, sW, sW2, b, reverse)[0])           # the names do something
+    f = [a.astype(F32) for a in (x, iW, sW, sW2, b)]
+    ref = oracle.gru(*f, act=act, gate=gate, reverse=reverse)
+    # (the C oracle computes in float32: 2e-5 of the largest state, which an unsquashed candidate lets grow past 1)
+    assert np.abs(rg.gru_forward(*f, reverse, act=act, gate=gate)[0] - ref).max() <= 2e-5 * max(1.0, np.abs(ref).max())
+    h32 = rg.gru_forward(x, iW, sW, sW2, b, reverse, None, F32, act=act, gate=gate)[0]
+    assert h32.dtype == F32 and 0 < np.abs(h32 - h).max() < 2e-5 * max(1.0, np.abs(h).max())
+    for name in (act, gate):
+        assert rg.ACTIVATIONS[name][1] == activation.act_id(name)
+    # each function where it bends: around zero, at the clip's ends, far out
+    v = np.array([-30.0, -2.5, -2.0, -1e-3, 0.0, 1e-3, 2.0, 2.5, 30.0])
+    for name in (act, gate):
+        assert np.abs(rg.ACTIVATIONS[name][0](v) - oracle_np.ACT[name](v)).max() <= 1e-15
+        assert rg.ACTIVATIONS[name][0](v.astype(F32)).dtype == F32
+
+
+@pytest.mark.parametrize("reverse", [False, True])
+def test_f32_scan_case_is_ragged_and_reversed_as_the_entries_document(reverse):
+    """Each chunk of a ragged f32_scan_case is the case of that chunk alone over its own rows of the same vI, a reversed scan from the
+    chunk's own last row; rows behind a chunk's end are MARKER; vI is the float32 rounding of the float64 projection."""
+    T, lens = rg.f32_ragged_lens(4)
+    c = rg.f32_scan_case(144, T, rg.F32_RAGGED_B, reverse, lens)
+    assert c["grade"] == "y32" and c["h32"].dtype == F32 and c["vI"].dtype == F32 and c["zr"] is None and set(c["yard"]) == {"h"}
+    assert c["yard"]["h"] == rg.chunk_errors(c["h32"], c["h"], c["lens"]).max() > 0
+    for b, tb in enumerate(lens):
+        alone = rg.gru_forward(None, None, c["sW"], c["sW2"], None, reverse, vI=c["vI"][:tb, b:b + 1])[0]
+        assert np.abs(c["h"][:tb, b:b + 1] - alone).max() <= 1e-12
+        assert np.isnan(c["h"][tb:, b]).all() and np.isnan(c["h32"][tb:, b]).all()
+        if reverse and tb < T:                                                    # not the scan that starts at row T - 1
+            wrong = rg.gru_forward(None, None, c["sW"], c["sW2"], None, True, vI=c["vI"][:, b:b + 1])[0]
+            assert np.abs(c["h"][:tb, b:b + 1] - wrong[:tb]).max() > 1e-3
+    full = rg.f32_scan_case(144, T, rg.F32_RAGGED_B, reverse, (T,) * rg.F32_RAGGED_B)
+    assert np.array_equal(full["h"], rg.gru_forward(None, None, full["sW"], full["sW2"], None, reverse, vI=full["vI"])[0])
+    # the same recursion as the oracle's, from the weights and inputs the case was made of
+    iW, sW, sW2, b = rg.weights(rg.SCAN_INSIZE, 144, "moderate")
+    plain = rg.f32_scan_case(144, 5, 3, reverse)
+    x = rg.inputs(rg.SCAN_INSIZE, 5, 3, 7 * rg.SCAN_INSIZE + 3 * 144 + 5)
+    assert np.array_equal(plain["vI"], (x.astype(F64) @ iW.astype(F64).T + b).astype(F32))
+    assert np.array_equal(plain["sW"], sW * F32(rg.F32_RECURRENT_SCALE))
+    assert np.abs(plain["h"] - oracle_np.gru(x, iW, plain["sW"], plain["sW2"], b, reverse=reverse)).max() <= 1e-6   # (vI rounded)
+    small = plain.take(2)
+    assert small["h32"].shape[1] == 2 and small["yard"]["h"] <= plain["yard"]["h"]
+
+
+def test_f32_tables_follow_the_declared_geometry_of_recurrent_hip():
+    """KB and the tile of four chunks as csrc/recurrent.hip states them; every F32_* table laid around them."""
+    geo = rg.declared_f32_scan_geometry()
+    assert geo == {"KB": (128, 8, 4), "tile": 4}
+    widest, kb_lo, kb_hi = geo["KB"]
+    assert {rg.f32_kb(n) for n in rg.F32_MFMA_SIZES if n <= widest} == {kb_lo}
+    assert {rg.f32_kb(n) for n in rg.F32_MFMA_SIZES if n > widest} == {kb_hi} and set(rg.F32_T) == {kb_lo, kb_hi}
+    for kb, table in rg.F32_T.items():
+        assert set(table) == rg.demanded_f32_edges(kb), (kb, sorted(rg.demanded_f32_edges(kb) ^ set(table)))
+        T, lengths = rg.F32_RAGGED[kb]
+        assert set(lengths) == {1, kb - 1, kb, kb + 1, 2 * kb - 1, 2 * kb, 2 * kb + 1, 3 * kb, 3 * kb + 1} and T == 3 * kb + 1
+    tile = geo["tile"]
+    assert rg.F32_EDGE_B % tile == 1 and rg.F32_EDGE_B > 2 * tile and rg.F32_RAGGED_B % tile == 1
+    assert {B % tile for B in rg.F32_BATCH_B} == set(range(tile)) and {1, tile, tile + 1, 2 * tile, 2 * tile + 1} <= set(rg.F32_BATCH_B)
+    assert rg.F32_LONG_B % tile == 2
+    # the instantiations of launch_gru_mfma / launch_gru_mfma144, and sizes that have none
+    with open(rg.os.path.join(rg.CSRC, "recurrent.hip")) as fh:
+        src = fh.read()
+    sizes = {int(v) for v in rg.re.findall(r"case (\d+): return launch_gru_mfma<\1>", src)} | {int(v) for v in rg.re.findall(
+        r"gru_mfma_kernel<(\d+), SLK_ACT_TANH, SLK_ACT_SIGMOID, 12>", src)}
+    assert sizes == set(rg.F32_MFMA_SIZES)
+    assert not set(rg.F32_GENERIC_SIZES) & sizes and max(rg.F32_GENERIC_SIZES) > max(sizes) > min(rg.F32_GENERIC_SIZES)
+    assert set(rg.F32_FORCED_SIZES) <= sizes and set(rg.F32_ACT_SIZES) <= sizes and set(rg.F32_LONG_SIZES) <= sizes
+    for n in rg.F32_ACT_SIZES + (144,):
+        kb = rg.f32_kb(n)
+        assert rg.f32_act_T(n) == (1, kb, kb + 1, 2 * kb + 1)
+    assert 0 < rg.F32_RECURRENT_SCALE <= 1.0
+
+
+def test_f32_ragged_sets_hold_the_tiles_they_claim():
+    """B = 17 in tiles of four: three tiles of four different lengths each, the longest beside the shortest, one tile of length 1
+    only, and a last tile of one chunk of length 1; every length somewhere, the ones that come twice in two slots."""
+    tile = rg.declared_f32_scan_geometry()["tile"]
+    for kb in rg.F32_T:
+        T, lens = rg.f32_ragged_lens(kb)
+        lengths = rg.F32_RAGGED[kb][1]
+        assert len(lens) == rg.F32_RAGGED_B == 4 * tile + 1 and max(lens) == T and set(lens) == set(lengths)
+        tiles = [lens[k:k + tile] for k in range(0, len(lens), tile)]
+        assert [len(set(t)) for t in tiles] == [tile, tile, tile, 1, 1] and tiles[3] == (1,) * tile and tiles[4] == (1,)
+        assert {1, T} <= set(tiles[0])                                            # a chunk that ends at once beside one that never does
+        for t in tiles[:3]:
+            assert min(t) < kb + 1 < max(t) or kb + 1 in t                        # lengths in different blocks of the ring
+            assert len({(v - 1) // kb for v in t}) >= 3                           # ... three different last blocks per tile
+        for length in lengths:
+            slots = [b % tile for b in range(3 * tile) if lens[b] == length]
+            assert len(slots) >= 1 and len(set(slots)) == len(slots), (kb, length, slots)
+        assert sorted(v for v in lengths if lens[:3 * tile].count(v) == 2) == [1, kb + 1, T]
+    assert 1 in rg.F32_GENERIC_LENS and max(rg.F32_GENERIC_LENS) == max(rg.F32_GENERIC_T) and len(rg.F32_GENERIC_LENS) == max(rg.F32_GENERIC_B)
+    assert 1 in rg.F32_ACT_LENS and len(rg.F32_ACT_LENS) == rg.F32_ACT_B
+
+
+def test_every_listed_f32_case_is_admitted():
+    """y32 of every case the GPU tests run through the float32 scan, on that case's own inputs, is at most CAP / 8.  The time-edge,
+    batch-edge and ragged sets hold every entry the geometry demands (the test above); the long and other-activation cases run at the
+    lengths asked for unless their tables say otherwise."""
+    listed = rg.listed_f32_cases()
+    assert len(listed["edges"]) == 2 * len(rg.F32_MFMA_SIZES) * (12 + 3)
+    for name, cases in listed.items():
+        for args in cases:
+            c = rg.f32_scan_case(*args)
+            assert np.isfinite(c["vI"]).all() and c["grade"] == "y32"
+            assert c["yard"]["h"] <= rg.ADMIT, (name, args[:4], args[5:], c["yard"])
+    assert all(T == 100 for T in rg.F32_LONG_T.values())
+    shortened = {key: ts for key, ts in rg.F32_ACT_T.items() if ts != rg.f32_act_T(key[0])}
+    assert shortened == {(128, "linear"): (1, 8, 9, 15)}                          # 2 KB + 1 = 17 is not admitted there, nor is 16
+    assert rg.f32_scan_case(128, 17, rg.F32_ACT_B, False, None, "linear", "sigmoid")["yard"]["h"] > rg.TABLE_MARGIN * rg.ADMIT
+    T, lens = rg.f32_ragged_lens(8)
+    for reverse in (False, True):
+        for I, n in rg.F32_LAYER_SHAPES:
+            c = rg.f32_layer_case(I, n, *rg.F32_LAYER_TB, reverse)
+            assert c["grade"] == "y32" and c["yard"]["h"] <= rg.ADMIT, (I, n, c["yard"])
+        for I, n, act, gate in rg.F32_NET_SCAN:
+            c = rg.f32_layer_case(I, n, T, rg.F32_RAGGED_B, reverse, lens, "y22", act, gate)
+            assert c["grade"] == "y22" and c["h22"].dtype == F32 and c["yard"]["h"] <= rg.ADMIT, (I, n, c["yard"])
+        c = rg.f32_layer_case(*rg.F32_NET_EXACT, T, rg.F32_RAGGED_B, reverse, lens, "y32")
+        assert c["yard"]["h"] <= rg.ADMIT, c["yard"]
+
+
+def test_y32_of_the_float32_scan_is_the_worse_of_two_summation_orders():
+    """One accumulator in the order of k against the host's BLAS: both float32, both the same recursion, and the case keeps the one
+    further from float64."""
+    v, W = np.random.RandomState(5).normal(size=(3, 40)).astype(F32), np.random.RandomState(6).normal(size=(7, 40)).astype(F32)
+    chain = rg._product(None, "chain")(v, W)
+    assert chain.dtype == F32 and chain.shape == (3, 7)
+    acc = np.zeros((3, 7), F32)
+    for k in range(40):
+        acc = acc + v[:, k, None] * W[None, :, k]
+    assert np.array_equal(chain, acc) and np.abs(chain - v.astype(F64) @ W.astype(F64).T).max() < 1e-5
+    assert rg.F32_ORDERS == (None, "chain")
+    c = rg.f32_scan_case(144, 4, rg.F32_ACT_B, False, None, "elu", "sigmoid")
+    each = [rg.gru_forward(None, None, c["sW"], c["sW2"], None, False, None, F32, vI=c["vI"], act="elu", gate="sigmoid", order=o)[0]
+            for o in rg.F32_ORDERS]
+    errs = [rg.chunk_errors(h, c["h"], None).max() for h in each]
+    assert c["yard"]["h"] == max(errs) and min(errs) > 0 and errs[0] != errs[1]
+
+
+def test_checker_grades_a_y32_case_by_its_own_yardstick(capsys):
+    c = rg.f32_scan_case(48, 9, 5, True, rg.F32_GENERIC_LENS)
+    rg.check(c["h"], None, c, "self")
+    rg.check(c["h32"], None, c, "y32")
+    assert all(" yardstick y32 " in l for l in capsys.readouterr().out.splitlines() if l.startswith("GRUFWD "))
+    got = c["h"].copy()
+    got[0, 1, 5] += 3e-6                                                          # the only step of chunk 1
+    with pytest.raises(AssertionError, match="chunk 1"):
+        rg.check(got, None, c, "moved")
+    short = rg.gru_forward(None, None, c["sW"], c["sW2"], None, True, np.array([9, 1, 4, 5, 7]), vI=c["vI"])[0]
+    with pytest.raises(AssertionError, match="chunk 4"):
+        rg.check(short, None, c, "short")
+
+
 # ----------------------------------------------------------------------------------------------------- the checker
 def _ragged(reverse):
     return rg.layer_case(48, 32, "moderate", rg.RAGGED_T, rg.RAGGED_B, reverse, rg.ragged_lens())
