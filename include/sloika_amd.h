@@ -436,6 +436,32 @@ SLK_API int slk_softmax_viterbi_f32(const float *x, long ldx, const void *pack, 
                             float skip_pen, float min_prob, const int32_t *lens, int plan, void *workspace,
                             size_t workspace_bytes, float *score_out, int32_t *path_out, int32_t *len_out, float *lp_dump,
                             slk_stream_t stream);
+/* f8. The sum-product twin of slk_viterbi_kmer_f32 (design/lattice_marginals.md): over the SAME lattice -- per row a stay
+ * (weight p[i][0]), a step (p[i][1+s]) or a skip (exp(-skip_pen) p[i][1+s]) into k-mer state s, row 0 weighing p[0][1+s]; p the
+ * float32 values slk_prepare_post_f32 gives (SLK_POST_RAW; the input itself for SLK_POST_PLAIN) widened to float64; the 1e-10 of
+ * decode.viterbi's log is no part of the weights -- the sum Z of all path weights, the share gamma[i][s] of Z that passes through
+ * s at row i, and for every position of the called path a confidence.
+ *   post       : [T][B][N + 1] float32 in the network layout, N = nbase^klen; input_mode SLK_POST_RAW or SLK_POST_PLAIN
+ *                (SLK_POST_LOG / SLK_POST_LN: SLK_ERR_UNSUPPORTED -- the sum needs the weights, not their logarithms)
+ *   klen >= 3, nbase 4 or 5, N <= 1024; anything else: SLK_ERR_UNSUPPORTED (workspace_bytes: 0), nothing is written
+ *   lens       : NULL, or [B] int32 on the device: chunk b owns its first lens[b] rows, clamped to 1 .. T
+ *   score_out, path_out, len_out : what slk_viterbi_kmer_f32 returns for the chunk's rows, bit for bit (the same float32
+ *                recursion and tie rules)
+ *   move_row   : [B][T] int32, move_row[b][j] = the row at which the path enters its j-th state (move_row[b][0] = 0); position j
+ *                dwells on rows move_row[j] .. move_row[j + 1] - 1, the last one up to the chunk's last row
+ *   conf       : [B][T] float64, conf[b][j] = the largest gamma[i][path[j]] over the rows i of position j's dwell
+ *   logz       : [B] float64, log Z (natural)
+ *   gamma      : NULL, or [T][B][N] float32: each float64 value rounded once; rows behind a chunk's own are 0
+ *   entries of move_row / conf at or behind len_out[b] are -1 / 0.
+ * The sum runs in float64, rows scaled by exact powers of two.  A chunk's outputs have the same bits alone, in any batch, with or
+ * without gamma.  workspace: 8-byte aligned, slk_viterbi_marginals_workspace_bytes(T, B, nbase, klen) bytes (9 N + 20 per row and
+ * chunk: the float64 forward rows and a traceback byte per state), else SLK_ERR_WORKSPACE and nothing is written; T, B < 1, a null
+ * pointer, min_prob outside [0, 1): SLK_ERR_INVALID_ARG. */
+SLK_API size_t slk_viterbi_marginals_workspace_bytes(int T, int B, int nbase, int klen);   /* host only; 0 for a refused shape */
+SLK_API int slk_viterbi_marginals_f32(const float *post, int T, int B, int nbase, int klen, float skip_pen, int input_mode,
+                              float min_prob, const int32_t *lens, void *workspace, size_t workspace_bytes, float *score_out,
+                              int32_t *path_out, int32_t *len_out, int32_t *move_row, double *conf, double *logz, float *gamma,
+                              slk_stream_t stream);
 /* decode.prepare_post on its own: out = min_prob + (1-min_prob)*post (decode.py:36).                        */
 SLK_API int slk_prepare_post_f32(const float *post, float *out, size_t count, float min_prob, slk_stream_t stream);
 /* decode.argmax (decode.py:5-18), batched: per (b) the states with argmax != blank, minus 1 if
@@ -488,6 +514,16 @@ SLK_API int slk_decode_profile_f64(const float *post, int T, int B, int nbase, i
  * ------------------------------------------------------------------------------------------------------- */
 SLK_API int slk_paths_to_bases(const int32_t *paths, long ld, const int32_t *lens, int B, int klen, int nbase, int always_move,
                        unsigned long long alphabet, uint8_t *out, long cap, int32_t *nbases, slk_stream_t stream);
+/* f8. The same letters, byte for byte, and a Phred value beside each: qual:[B][cap] bytes, qual[b][m] = the value of the path
+ *   position that emitted letter m (the first position emits klen letters, a later one its move's).  conf:[B][ldc] float64, one
+ *   confidence per path position (slk_viterbi_marginals_f32); thresholds:[qmax] float64 ON THE DEVICE, thresholds[k - 1] =
+ *   10^(-k/10) as the host's float64 pow gives it, 1 <= qmax <= 93.  The value is the number of k in 1 .. qmax with
+ *   1.0 - conf <= thresholds[k - 1]: comparisons only, no log on the device, an exact integer that a search of the same table
+ *   reproduces (a conf that is NaN gives 0). */
+SLK_API int slk_paths_to_bases_qual(const int32_t *paths, long ld, const int32_t *lens, const double *conf, long ldc,
+                            const double *thresholds, int qmax, int B, int klen, int nbase, int always_move,
+                            unsigned long long alphabet, uint8_t *out, uint8_t *qual, long cap, int32_t *nbases,
+                            slk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * a9. The reference's only true FFI: viterbi_helpers.slip_update (sloika/viterbi_helpers.pyx:12-35), and

@@ -311,23 +311,77 @@ def error_summary(profile):
 _COMPLEMENT = bytes.maketrans(b"ACGT", b"TGCA")
 
 
-def sam_record(name, row, strand, codes, query_length, rname, seq=None):
+def sam_record(name, row, strand, codes, query_length, rname, seq=None, qual=None):
     """One SAM line (no newline) of an alignment: row = FIELDS with forward-strand r_start, codes = its columns in query order.
-    See sam_records for the field rules."""
+    See sam_records for the field rules.  qual: None ('*'), or the QUAL string of `seq` (Phred + 33, one character per letter, in the
+    query's own direction: reversed with SEQ for a '-' alignment)."""
     score, qs, qe, rs = int(row[0]), int(row[1]), int(row[2]), int(row[3])
     if seq is not None and not isinstance(seq, str):
         seq = bytes(bytearray(_as_u8(seq))).decode('ascii')
+    if qual is not None:
+        if not seq or len(qual) != len(seq):
+            raise ValueError("align: QUAL needs a SEQ of the same length")
+        qual = str(qual)
     if score <= 0:
-        return "\t".join([str(name), "4", "*", "0", "0", "*", "*", "0", "0", seq if seq else "*", "*"])
+        return "\t".join([str(name), "4", "*", "0", "0", "*", "*", "0", "0", seq if seq else "*", qual if qual else "*"])
     front, back = qs, int(query_length) - qe
     if strand == '-':
         codes, front, back = np.asarray(codes)[::-1], back, front
         if seq is not None:
             seq = seq.encode('ascii').translate(_COMPLEMENT)[::-1].decode('ascii')
+        if qual is not None:
+            qual = qual[::-1]
     nm = int(row[6]) + int(row[7]) + int(row[8])
     return "\t".join([str(name), "16" if strand == '-' else "0", str(rname), str(rs + 1), "255",
-                      cigar_string(codes, False, front, back), "*", "0", "0", seq if seq else "*", "*", "NM:i:%d" % nm,
-                      "AS:i:%d" % score])
+                      cigar_string(codes, False, front, back), "*", "0", "0", seq if seq else "*", qual if qual else "*",
+                      "NM:i:%d" % nm, "AS:i:%d" % score])
+
+
+# ---- are the qualities of calls calibrated?  (design/lattice_marginals.md) ----------------------------------------------------------
+
+def calibration_counts(columns, starts, quals, qmax=60):
+    """Right and wrong letters per Phred value, from plain arrays: columns[b] the codes of pair b's alignment in query order (OP_*),
+    starts[b] the query letter its first column lies at, quals[b] the Phred values of the query's letters.  The j-th column that
+    consumes a query letter (match, mismatch, insertion) is letter starts[b] + j: OP_MATCH counts right, OP_MISMATCH and OP_INSERTION
+    wrong; deletions have no letter and the clipped letters outside the alignment count nowhere.  -> int64 [qmax + 1][2]."""
+    qmax = int(qmax)
+    counts = np.zeros((qmax + 1, 2), dtype=np.int64)
+    if not len(columns) == len(starts) == len(quals):
+        raise ValueError("calibration_counts needs one start and one quality array per alignment")
+    for b, (codes, start, q) in enumerate(zip(columns, starts, quals)):
+        codes = np.asarray(codes, dtype=np.uint8).reshape(-1)
+        q = np.asarray(q).reshape(-1)
+        letters = codes[codes != OP_DELETION]
+        if letters.size == 0:
+            continue
+        if (letters > OP_DELETION).any():
+            raise ValueError("alignment %d holds a code that is no column" % b)
+        start = int(start)
+        if start < 0 or start + letters.size > q.size:
+            raise ValueError("alignment %d covers letters %d .. %d of a query with %d qualities" % (b, start, start + letters.size, q.size))
+        mine = q[start:start + letters.size].astype(np.int64)
+        if mine.min() < 0 or mine.max() > qmax:
+            raise ValueError("alignment %d: qualities must lie in 0 .. %d" % (b, qmax))
+        np.add.at(counts, (mine, (letters != OP_MATCH).astype(np.int64)), 1)
+    return counts
+
+
+def quality_calibration(ops, quals, qmax=60):
+    """calibration_counts over the alignments of an Ops (align_batch / accuracy_of_paths with ops=True): quals[b] the Phred values of
+    query b's letters (bio.paths_to_bases_qual).  A pair without an alignment counts nowhere.  -> int64 [qmax + 1][2], the right and
+    the wrong letters per Phred value."""
+    if len(quals) != len(ops):
+        raise ValueError("quality_calibration needs one quality array per pair")
+    return calibration_counts([ops.codes(b) for b in range(len(ops))], [int(ops.rows[b, 1]) for b in range(len(ops))], quals, qmax)
+
+
+def calibration_table(counts):
+    """The empirical Phred value of every bin of quality_calibration's counts: -10 log10(wrong / (right + wrong)) as float64
+    [qmax + 1]; NaN for a bin without letters, inf for one without a wrong letter."""
+    counts = np.asarray(counts, dtype=np.float64)
+    total = counts.sum(axis=1)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where(total > 0, -10.0 * np.log10(counts[:, 1] / total), np.nan)
 
 
 def sam_records(res, strand, ops, names, ref_names, ref_lengths, queries=None):

@@ -6,6 +6,8 @@ significant -- the index `all_kmers` gives it (bio.py:12-24).  The reference's s
     k1[i:] == k2[:-i]      <=>      s1 mod nbase^(k-i) == s2 div nbase^i
 
 `paths_to_bases` runs whole batches of decoded paths on the device (csrc/bases.hip, C ABI slk_paths_to_bases);
+`paths_to_bases_qual` does the same with a Phred value beside every letter (slk_paths_to_bases_qual, design/lattice_marginals.md)
+and `fastq_text` prints them;
 `kmers_to_sequence` & co. keep the reference's string-level signatures for single calls and evaluate the same integer
 rule with numpy (they are host-side string utilities in the reference too).
 """
@@ -154,3 +156,69 @@ def paths_to_bases(paths, lens, klen, alphabet='ACGT', always_move=True):
     counts = nb.cpu().numpy()
     host = out[:, :int(counts.max()) if B else 0].cpu().numpy()
     return [host[b, :counts[b]].tobytes().decode('utf-8') for b in range(B)]
+
+
+#: the largest Phred value a FASTQ line can print (Phred + 33 <= 126, '~')
+PHRED_MAX = 93
+
+
+def phred_thresholds(qmax=60):
+    """float64 [qmax]: entry k - 1 is 10^(-k/10), the largest error probability that still earns Phred k.  The Phred value of an error
+    probability is the number of entries it does not exceed -- on the device (slk_paths_to_bases_qual) and, for the same table,
+    `qmax - np.searchsorted(table[::-1], err, side='left')`."""
+    qmax = int(qmax)
+    if not 1 <= qmax <= PHRED_MAX:
+        raise ValueError("qmax must lie in 1 .. %d" % PHRED_MAX)
+    return np.array([10.0 ** (-k / 10.0) for k in range(1, qmax + 1)], dtype=np.float64)
+
+
+def phred_of_error(err, qmax=60):
+    """Host restatement of the device's rule: int64 Phred values of error probabilities (NaN -> 0)."""
+    table = phred_thresholds(qmax)
+    err = np.asarray(err, dtype=np.float64)
+    q = qmax - np.searchsorted(table[::-1], err, side='left')
+    return np.where(np.isnan(err), 0, q).astype(np.int64)
+
+
+def paths_to_bases_qual(paths, lens, conf, klen, alphabet='ACGT', qmax=60):
+    """paths_to_bases(always_move=True) with a quality per letter: conf [B, T] float64 device tensor, one confidence per path position
+    (decode.viterbi_marginals_batch); a letter gets the Phred value of 1 - conf of the position that emitted it, capped at qmax.
+    -> list of B (base string, uint8 array of Phred values)."""
+    import torch
+    from . import _lib, device as D
+    _lib.require_gpu()
+    if isinstance(alphabet, str):
+        alphabet = alphabet.encode('utf-8')
+    B, Tmax = paths.shape
+    if conf.dtype != torch.float64 or conf.shape[0] != B or conf.shape[1] < Tmax or conf.stride(1) != 1:
+        raise ValueError("conf must be a float64 device tensor with one row per path and one entry per position")
+    table = torch.from_numpy(phred_thresholds(qmax)).to(paths.device)
+    cap = max(klen * max(Tmax, 1), klen)
+    out = torch.empty((B, cap), dtype=torch.uint8, device=paths.device)
+    qual = torch.empty((B, cap), dtype=torch.uint8, device=paths.device)
+    nb = torch.empty((B,), dtype=torch.int32, device=paths.device)
+    packed = int.from_bytes(alphabet.ljust(8, b'\0'), 'little')
+    _lib.check(_lib.lib().slk_paths_to_bases_qual(paths.data_ptr(), paths.stride(0), lens.data_ptr(), conf.data_ptr(), conf.stride(0),
+                                                  table.data_ptr(), int(qmax), B, klen, len(alphabet), 1, packed, out.data_ptr(),
+                                                  qual.data_ptr(), cap, nb.data_ptr(), D.stream_ptr()), "paths_to_bases_qual")
+    counts = nb.cpu().numpy()
+    width = int(counts.max()) if B else 0
+    host, hq = out[:, :width].cpu().numpy(), qual[:, :width].cpu().numpy()
+    return [(host[b, :counts[b]].tobytes().decode('utf-8'), hq[b, :counts[b]].copy()) for b in range(B)]
+
+
+def fastq_text(names, bases, quals):
+    """FASTQ text of calls: four lines per read, qualities as Phred + 33 (Sanger).  quals[b]: one integer in 0 .. 93 per letter."""
+    if not len(names) == len(bases) == len(quals):
+        raise ValueError("fastq_text needs one name, one sequence and one quality array per read")
+    out = []
+    for name, seq, q in zip(names, bases, quals):
+        q = np.asarray(q)
+        if isinstance(seq, bytes):
+            seq = seq.decode('ascii')
+        if q.shape != (len(seq),):
+            raise ValueError("read %s: %d qualities for %d letters" % (name, q.size, len(seq)))
+        if q.size and (q.min() < 0 or q.max() > PHRED_MAX):
+            raise ValueError("read %s: qualities must lie in 0 .. %d" % (name, PHRED_MAX))
+        out.append("@%s\n%s\n+\n%s\n" % (name, seq, (q.astype(np.uint8) + 33).tobytes().decode('ascii')))
+    return "".join(out)

@@ -12,11 +12,17 @@
 
 #define BASES_MAX_K 12
 
+// QUAL: every letter also gets the Phred value of the position that emitted it (design/lattice_marginals.md): the number of
+// k in 1 .. qmax with 1 - conf <= thresholds[k - 1], thresholds[k - 1] = 10^(-k/10) made by the host -- comparisons only, so the
+// value is an exact integer that a search of the same table reproduces.
+template <bool QUAL>
 __global__ void __launch_bounds__(256) paths_to_bases_kernel(const int32_t *__restrict__ paths, long ld,
                                                              const int32_t *__restrict__ lens, int klen, int nbase,
                                                              int always_move, unsigned long long alphabet,
                                                              uint8_t *__restrict__ out, long cap,
-                                                             int32_t *__restrict__ nbases)
+                                                             int32_t *__restrict__ nbases, const double *__restrict__ conf,
+                                                             long ldc, const double *__restrict__ thresholds, int qmax,
+                                                             uint8_t *__restrict__ qual)
 {
     __shared__ int wsum[4];
     __shared__ int carry;
@@ -27,6 +33,12 @@ __global__ void __launch_bounds__(256) paths_to_bases_kernel(const int32_t *__re
     int nstate = 1;                                            // nbase^klen
     for (int i = 0; i < klen; i++) nstate *= nbase;
     auto letter = [&](int digit) { return (uint8_t)((alphabet >> (8 * digit)) & 0xff); };
+    auto phred = [&](int i) {
+        const double err = 1.0 - conf[(size_t)b * ldc + i];
+        int q = 0;
+        for (int k = 0; k < qmax; k++) q += err <= thresholds[k] ? 1 : 0;
+        return (uint8_t)q;
+    };
     if (n < 1) {
         if (j == 0) nbases[b] = 0;
         return;
@@ -34,6 +46,10 @@ __global__ void __launch_bounds__(256) paths_to_bases_kernel(const int32_t *__re
     if (j == 0) {                                              // the first k-mer in full (bio.py:216)
         int t = p[0];
         for (int d = klen - 1; d >= 0; d--) { o[d] = letter(t % nbase); t /= nbase; }
+        if constexpr (QUAL) {
+            const uint8_t q = phred(0);
+            for (int d = 0; d < klen; d++) qual[(size_t)b * cap + d] = q;
+        }
     }
     if (j == 0) carry = klen;
     __syncthreads();
@@ -69,6 +85,12 @@ __global__ void __launch_bounds__(256) paths_to_bases_kernel(const int32_t *__re
         if (i < n) {                                            // the last mv letters of s2 (bio.py:219-224)
             int t = s2;
             for (int d = mv - 1; d >= 0; d--) { o[pos + d] = letter(t % nbase); t /= nbase; }
+            if constexpr (QUAL) {
+                if (mv > 0) {
+                    const uint8_t q = phred(i);
+                    for (int d = 0; d < mv; d++) qual[(size_t)b * cap + pos + d] = q;
+                }
+            }
         }
         __syncthreads();
         if (j == 255) carry = before + incl;
@@ -90,7 +112,27 @@ extern "C" int slk_paths_to_bases(const int32_t *paths, long ld, const int32_t *
     for (int i = 0; i < klen; i++) states *= nbase;
     if (states > 2147483647.0) return SLK_ERR_INVALID_ARG;
     if (B == 0) return SLK_OK;
-    hipLaunchKernelGGL(paths_to_bases_kernel, dim3(B), dim3(256), 0, slk_stream(stream), paths, ld, lens, klen, nbase,
-                       always_move, alphabet, out, cap, nbases);
+    hipLaunchKernelGGL(paths_to_bases_kernel<false>, dim3(B), dim3(256), 0, slk_stream(stream), paths, ld, lens, klen, nbase,
+                       always_move, alphabet, out, cap, nbases, nullptr, 0, nullptr, 0, nullptr);
+    return slk_launch_status();
+}
+
+// The same letters, and beside them qual:[B][cap] bytes: the Phred value of the path position that emitted each letter (the first
+// position emits klen letters, a later one its move's), from conf:[B][ldc] float64 (slk_viterbi_marginals_f32) and
+// thresholds:[qmax] float64 on the device, thresholds[k - 1] = 10^(-k/10), qmax <= 93 (Phred + 33 stays printable).
+extern "C" int slk_paths_to_bases_qual(const int32_t *paths, long ld, const int32_t *lens, const double *conf, long ldc,
+                                       const double *thresholds, int qmax, int B, int klen, int nbase, int always_move,
+                                       unsigned long long alphabet, uint8_t *out, uint8_t *qual, long cap, int32_t *nbases,
+                                       slk_stream_t stream)
+{
+    if (!paths || !lens || !conf || !thresholds || !out || !qual || !nbases || B < 0 || klen < 1 || klen > BASES_MAX_K || nbase < 2 ||
+        nbase > 8 || cap < klen || qmax < 1 || qmax > 93)
+        return SLK_ERR_INVALID_ARG;
+    double states = 1.0;
+    for (int i = 0; i < klen; i++) states *= nbase;
+    if (states > 2147483647.0) return SLK_ERR_INVALID_ARG;
+    if (B == 0) return SLK_OK;
+    hipLaunchKernelGGL(paths_to_bases_kernel<true>, dim3(B), dim3(256), 0, slk_stream(stream), paths, ld, lens, klen, nbase,
+                       always_move, alphabet, out, cap, nbases, conf, ldc, thresholds, qmax, qual);
     return slk_launch_status();
 }

@@ -9,6 +9,8 @@
     forwards_batch(post[T,B,S] | rows + row_off, seqs)     batched extension    -> scores[B] float64, on the device
     forwards_backwards(post, seq, full=False)              the backward half    -> (score, occ, emit_row, emit_prob)
     forwards_backwards_batch(post | rows + row_off, seqs)  (csrc/forward_backward.hip, design/forward_backward.md)
+    viterbi_marginals_batch(post[T,B,S], klen, ...)        the decoder's sum-product twin: state marginals, log Z, a confidence per
+                                                           called position (csrc/lattice_marginals.hip, design/lattice_marginals.md)
 
 Inputs may be numpy arrays or device tensors; float32 arithmetic (the network's dtype).  float64 input is
 converted to float32 first -- unlike numpy, which would then decode in float64.  The forward score is the exception:
@@ -108,6 +110,80 @@ def viterbi_batch(post, klen, skip_pen=0.0, log=False, nbase=4, min_prob=None, w
                                     scores.data_ptr(), paths.data_ptr(), lens.data_ptr(), D.stream_ptr())
     _lib.check(rc, "decode.viterbi")
     return scores, paths, lens
+
+
+def viterbi_marginals_batch(post, klen, skip_pen=0.0, nbase=4, min_prob=1e-5, lengths=None, gamma=False, workspace_limit=None):
+    """viterbi_batch and, over the same lattice, the sum over ALL its paths (csrc/lattice_marginals.hip,
+    design/lattice_marginals.md): how much of the total likelihood passes through each state at each row, and how sure the called
+    path is of each of its positions.
+
+    post: [T, B, nbase^klen + 1] float32 (numpy or device tensor), the raw network output; min_prob: decode.prepare_post's floor,
+    applied first (None: `post` is taken as it is).  lengths: None, or per chunk the rows it owns (host integers or an int32 device
+    tensor), clamped to 1 .. T.  nbase 4 or 5, klen >= 3, at most 1024 k-mers.
+    -> (scores float32 [B], paths int32 [B, T], lens int32 [B]: the bits of viterbi_batch;
+        move_row int32 [B, T]: the row at which the path enters each of its states (-1 behind lens[b]);
+        conf float64 [B, T]: per position the largest marginal of its state over the rows it dwells on (0 behind lens[b]);
+        logz float64 [B]: the log of the summed weight of all paths;
+        and with gamma=True, gamma float32 [T, B, nbase^klen]: the marginals, every row of a chunk summing to 1), all on the device.
+    The forward rows of a launch live in a workspace of 9 nbase^klen + 20 bytes per row and chunk; the batch runs as consecutive
+    launches whose workspace stays within `workspace_limit` bytes (default transducer.WORKSPACE_LIMIT; a chunk's results do not depend
+    on the split).  A chunk that needs more on its own raises ValueError."""
+    import torch
+    from . import device as D
+    from . import transducer
+    pd = _dev(post)
+    if pd.dim() != 3:
+        raise ValueError("viterbi_marginals_batch expects [time, batch, state]")
+    T, B, S = pd.shape
+    if klen < 3:
+        raise ValueError("Kmer not long enough to apply Viterbi with skips")          # decode.py:50
+    if sv.nstate(klen, transducer=True, nbase=nbase) != S:
+        raise ValueError("posterior has %d states, klen=%d nbase=%d needs %d" % (S, klen, nbase, sv.nstate(klen, nbase=nbase)))
+    if min_prob is not None and not 0.0 <= float(min_prob) < 1.0:
+        raise ValueError("min_prob must lie in [0, 1)")
+    L = _lib.lib()
+    alone = int(L.slk_viterbi_marginals_workspace_bytes(T, 1, nbase, klen))
+    if T < 1 or B < 1 or alone == 0:
+        raise ValueError("the lattice marginals take nbase 4 or 5, klen >= 3 and at most 1024 k-mers")
+    limit = transducer.WORKSPACE_LIMIT if workspace_limit is None else int(workspace_limit)
+    if alone > limit:
+        raise ValueError("a chunk needs %d bytes of workspace, above the workspace_limit of %d" % (alone, limit))
+    lens_d = None
+    if lengths is not None:
+        lens_d = lengths if isinstance(lengths, torch.Tensor) else torch.as_tensor(np.asarray(lengths, dtype=np.int32))
+        if lens_d.numel() != B:
+            raise ValueError("lengths needs one entry per chunk")
+        lens_d = lens_d.to(device=pd.device, dtype=torch.int32).contiguous()
+    nk = nbase ** klen
+    dev = pd.device
+    scores = D.scratch(B, torch.float32, dev, result=True)
+    paths = D.scratch((B, T), torch.int32, dev, result=True)
+    lens = D.scratch(B, torch.int32, dev, result=True)
+    move_row = D.scratch((B, T), torch.int32, dev, result=True)
+    conf = D.scratch((B, T), torch.float64, dev, result=True)
+    logz = D.scratch(B, torch.float64, dev, result=True)
+    gam = D.scratch((T, B, nk), torch.float32, dev, result=True) if gamma else None
+    per = max(1, min(B, limit // alone))                         # (the size is a multiple of 256 per call, never more than B * alone)
+    runs = [(lo, min(lo + per, B)) for lo in range(0, B, per)]
+    ws = torch.empty(int(L.slk_viterbi_marginals_workspace_bytes(T, runs[0][1] - runs[0][0], nbase, klen)), dtype=torch.uint8, device=dev)
+    mode = _lib.POST_RAW if min_prob is not None else _lib.POST_PLAIN
+    with profiler.region("lattice_marginals", 20.0 * T * B * nk, float(T) * B * (8.0 * S + 18.0 * nk)):
+        for lo, hi in runs:
+            n = hi - lo
+            whole = n == B
+            sub = pd if whole else pd[:, lo:hi].contiguous()
+            g = gam if whole or gam is None else torch.empty((T, n, nk), dtype=torch.float32, device=dev)
+            rc = L.slk_viterbi_marginals_f32(sub.data_ptr(), T, n, nbase, klen, float(skip_pen), mode,
+                                             float(min_prob if min_prob is not None else 0.0),
+                                             None if lens_d is None else lens_d[lo:hi].data_ptr(), ws.data_ptr(),
+                                             int(L.slk_viterbi_marginals_workspace_bytes(T, n, nbase, klen)),
+                                             scores[lo:hi].data_ptr(), paths[lo:hi].data_ptr(), lens[lo:hi].data_ptr(),
+                                             move_row[lo:hi].data_ptr(), conf[lo:hi].data_ptr(), logz[lo:hi].data_ptr(), D.ptr(g),
+                                             D.stream_ptr())
+            _lib.check(rc, "decode.viterbi_marginals")
+            if g is not None and not whole:
+                gam[:, lo:hi] = g
+    return (scores, paths, lens, move_row, conf, logz) + ((gam,) if gamma else ())
 
 
 def viterbi_logits_batch(logits, stats, klen, T, B, ld=None, skip_pen=0.0, nbase=4, min_prob=1e-5, workspace=None,

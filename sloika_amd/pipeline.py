@@ -325,6 +325,56 @@ class Basecaller(object):
         scores, paths, lens = self.call_chunks(chunks)
         return scores, bio.paths_to_bases(paths, lens, self.kmer_len, alphabet, always_move=True)
 
+    def _marginals(self, post, lengths=None):
+        """decode.viterbi_marginals_batch on a materialised posterior with this Basecaller's decoder settings."""
+        return decode.viterbi_marginals_batch(post, self.kmer_len, skip_pen=self.skip, nbase=self.nbase, min_prob=self.min_prob,
+                                              lengths=lengths)
+
+    def _qual_check(self, who):
+        if not self.transducer:
+            raise NotImplementedError("%s is built on the transducer decoder's lattice" % who)
+
+    def call_chunks_qual(self, chunks, scaling=None):
+        """call_chunks with a confidence per called position (design/lattice_marginals.md): the decoder's lattice is summed over all its
+        paths on the posterior posteriors() leaves (csrc/lattice_marginals.hip).  chunks, scaling: as in call_chunks.
+        -> device tensors (scores, paths, lens: the bits Basecaller(fused_decode=False).call_chunks returns; move_row int32 [B, T'], the
+        row at which the path enters each state; conf float64 [B, T'], per position the largest marginal of its state over its dwell;
+        logz float64 [B], the log of the summed weight of all paths).  bio.paths_to_bases_qual turns paths and conf into letters with
+        Phred values."""
+        self._qual_check("call_chunks_qual")
+        with self._scope():
+            return self._marginals(self.posteriors(chunks, scaling))
+
+    def call_reads_qual(self, signals, trim=(0, 0), open_pore_fraction=0.0, scaling=None):
+        """call_reads with a confidence per called position: the same upload, trimming and failures, the network on the zero-padded batch
+        with per-read lengths, then the lattice of every read over its own rows of the posterior -- each read gets what a batch-1 call
+        gives.  -> (scores, paths, lens, move_row, conf, logz) as call_chunks_qual returns them, and the per-read sample counts."""
+        self._qual_check("call_reads_qual")
+        net = self.network
+        if not isinstance(net, layers.Serial) or type(net.layers[-1]) is not layers.Softmax:
+            raise ValueError("call_reads_qual needs a Serial network ending in a Softmax layer")
+        if min(len(s) for s in signals) < 100:
+            raise ValueError("a read is shorter than one window of 100 samples")
+        dev, start, nsamp, flags = self._trimmed_read_set(signals, trim, open_pore_fraction, scaling)
+        for r, f in enumerate(flags):
+            if f:
+                raise ValueError(batch.read_failure(f)[2].format(r))
+        padded = batch.pack_batch(dev, start, nsamp, max(nsamp))
+        with self._scope():
+            lengths = layers.ragged_lengths(nsamp)
+            post, steps = self._ragged_run(batch.normalise_reads_ragged(padded, lengths), lengths)
+            return self._marginals(post, steps) + (nsamp,)
+
+    def call_fastq(self, signals, names=None, trim=(0, 0), open_pore_fraction=0.0, scaling=None, alphabet='ACGT', qmax=60):
+        """Whole reads -> FASTQ records (call_reads_qual, bio.paths_to_bases_qual, bio.fastq_text): a list with one four-line record
+        per read, qualities as Phred + 33 capped at qmax; names default to read0, read1, ...  ''.join(records) is the file."""
+        from . import bio
+        res = self.call_reads_qual(signals, trim=trim, open_pore_fraction=open_pore_fraction, scaling=scaling)
+        calls = bio.paths_to_bases_qual(res[1], res[2], res[4], self.kmer_len, alphabet, qmax=qmax)
+        if names is None:
+            names = ["read%d" % r for r in range(len(calls))]
+        return [bio.fastq_text([n], [seq], [q]) for n, (seq, q) in zip(names, calls)]
+
     def score_chunks(self, chunks, sequences, full=True, scaling=None):
         """How likely is each sequence under the network's posterior of its chunk, summed over all alignments: decode.forwards
         (decode.py:108-139) of basecall.decode_post's prepared posterior (min_prob as in call_chunks), for the whole batch in one
