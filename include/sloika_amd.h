@@ -462,6 +462,21 @@ SLK_API int slk_viterbi_marginals_f32(const float *post, int T, int B, int nbase
                               float min_prob, const int32_t *lens, void *workspace, size_t workspace_bytes, float *score_out,
                               int32_t *path_out, int32_t *len_out, int32_t *move_row, double *conf, double *logz, float *gamma,
                               slk_stream_t stream);
+/* f8. slk_viterbi_marginals_f32 with checkpointed forward rows (design/lattice_marginals.md 8): the same arguments, limits and
+ * refusals, and on the same input the same bits in every output, for every legal `every`.  Pass 1 keeps the forward state of every
+ * `every`-th row only (row 0 included); pass 2 recomputes each segment of `every` rows into LDS just before it walks down it, so no
+ * forward row travels to device memory and the workspace shrinks about `every`-fold.
+ *   every      : rows per checkpoint, K.  0: the launcher's choice for N (36 KiB of LDS for the segment: 4 at N = 1024, more for a
+ *                smaller N, at most 64); < 0: SLK_ERR_INVALID_ARG; a K whose segment buffer of 9 N K bytes does not fit into the
+ *                160 KiB of a CU's LDS beside the kernel's 21.1 KiB (K >= 16 at N = 1024): SLK_ERR_UNSUPPORTED; nothing is written
+ *   workspace  : 8-byte aligned, slk_viterbi_marginals_ckpt_workspace_bytes(T, B, nbase, klen, every) bytes: ceil(T / K)
+ *                checkpoints of 13 N bytes per chunk (float64 forward row, float32 max-plus row, a traceback byte per state) and 20
+ *                bytes per row and chunk, else SLK_ERR_WORKSPACE and nothing is written. */
+SLK_API size_t slk_viterbi_marginals_ckpt_workspace_bytes(int T, int B, int nbase, int klen, int every); /* host only; 0 when refused */
+SLK_API int slk_viterbi_marginals_ckpt_f32(const float *post, int T, int B, int nbase, int klen, float skip_pen, int input_mode,
+                                   float min_prob, const int32_t *lens, int every, void *workspace, size_t workspace_bytes,
+                                   float *score_out, int32_t *path_out, int32_t *len_out, int32_t *move_row, double *conf,
+                                   double *logz, float *gamma, slk_stream_t stream);
 /* decode.prepare_post on its own: out = min_prob + (1-min_prob)*post (decode.py:36).                        */
 SLK_API int slk_prepare_post_f32(const float *post, float *out, size_t count, float min_prob, slk_stream_t stream);
 /* decode.argmax (decode.py:5-18), batched: per (b) the states with argmax != blank, minus 1 if

@@ -95,6 +95,8 @@ PROTOTYPES = {
     "slk_viterbi_kmer_f32": (_i, [_vp, _i, _i, _i, _i, _f, _i, _f, _vp, _sz, _vp, _vp, _vp, _vp]),
     "slk_viterbi_marginals_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "slk_viterbi_marginals_f32": (_i, [_vp, _i, _i, _i, _i, _f, _i, _f, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "slk_viterbi_marginals_ckpt_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "slk_viterbi_marginals_ckpt_f32": (_i, [_vp, _i, _i, _i, _i, _f, _i, _f, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "slk_paths_to_bases_qual": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, C.c_ulonglong, _vp, _vp, _l, _vp, _vp]),
     "slk_log_post_f32": (_i, [_vp, _vp, _sz, _i, _f, _vp]),
     "slk_prepare_post_f32": (_i, [_vp, _vp, _sz, _f, _vp]),

@@ -112,7 +112,35 @@ def viterbi_batch(post, klen, skip_pen=0.0, log=False, nbase=4, min_prob=None, w
     return scores, paths, lens
 
 
-def viterbi_marginals_batch(post, klen, skip_pen=0.0, nbase=4, min_prob=1e-5, lengths=None, gamma=False, workspace_limit=None):
+def marginals_rows_per_checkpoint(checkpoint):
+    """The `every` argument of slk_viterbi_marginals_ckpt_f32 for viterbi_marginals_batch's `checkpoint`: None for None (the stored-row
+    kernel), 0 for True (the kernel's own choice), else the integer K >= 1."""
+    if checkpoint is None:
+        return None
+    if checkpoint is True:
+        return 0
+    if checkpoint is False or int(checkpoint) != checkpoint or int(checkpoint) < 1:
+        raise ValueError("checkpoint is None, True or the rows per checkpoint (an integer >= 1)")
+    return int(checkpoint)
+
+
+def marginals_default_rows(nbase, klen):
+    """The rows per checkpoint slk_viterbi_marginals_ckpt_f32 takes for every = 0: what 36 KiB of LDS hold of 9 nbase^klen bytes per
+    row, at most 64 (csrc/lattice_marginals.hip, lmc_every; design/lattice_marginals.md 8)."""
+    return max(1, min(64, (36 * 1024) // (9 * nbase ** klen)))
+
+
+def marginals_workspace_bytes(T, B, nbase, klen, checkpoint=None):
+    """Bytes of workspace one launch of viterbi_marginals_batch takes for B chunks of T rows (0 for a shape the kernels refuse)."""
+    L = _lib.lib()
+    every = marginals_rows_per_checkpoint(checkpoint)
+    if every is None:
+        return int(L.slk_viterbi_marginals_workspace_bytes(T, B, nbase, klen))
+    return int(L.slk_viterbi_marginals_ckpt_workspace_bytes(T, B, nbase, klen, every))
+
+
+def viterbi_marginals_batch(post, klen, skip_pen=0.0, nbase=4, min_prob=1e-5, lengths=None, gamma=False, workspace_limit=None,
+                            checkpoint=None):
     """viterbi_batch and, over the same lattice, the sum over ALL its paths (csrc/lattice_marginals.hip,
     design/lattice_marginals.md): how much of the total likelihood passes through each state at each row, and how sure the called
     path is of each of its positions.
@@ -127,13 +155,19 @@ def viterbi_marginals_batch(post, klen, skip_pen=0.0, nbase=4, min_prob=1e-5, le
         and with gamma=True, gamma float32 [T, B, nbase^klen]: the marginals, every row of a chunk summing to 1), all on the device.
     The forward rows of a launch live in a workspace of 9 nbase^klen + 20 bytes per row and chunk; the batch runs as consecutive
     launches whose workspace stays within `workspace_limit` bytes (default transducer.WORKSPACE_LIMIT; a chunk's results do not depend
-    on the split).  A chunk that needs more on its own raises ValueError."""
+    on the split).  A chunk that needs more on its own raises ValueError.
+
+    checkpoint: None runs slk_viterbi_marginals_f32 as above.  True, or an integer K >= 1, runs slk_viterbi_marginals_ckpt_f32, which
+    keeps the forward state of every K-th row only (True: the kernel's own K for nbase^klen) and recomputes the rows between in LDS:
+    about 13 nbase^klen / K + 20 bytes per row and chunk, which is then what `workspace_limit` splits by.  Every output has the same
+    bits whatever `checkpoint` is."""
     import torch
     from . import device as D
     from . import transducer
     pd = _dev(post)
     if pd.dim() != 3:
         raise ValueError("viterbi_marginals_batch expects [time, batch, state]")
+    every = marginals_rows_per_checkpoint(checkpoint)
     T, B, S = pd.shape
     if klen < 3:
         raise ValueError("Kmer not long enough to apply Viterbi with skips")          # decode.py:50
@@ -142,7 +176,11 @@ def viterbi_marginals_batch(post, klen, skip_pen=0.0, nbase=4, min_prob=1e-5, le
     if min_prob is not None and not 0.0 <= float(min_prob) < 1.0:
         raise ValueError("min_prob must lie in [0, 1)")
     L = _lib.lib()
-    alone = int(L.slk_viterbi_marginals_workspace_bytes(T, 1, nbase, klen))
+
+    def need(n):
+        return marginals_workspace_bytes(T, n, nbase, klen, checkpoint)
+
+    alone = need(1) if T >= 1 else 0
     if T < 1 or B < 1 or alone == 0:
         raise ValueError("the lattice marginals take nbase 4 or 5, klen >= 3 and at most 1024 k-mers")
     limit = transducer.WORKSPACE_LIMIT if workspace_limit is None else int(workspace_limit)
@@ -165,7 +203,7 @@ def viterbi_marginals_batch(post, klen, skip_pen=0.0, nbase=4, min_prob=1e-5, le
     gam = D.scratch((T, B, nk), torch.float32, dev, result=True) if gamma else None
     per = max(1, min(B, limit // alone))                         # (the size is a multiple of 256 per call, never more than B * alone)
     runs = [(lo, min(lo + per, B)) for lo in range(0, B, per)]
-    ws = torch.empty(int(L.slk_viterbi_marginals_workspace_bytes(T, runs[0][1] - runs[0][0], nbase, klen)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(need(runs[0][1] - runs[0][0]), dtype=torch.uint8, device=dev)
     mode = _lib.POST_RAW if min_prob is not None else _lib.POST_PLAIN
     with profiler.region("lattice_marginals", 20.0 * T * B * nk, float(T) * B * (8.0 * S + 18.0 * nk)):
         for lo, hi in runs:
@@ -173,13 +211,14 @@ def viterbi_marginals_batch(post, klen, skip_pen=0.0, nbase=4, min_prob=1e-5, le
             whole = n == B
             sub = pd if whole else pd[:, lo:hi].contiguous()
             g = gam if whole or gam is None else torch.empty((T, n, nk), dtype=torch.float32, device=dev)
-            rc = L.slk_viterbi_marginals_f32(sub.data_ptr(), T, n, nbase, klen, float(skip_pen), mode,
-                                             float(min_prob if min_prob is not None else 0.0),
-                                             None if lens_d is None else lens_d[lo:hi].data_ptr(), ws.data_ptr(),
-                                             int(L.slk_viterbi_marginals_workspace_bytes(T, n, nbase, klen)),
-                                             scores[lo:hi].data_ptr(), paths[lo:hi].data_ptr(), lens[lo:hi].data_ptr(),
-                                             move_row[lo:hi].data_ptr(), conf[lo:hi].data_ptr(), logz[lo:hi].data_ptr(), D.ptr(g),
-                                             D.stream_ptr())
+            head = (sub.data_ptr(), T, n, nbase, klen, float(skip_pen), mode, float(min_prob if min_prob is not None else 0.0),
+                    None if lens_d is None else lens_d[lo:hi].data_ptr())
+            tail = (ws.data_ptr(), need(n), scores[lo:hi].data_ptr(), paths[lo:hi].data_ptr(), lens[lo:hi].data_ptr(),
+                    move_row[lo:hi].data_ptr(), conf[lo:hi].data_ptr(), logz[lo:hi].data_ptr(), D.ptr(g), D.stream_ptr())
+            if every is None:
+                rc = L.slk_viterbi_marginals_f32(*(head + tail))
+            else:
+                rc = L.slk_viterbi_marginals_ckpt_f32(*(head + (every,) + tail))
             _lib.check(rc, "decode.viterbi_marginals")
             if g is not None and not whole:
                 gam[:, lo:hi] = g

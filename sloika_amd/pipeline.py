@@ -325,10 +325,10 @@ class Basecaller(object):
         scores, paths, lens = self.call_chunks(chunks)
         return scores, bio.paths_to_bases(paths, lens, self.kmer_len, alphabet, always_move=True)
 
-    def _marginals(self, post, lengths=None):
+    def _marginals(self, post, lengths=None, checkpoint=None, workspace_limit=None):
         """decode.viterbi_marginals_batch on a materialised posterior with this Basecaller's decoder settings."""
         return decode.viterbi_marginals_batch(post, self.kmer_len, skip_pen=self.skip, nbase=self.nbase, min_prob=self.min_prob,
-                                              lengths=lengths)
+                                              lengths=lengths, checkpoint=checkpoint, workspace_limit=workspace_limit)
 
     def _qual_check(self, who):
         if not self.transducer:
@@ -535,17 +535,21 @@ class Basecaller(object):
                 sys.stderr.write("Failure calling read {}: {}\n".format(r if ids is None else ids[r], batch.read_failure(f)[1]))
 
     @staticmethod
-    def length_buckets(nsamp, max_batch=256, max_waste=0.08):
+    def length_buckets(nsamp, max_batch=256, max_waste=0.08, footprint=None):
         """Group read indices into batches of similar length: reads sorted by length, a batch closed when it holds `max_batch`
         reads or when padding every member to the longest would waste more than `max_waste` of the batch's steps.  -> list of
-        index lists (longest reads first: the big batches start while the host still packs the small ones)."""
+        index lists (longest reads first: the big batches start while the host still packs the small ones).
+
+        footprint (default: off): a pair (bytes_of, limit) -- bytes_of(longest sample count, reads) gives the device bytes a batch of
+        that shape holds; a batch is also closed before one more read would take it past `limit`."""
         order = sorted(range(len(nsamp)), key=lambda i: -nsamp[i])
         buckets, cur = [], []
         for i in order:
             if cur:
                 lmax = nsamp[cur[0]]
                 used = sum(nsamp[j] for j in cur) + nsamp[i]
-                if len(cur) >= max_batch or 1.0 - used / float(lmax * (len(cur) + 1)) > max_waste:
+                if (len(cur) >= max_batch or 1.0 - used / float(lmax * (len(cur) + 1)) > max_waste
+                        or (footprint is not None and footprint[0](lmax, len(cur) + 1) > footprint[1])):
                     buckets.append(cur)
                     cur = []
             cur.append(i)
@@ -555,7 +559,7 @@ class Basecaller(object):
 
     @classmethod
     def prepare_read_batches(cls, network, signals, trim=(0, 0), open_pore_fraction=0.0, max_batch=256, max_waste=0.08, ids=None,
-                             scaling=None, **kwargs):
+                             scaling=None, footprint=None, **kwargs):
         """Preparation of the whole-read mode: the read set goes to the device in one upload, trimming bounds come from one launch over
         all windows (basecall.py:111-112), reads are bucketed by length and every bucket becomes a zero-padded device batch (one launch
         per bucket).  -> (batches, nsamp): batches = [(read indices, padded device tensor [B, Lmax], their sample counts)], nsamp =
@@ -567,13 +571,17 @@ class Basecaller(object):
         on (basecall.py:103-115).  The other reads of the set are unaffected.
 
         scaling: as in call_reads -- int16 reads go to the device as they are and are scaled there (batch.upload_read_set), the
-        check for samples that are not finite coming out of the same kernel."""
+        check for samples that are not finite coming out of the same kernel.
+
+        footprint: as in length_buckets; a read whose batch of one is past the limit raises ValueError before any batch is packed."""
         # the host touches every sample once; the padded batches are built on the device (a launch per bucket)
         dev, start, nsamp, flags = cls._trimmed_read_set(signals, trim, open_pore_fraction, scaling)
         cls._report_failures(flags, ids)
         good = [r for r in range(len(nsamp)) if nsamp[r] > 0]
+        if footprint is not None:
+            cls._check_footprints([nsamp[r] for r in good], [r if ids is None else ids[r] for r in good], footprint)
         batches = []
-        for sub in cls.length_buckets([nsamp[r] for r in good], max_batch, max_waste):
+        for sub in cls.length_buckets([nsamp[r] for r in good], max_batch, max_waste, footprint):
             idx = [good[j] for j in sub]
             ns = [nsamp[i] for i in idx]
             batches.append((idx, batch.pack_batch(dev, [start[i] for i in idx], ns, max(ns)), ns))
@@ -661,6 +669,159 @@ class Basecaller(object):
         if streamed:
             stats["streamed"] = True
         return scores, paths, nsamp, stats
+
+    #: the share of the device's free memory call_reads_bucketed_qual gives its resident buckets when no memory_limit is named
+    QUAL_MEMORY_FRACTION = 0.5
+
+    @staticmethod
+    def _check_footprints(nsamp, names, footprint):
+        bytes_of, limit = footprint
+        for n, name in zip(nsamp, names):
+            if bytes_of(n, 1) > limit:
+                raise ValueError("read {}: its {} samples need {} bytes on the device on their own, above its lane's share of {}"
+                                 .format(name, n, bytes_of(n, 1), limit))
+
+    def _out_steps(self, nsamp):
+        """Rows of the posterior for a read of `nsamp` samples: the sample count mapped through every Convolution's stride."""
+        steps = int(nsamp)
+        for layer in self.network.layers:
+            if isinstance(layer, layers.Convolution):
+                steps = max(1, int(layer.out_len(steps)))
+        return steps
+
+    def qual_footprint(self, nsamp, reads, checkpoint=True):
+        """Device bytes a ragged batch of `reads` reads, the longest of `nsamp` samples, holds while its qualities are made: the
+        posterior [T', reads, nstate] float32 and the marginals' workspace (computed from the shapes, nothing is measured)."""
+        steps = self._out_steps(nsamp)
+        return (4 * steps * reads * (self.nbase ** self.kmer_len + 1)
+                + decode.marginals_workspace_bytes(steps, reads, self.nbase, self.kmer_len, checkpoint))
+
+    def _call_padded_qual(self, padded, nsamp, checkpoint=True):
+        """_call_padded with qualities: the posterior of the ragged batch, then the checkpointed lattice marginals of every read over
+        its own rows, in one launch.  -> (scores, paths, lens, move_row, conf, logz) on the device."""
+        with self._scope():
+            lengths = layers.ragged_lengths(nsamp)
+            post, steps = self._ragged_run(batch.normalise_reads_ragged(padded, lengths), lengths)
+            one_launch = decode.marginals_workspace_bytes(post.shape[0], post.shape[1], self.nbase, self.kmer_len, checkpoint)
+            return self._marginals(post, steps, checkpoint=checkpoint, workspace_limit=one_launch)
+
+    @classmethod
+    def _queue_read_batches_qual(cls, batches, lanes, checkpoint, to_host=True):
+        """Every prepared batch queued on its lane (batch k on lane k % lanes), with `to_host` its results' way to the host behind it:
+        into pinned memory, so that the copies do not hold the host up and every batch is queued before the first one is done.
+        Nothing waits: a lane's posterior and workspace go back to the allocator in stream order, where the lane's next batch finds
+        them.  -> [(read indices, host tensors, event, device tensors, lane)]."""
+        import torch
+        cur = torch.cuda.current_stream()
+        pending = []
+        for k, (idx, padded, ns) in enumerate(batches):
+            bc, s = lanes[k % len(lanes)]
+            s.wait_stream(cur)
+            with torch.cuda.stream(s):
+                padded.record_stream(s)
+                res = bc._call_padded_qual(padded, ns, checkpoint)
+                host = ()
+                if to_host:
+                    host = tuple(torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in res)
+                ev = torch.cuda.Event()
+                ev.record(s)
+            pending.append((idx, host, ev, res, k % len(lanes)))
+        return pending
+
+    @classmethod
+    def _bucketed_qual(cls, network, signals, trim, open_pore_fraction, max_batch, max_waste, in_flight, lanes, scaling, memory_limit,
+                       kwargs, to_host=True):
+        """The shared body of call_reads_bucketed_qual and fastq_bucketed -> (pending batches, lanes, nsamp, stats)."""
+        import torch
+        cls._transducer_only(kwargs, "call_reads_bucketed_qual")
+        if not isinstance(network, layers.Serial) or type(network.layers[-1]) is not layers.Softmax:
+            raise ValueError("call_reads_bucketed_qual needs a Serial network ending in a Softmax layer")
+        kwargs = dict(kwargs)
+        checkpoint = kwargs.pop("checkpoint", True)
+        if checkpoint is None:
+            raise ValueError("call_reads_bucketed_qual runs the checkpointed marginals: checkpoint is True or the rows per checkpoint")
+        if lanes is None:
+            # as many lanes as the set has buckets by length alone, at most 8 (run_read_batches)
+            raw = [len(s) - trim[0] - trim[1] for s in signals if len(s) > trim[0] + trim[1]]
+            nlane = max(1, min(8, len(cls.length_buckets(raw, max_batch, max_waste)))) if in_flight is None else in_flight
+            lanes = cls.read_lanes(network, nlane, **kwargs)
+        bc = lanes[0][0]
+        if memory_limit is None:
+            # free memory, and what torch's allocator holds without using it (it hands that back when a request needs it)
+            idle = torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
+            memory_limit = int(cls.QUAL_MEMORY_FRACTION * (torch.cuda.mem_get_info()[0] + idle))
+        share = int(memory_limit) // len(lanes)
+
+        def bytes_of(nsamp, reads):
+            return bc.qual_footprint(nsamp, reads, checkpoint)
+
+        if open_pore_fraction == 0:
+            # what the host knows without a launch: trimming takes exactly trim[0] + trim[1] samples off a read that can be called
+            cls._check_footprints([max(1, len(s) - trim[0] - trim[1]) for s in signals], range(len(signals)), (bytes_of, share))
+        batches, nsamp = cls.prepare_read_batches(network, signals, trim, open_pore_fraction, max_batch, max_waste, scaling=scaling,
+                                                  footprint=(bytes_of, share), **kwargs)
+        pending = cls._queue_read_batches_qual(batches, lanes, checkpoint, to_host)
+        used, padded = sum(nsamp), sum(ns[0] * len(idx) for idx, _, ns in batches)
+        every = decode.marginals_rows_per_checkpoint(checkpoint)
+        stats = {"reads": len(nsamp), "batches": len(batches), "samples": used, "padded_samples": padded,
+                 "padded_step_waste": 1.0 - used / float(max(padded, 1)), "failed": cls.failed_reads(nsamp),
+                 "lanes": len(lanes), "memory_limit": int(memory_limit),
+                 "peak_bucket_bytes": max([bytes_of(ns[0], len(idx)) for idx, _, ns in batches] or [0]),
+                 "rows_per_checkpoint": every or decode.marginals_default_rows(bc.nbase, bc.kmer_len)}
+        return pending, lanes, nsamp, stats
+
+    @classmethod
+    def call_reads_bucketed_qual(cls, network, signals, trim=(0, 0), open_pore_fraction=0.0, max_batch=256, max_waste=0.08,
+                                 in_flight=None, lanes=None, scaling=None, memory_limit=None, **kwargs):
+        """call_reads_bucketed with a confidence per called position (design/lattice_marginals.md 8): the same preparation
+        (prepare_read_batches), buckets and lanes; per bucket the ragged posterior (_ragged_run) and the checkpointed lattice marginals
+        (slk_viterbi_marginals_ckpt_f32) of every read over its own rows.  Each read gets bit for bit what call_reads_qual([read])
+        gives.  -> (scores [N] float32, paths, move_rows, confs: lists of N host arrays (int32, int32, float64, one entry per called
+        position), logz [N] float64, sample counts [N], stats), all on the host.  A read that cannot be called is reported and left
+        out as call_reads_bucketed does it: score and logz NaN, path, move rows and confidences None, sample count 0, listed in
+        stats["failed"].
+
+        memory_limit: the bytes of posterior plus marginals workspace that the buckets resident at one time -- one per lane -- may
+        hold together (default: QUAL_MEMORY_FRACTION of the device's free memory, what torch's allocator holds idle counted as free,
+        read once per call).  It is a condition on computed sizes:
+        a bucket is closed before it outgrows its lane's share, memory_limit / lanes (length_buckets' footprint), and a read that
+        exceeds the share on its own raises ValueError naming the read before the network or the marginals are launched for any
+        read.  stats holds "memory_limit", "peak_bucket_bytes" (the largest bucket's computed footprint), "lanes" and
+        "rows_per_checkpoint".  The set is always prepared first (no streamed upload).  kwargs: Basecaller's, and `checkpoint` (True,
+        or the rows per checkpoint) for decode.viterbi_marginals_batch."""
+        pending, _, nsamp, stats = cls._bucketed_qual(network, signals, trim, open_pore_fraction, max_batch, max_waste, in_flight, lanes,
+                                                      scaling, memory_limit, kwargs)
+        n = len(nsamp)
+        scores, logz = np.full(n, np.nan, dtype=np.float32), np.full(n, np.nan, dtype=np.float64)
+        paths, rows, confs = [None] * n, [None] * n, [None] * n
+        for idx, host, ev, _, _ in pending:
+            ev.synchronize()
+            sc, pa, le, mr, cf, lz = (h.numpy() for h in host)
+            for j, i in enumerate(idx):
+                scores[i], logz[i] = sc[j], lz[j]
+                paths[i], rows[i], confs[i] = pa[j, :le[j]].copy(), mr[j, :le[j]].copy(), cf[j, :le[j]].copy()
+        return scores, paths, rows, confs, logz, nsamp, stats
+
+    @classmethod
+    def fastq_bucketed(cls, network, signals, names=None, trim=(0, 0), open_pore_fraction=0.0, max_batch=256, max_waste=0.08,
+                       in_flight=None, lanes=None, scaling=None, memory_limit=None, alphabet='ACGT', qmax=60, **kwargs):
+        """Whole read sets -> FASTQ records: call_reads_bucketed_qual's flow, letters and Phred values per bucket on the device
+        (bio.paths_to_bases_qual).  -> a list with one four-line record per read -- character for character the record call_fastq
+        gives for that read -- and None for a read that could not be called; names default to read0, read1, ..."""
+        import torch
+        from . import bio
+        pending, lanes, nsamp, _ = cls._bucketed_qual(network, signals, trim, open_pore_fraction, max_batch, max_waste, in_flight, lanes,
+                                                      scaling, memory_limit, kwargs, to_host=False)
+        if names is None:
+            names = ["read%d" % r for r in range(len(nsamp))]
+        records = [None] * len(nsamp)
+        for idx, _, ev, res, lane in pending:                  # every bucket is queued by now: the lanes run while the host reads
+            bc, s = lanes[lane]
+            with torch.cuda.stream(s):
+                calls = bio.paths_to_bases_qual(res[1], res[2], res[4], bc.kmer_len, alphabet, qmax=qmax)
+            for i, (seq, q) in zip(idx, calls):
+                records[i] = bio.fastq_text([names[i]], [seq], [q])
+        return records
 
     _UPLOAD_STREAMS = {}
 
