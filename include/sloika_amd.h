@@ -986,6 +986,58 @@ SLK_API int slk_genome_seed_votes_u8(const uint8_t *q, long ldq, const int32_t *
 SLK_API int slk_genome_windows_u8(const uint8_t *genome, long G, const int64_t *start, const int64_t *end, const int32_t *minus,
                                   const int64_t *out_off, int B, long max_len, uint8_t *out, slk_stream_t stream);
 
+/* f9. The alignments of f7 / f8 on top of each other: counts per position of the packed genome and the consensus they give
+ * (csrc/pileup.hip; design/pileup.md section 1 DEFINES the forward view, the left-normalisation of gaps, the tables and the call, and
+ * is not repeated here).  Integer only; the tables are added to with integer atomics, so they depend on no launch shape or order.
+ *   slk_pileup_columns_u8: q, ldq, qlen, r, roff, rows, ops, ops_off, ops_bytes as slk_align_traceback_batch_u8 took and left them,
+ *     tb_status its status.  minus:[B] device int32 (non-zero: the pair was aligned against the reverse-complemented window), keep:[B]
+ *     device bytes, t0:[B] device int64, the packed-genome position of the forward view's first reference letter, G (host) the packed
+ *     genome's length.  fcodes: a buffer of ops_bytes bytes that does not overlap `ops`; pair b's forward view goes to
+ *     fcodes[ops_off[b] .. ops_off[b + 1]), left-normalised when normalise != 0.  status:[B] int32: SLK_PILEUP_DONE,
+ *     SLK_PILEUP_SKIPPED (keep[b] == 0, or tb_status[b] is not SLK_ALIGN_TB_DONE: nothing else of the pair is looked at) or a
+ *     negative SLK_PILEUP_* code.  Rows and codes are device data and are not trusted: a pair whose spans leave [0, qlen] /
+ *     [0, rlen] (lengths beyond 65535 or the row pitch included), whose counts are negative or do not add up to the spans, whose ops
+ *     slice is not its column count long or lies outside ops_bytes, whose t0 is negative or has t0 + r_span > G, that holds a code
+ *     byte above 3, or whose codes of a kind are not as many as its row says is REFUSED: nothing but its status is written, its
+ *     slice of fcodes is left as it was.  No loop bound depends on a value that has not passed these checks.
+ *   slk_pileup_count_u8: adds the pairs whose status (the array above) is SLK_PILEUP_DONE into counts:[hi - lo][8] and
+ *     ins:[hi - lo][max_ins][5] int32, the tables of packed positions [lo, hi), 0 <= lo <= hi <= G, max_ins 1..SLK_PILEUP_MAX_INS
+ *     (SLK_ERR_INVALID_ARG otherwise).  The caller zeroes the tables once; calls only ever add.  counts entries: 0..3 A C G T of a
+ *     query letter aligned to the position (of the forward strand: a '-' pair's letters are complemented), 4 another query letter,
+ *     5 deletion, 6 SLK_PILEUP_INS_READS reads with an insertion directly behind the position, 7 SLK_PILEUP_SPAN reads whose
+ *     alignment covers this reference letter and the next.  ins[p][k][c]: class c of the k-th letter of an insertion behind p, k <
+ *     max_ins.  Columns outside [lo, hi) are walked and not counted.  The rows are checked again (a pair that fails adds nothing): no
+ *     read depends on the status array being the one the first entry wrote.
+ *   slk_pileup_call_u8: per position of [lo, hi) the call of section 1.4 from the two tables and genome:[G]: letters:[hi - lo][1 +
+ *     max_ins] bytes of which the first nlet[p] (0 .. 1 + max_ins) are the position's part of the consensus and the rest 0,
+ *     flags:[hi - lo] bytes of SLK_PILEUP_FLAG_*.  A position whose depth (entries 0..5) is under min_depth, or that has no A, C, G, T
+ *     or deletion, keeps the genome's byte and gets SLK_PILEUP_FLAG_LOW.  counts must be 16-byte aligned.                        */
+#define SLK_PILEUP_MAX_INS 16
+#define SLK_PILEUP_INS_READS 6
+#define SLK_PILEUP_SPAN 7
+#define SLK_PILEUP_FLAG_LOW 1
+#define SLK_PILEUP_FLAG_CHANGED 2  /* a substitution or a deletion against the reference letter */
+#define SLK_PILEUP_FLAG_INSERTED 4
+#define SLK_PILEUP_DONE 0
+#define SLK_PILEUP_SKIPPED 1
+#define SLK_PILEUP_BAD_SPAN (-1)   /* a span outside [0, qlen] / [0, rlen], or a length beyond 65535 or the row pitch   */
+#define SLK_PILEUP_BAD_COUNT (-2)  /* a negative count                                                                   */
+#define SLK_PILEUP_BAD_SUM (-3)    /* the spans are not the sums of the counts                                           */
+#define SLK_PILEUP_OPS (-4)        /* the pair's ops slice is not its column count long, or outside `ops`                */
+#define SLK_PILEUP_POSITION (-5)   /* t0 < 0 or t0 + r_span > G                                                          */
+#define SLK_PILEUP_BAD_CODE (-6)   /* a code byte above 3                                                                */
+#define SLK_PILEUP_CODE_COUNT (-7) /* the columns of a kind are not as many as the row says                              */
+SLK_API int slk_pileup_columns_u8(const uint8_t *q, long ldq, const int32_t *qlen, const uint8_t *r, const int64_t *roff,
+                                  const int32_t *rows, const uint8_t *ops, const int64_t *ops_off, size_t ops_bytes,
+                                  const int32_t *tb_status, const int32_t *minus, const uint8_t *keep, const int64_t *t0, long G, int B,
+                                  int normalise, uint8_t *fcodes, int32_t *status, slk_stream_t stream);
+SLK_API int slk_pileup_count_u8(const uint8_t *q, long ldq, const int32_t *qlen, const int64_t *roff, const int32_t *rows,
+                                const uint8_t *fcodes, const int64_t *ops_off, size_t ops_bytes, const int32_t *status,
+                                const int32_t *minus, const int64_t *t0, long G, int B, long lo, long hi, int max_ins, int32_t *counts,
+                                int32_t *ins, slk_stream_t stream);
+SLK_API int slk_pileup_call_u8(const int32_t *counts, const int32_t *ins, const uint8_t *genome, long G, long lo, long hi, int max_ins,
+                               int min_depth, uint8_t *letters, uint8_t *nlet, uint8_t *flags, slk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,9 @@ PROTOTYPES = {
     "slk_genome_seed_workspace_bytes": (_sz, [_i, _i, _l, _i]),
     "slk_genome_seed_votes_u8": (_i, [_vp, _l, _vp, _i, _i, _vp, _i, _l, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "slk_genome_windows_u8": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _i, _l, _vp, _vp]),
+    "slk_pileup_columns_u8": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _l, _i, _i, _vp, _vp, _vp]),
+    "slk_pileup_count_u8": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _l, _i, _l, _l, _i, _vp, _vp, _vp]),
+    "slk_pileup_call_u8": (_i, [_vp, _vp, _vp, _l, _l, _l, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -16,7 +16,7 @@ import os
 
 import numpy as np
 
-from . import _lib, align, util
+from . import _lib, align, transducer, util
 
 #: added to every diagonal p - i: keeps it positive and makes the bins independent of the batch (csrc/genome_map.hip)
 DIAG0 = 65536
@@ -359,3 +359,233 @@ def read_references(index, res, strand, info, query_lengths, names, min_coverage
     text = out.cpu().numpy().tobytes().decode('ascii')
     records = [(trim_fast5_extension(names[b]), text[off[j]:off[j + 1]]) for j, b in enumerate(keep)]
     return records, [names[b] + ".fast5" for b in keep]
+
+
+# ---- pileup and consensus (csrc/pileup.hip, design/pileup.md) ----------------------------------------------------------------------
+
+#: entries of a row of Pileup.counts(): query letters by class, deletions, reads with an insertion behind the position, and `span`,
+#: the reads whose alignment covers this reference letter and the next one
+PILEUP_FIELDS = ("A", "C", "G", "T", "other", "deletion", "insertion_reads", "span")
+MAX_INS = 16
+#: bits of Consensus.flags (include/sloika_amd.h: SLK_PILEUP_FLAG_*)
+FLAG_LOW, FLAG_CHANGED, FLAG_INSERTED = 1, 2, 4
+#: per-pair status of Pileup.add (include/sloika_amd.h: SLK_PILEUP_*)
+PILEUP_DONE, PILEUP_SKIPPED = 0, 1
+PILEUP_REASONS = {
+    -1: "a span of its row lies outside the sequences",
+    -2: "its row has a negative count",
+    -3: "the spans of its row are not the sums of its counts",
+    -4: "its slice of the column codes does not have the length of its alignment",
+    -5: "its alignment does not lie inside the packed genome",
+    -6: "a byte of its columns is no column code",
+    -7: "its columns of a kind are not as many as its row says",
+}
+
+
+class Pileup(object):
+    """Zeroed count tables on the device for a span of the packed genome of `index`, to which batches of mapped reads are added
+    (design/pileup.md section 1 defines every quantity).
+
+    region: (contig name or index, start, end) within that contig, or None for the whole genome.  max_ins: S, the insertion
+    letters kept per position, 1..16.  The tables take (8 + 5 S) * 4 bytes per position; a span that needs more than memory_limit
+    raises a ValueError: pile such a genome region by region."""
+
+    def __init__(self, index, region=None, max_ins=4, memory_limit=transducer.WORKSPACE_LIMIT):
+        import torch
+        if int(max_ins) != max_ins or max_ins < 1 or max_ins > MAX_INS:
+            raise ValueError("genome: max_ins = %r outside 1..%d" % (max_ins, MAX_INS))
+        self.index, self.S = index, int(max_ins)
+        if region is None:
+            self.lo, self.hi = 0, index.G
+        else:
+            c, start, end = region
+            if not isinstance(c, (int, np.integer)):
+                if c not in index.names:
+                    raise ValueError("genome: region= names the contig %r, which the index does not hold" % (c,))
+                c = index.names.index(c)
+            if c < 0 or c >= len(index.names) or start < 0 or end < start or end > index.lengths[c]:
+                raise ValueError("genome: region=%r lies outside the contig" % (region,))
+            self.lo, self.hi = int(index.offsets[c]) + int(start), int(index.offsets[c]) + int(end)
+        self.P = self.hi - self.lo
+        nbytes = self.P * (8 + 5 * self.S) * 4
+        if nbytes > memory_limit:
+            raise ValueError("genome: the tables of %d positions take %d bytes, above the limit of %d: pile it in pieces with region="
+                             % (self.P, nbytes, memory_limit))
+        dev = index.genome.device
+        self.counts_dev = torch.zeros((max(self.P, 1), 8), dtype=torch.int32, device=dev)
+        self.ins_dev = torch.zeros((max(self.P, 1), self.S, 5), dtype=torch.int32, device=dev)
+        self.status = np.zeros(0, dtype=np.int32)
+        self._fcodes = self._offsets = None
+        self._names = None
+
+    def add(self, res, strand, info, ops, keep=None, normalise=True, names=None):
+        """Add the alignments of one batch: the values Index.map / map_paths return with ops=True.  keep: bool mask of the reads to
+        add (info['edge'] == 0 is the usual filter: an alignment cut by its window's end says nothing about the letters behind
+        it); unmapped reads and empty alignments are skipped anyway.  normalise: move every gap as far to the front of the forward
+        strand as its letters allow, so that both strands vote for the same place; off only to study the aligner's own placement.
+        -> host int32 status per read: PILEUP_DONE, PILEUP_SKIPPED or a negative code of PILEUP_REASONS (then nothing of the read
+        was added; `check` / `columns` raise a ValueError that names it).  May be called any number of times."""
+        import torch
+        from . import device as D
+        B = len(ops)
+        if len(res) != B or len(strand) != B:
+            raise ValueError("genome: %d rows but the columns of %d reads" % (len(res), B))
+        keep = np.ones(B, dtype=bool) if keep is None else np.asarray(keep, dtype=bool)
+        if keep.shape != (B,):
+            raise ValueError("genome: keep= is a mask of %d reads, not of %d" % (keep.size, B))
+        self._names = names
+        self._fcodes, self._offsets = None, ops.offsets
+        self.status = np.zeros(B, dtype=np.int32)
+        if B == 0:
+            return self.status
+        if len(ops.parts) != 1:
+            raise ValueError("genome: a pileup takes the columns of Index.map / map_paths (one reference buffer)")
+        ref, roff, rows_d, tb_d = ops.parts[0]
+        dev = ops.codes_dev.device
+        minus = np.asarray(strand) == '-'
+        rows = np.asarray(ops.rows)
+        t0 = np.where(minus, np.asarray(info['window_end'], dtype=np.int64) - rows[:, 4],
+                      np.asarray(info['window_start'], dtype=np.int64) + rows[:, 3]).astype(np.int64)
+        minus_d = torch.from_numpy(minus.astype(np.int32)).to(dev)
+        keep_d = torch.from_numpy(keep.astype(np.uint8)).to(dev)
+        t0_d = torch.from_numpy(t0).to(dev)
+        fcodes = torch.zeros_like(ops.codes_dev)
+        st_d = torch.empty(B, dtype=torch.int32, device=dev)
+        L = _lib.lib()
+        _lib.check(L.slk_pileup_columns_u8(ops.q.data_ptr(), ops.ldq, ops.qlen.data_ptr(), ref.data_ptr(), roff.data_ptr(),
+                                           rows_d.data_ptr(), ops.codes_dev.data_ptr(), ops.offsets_dev.data_ptr(),
+                                           ops.codes_dev.numel(), tb_d.data_ptr(), minus_d.data_ptr(), keep_d.data_ptr(),
+                                           t0_d.data_ptr(), self.index.G, B, int(bool(normalise)), fcodes.data_ptr(),
+                                           st_d.data_ptr(), D.stream_ptr()), "pileup_columns")
+        _lib.check(L.slk_pileup_count_u8(ops.q.data_ptr(), ops.ldq, ops.qlen.data_ptr(), roff.data_ptr(), rows_d.data_ptr(),
+                                         fcodes.data_ptr(), ops.offsets_dev.data_ptr(), fcodes.numel(), st_d.data_ptr(),
+                                         minus_d.data_ptr(), t0_d.data_ptr(), self.index.G, B, self.lo, self.hi, self.S,
+                                         self.counts_dev.data_ptr(), self.ins_dev.data_ptr(), D.stream_ptr()), "pileup_count")
+        self.status = st_d.cpu().numpy()
+        self._fcodes = fcodes
+        return self.status
+
+    def check(self, b):
+        if self.status[b] < 0:
+            raise ValueError("genome: read %s was not piled: %s"
+                             % (self._names[b] if self._names is not None else b,
+                                PILEUP_REASONS.get(int(self.status[b]), "status %d" % self.status[b])))
+
+    def columns(self, b):
+        """uint8 host array: the forward-view codes of read b of the last `add` (empty for a read that was skipped)."""
+        self.check(b)
+        if self.status[b] != PILEUP_DONE or self._fcodes is None:
+            return np.zeros(0, dtype=np.uint8)
+        if not isinstance(self._fcodes, np.ndarray):
+            self._fcodes = self._fcodes.cpu().numpy()
+        return self._fcodes[self._offsets[b]:self._offsets[b + 1]]
+
+    def counts(self):
+        """Host int32 [P, 8] (PILEUP_FIELDS)."""
+        return self.counts_dev[:self.P].cpu().numpy()
+
+    def insertions(self):
+        """Host int32 [P, max_ins, 5]: classes A C G T other of the k-th letter of an insertion behind the position."""
+        return self.ins_dev[:self.P].cpu().numpy()
+
+    def consensus(self, min_depth=3):
+        """The call of every position (slk_pileup_call_u8) -> Consensus."""
+        import torch
+        from . import device as D
+        dev = self.counts_dev.device
+        n = max(self.P, 1)
+        letters = torch.zeros((n, 1 + self.S), dtype=torch.uint8, device=dev)
+        nlet = torch.zeros(n, dtype=torch.uint8, device=dev)
+        flags = torch.zeros(n, dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib().slk_pileup_call_u8(self.counts_dev.data_ptr(), self.ins_dev.data_ptr(), self.index.genome.data_ptr(),
+                                                 self.index.G, self.lo, self.hi, self.S, int(min_depth), letters.data_ptr(),
+                                                 nlet.data_ptr(), flags.data_ptr(), D.stream_ptr()), "pileup_call")
+        return Consensus(self, letters[:self.P], nlet[:self.P], flags[:self.P], int(min_depth))
+
+
+class Consensus(object):
+    """The calls of a Pileup.  letters_dev:[P, 1 + max_ins] uint8, nlet_dev:[P], flags_dev:[P] on the device; `flags` the host copy
+    (FLAG_LOW: too little depth, the genome's letter was kept; FLAG_CHANGED: a substitution or a deletion; FLAG_INSERTED)."""
+
+    def __init__(self, pileup, letters, nlet, flags, min_depth):
+        self.pileup, self.letters_dev, self.nlet_dev, self.flags_dev, self.min_depth = pileup, letters, nlet, flags, min_depth
+        self.flags = flags.cpu().numpy()
+
+    def sequences(self):
+        """[(contig name, str)]: the region's part of every contig it touches, in genome order: the selected letters in order
+        (a mask and a cumulative sum on the device)."""
+        import torch
+        pl, ix = self.pileup, self.pileup.index
+        if pl.P == 0:
+            return []
+        width = self.letters_dev.shape[1]
+        mask = torch.arange(width, device=self.nlet_dev.device)[None, :] < self.nlet_dev[:, None]
+        text = self.letters_dev[mask].cpu().numpy().tobytes().decode('ascii')
+        ends = torch.cumsum(self.nlet_dev.to(torch.int64), 0).cpu().numpy()
+        out = []
+        for c in range(ix.contig_of(pl.lo), ix.contig_of(pl.hi - 1) + 1):
+            s, e = max(int(ix.offsets[c]), pl.lo) - pl.lo, min(int(ix.offsets[c + 1]), pl.hi) - pl.lo
+            if e > s:
+                out.append((ix.names[c], text[int(ends[s - 1]) if s else 0:int(ends[e - 1])]))
+        return out
+
+    def variants(self):
+        """Host list of (contig name, position within the contig, kind, ref, alt, depth, support), in position order.  kind 'sub':
+        ref and alt are letters, depth the position's depth (query letters + deletions) and support the winner's count; 'del': alt
+        is '', support the deletions; 'ins': ref is '', alt the letters inserted BEHIND the position, depth its `span` entry and
+        support the reads with an insertion there.  Gaps are left-normalised: one in a repeat is reported at the repeat's front."""
+        pl, ix = self.pileup, self.pileup.index
+        hit = np.flatnonzero(self.flags & (FLAG_CHANGED | FLAG_INSERTED))
+        if not len(hit):
+            return []
+        import torch
+        hit_d = torch.from_numpy(hit).to(self.letters_dev.device)
+        letters, nlet = self.letters_dev[hit_d].cpu().numpy(), self.nlet_dev[hit_d].cpu().numpy()
+        counts, ref = pl.counts_dev[hit_d].cpu().numpy(), ix.genome[hit_d + pl.lo].cpu().numpy()
+        out = []
+        for k, p in enumerate(hit):
+            c = ix.contig_of(pl.lo + int(p))
+            pos, cn, text = pl.lo + int(p) - int(ix.offsets[c]), counts[k], letters[k, :nlet[k]].tobytes().decode('ascii')
+            depth = int(cn[:6].sum())
+            deleted = _deletion_wins(cn, chr(ref[k]))
+            nins = len(text) - (0 if deleted else 1)
+            if deleted:
+                out.append((ix.names[c], pos, 'del', chr(ref[k]), '', depth, int(cn[5])))
+            elif self.flags[p] & FLAG_CHANGED:
+                out.append((ix.names[c], pos, 'sub', chr(ref[k]), text[0], depth, int(cn["ACGT".index(text[0])])))
+            if self.flags[p] & FLAG_INSERTED:
+                out.append((ix.names[c], pos, 'ins', '', text[len(text) - nins:], int(cn[7]), int(cn[6])))
+        return out
+
+    def summary(self):
+        """dict: `covered` (positions called, i.e. not FLAG_LOW), `substitutions`, `deleted` and `inserted` letters against the
+        genome, and `identity` = 1 - their sum / covered (nan without a covered position)."""
+        covered = int((self.flags & FLAG_LOW == 0).sum())
+        sub = dele = ins = 0
+        for _, _, kind, _, alt, _, _ in self.variants():
+            if kind == 'sub':
+                sub += 1
+            elif kind == 'del':
+                dele += 1
+            else:
+                ins += len(alt)
+        return {'covered': covered, 'substitutions': sub, 'deleted': dele, 'inserted': ins,
+                'identity': 1.0 - float(sub + dele + ins) / covered if covered else float('nan')}
+
+
+def _deletion_wins(cn, ref):
+    """Whether the winner of a position's counts is the deletion (design/pileup.md 1.4: the greatest of A C G T deletion; a tie to
+    the reference letter's class, else to the first in that order)."""
+    cand = [int(cn[0]), int(cn[1]), int(cn[2]), int(cn[3]), int(cn[5])]
+    best = max(cand)
+    r = "ACGT".find(ref)
+    return cand[4] == best and not (r >= 0 and cand[r] == best) and cand.index(best) == 4
+
+
+def pileup(index, res, strand, info, ops, region=None, max_ins=4, keep=None, normalise=True, min_depth=3,
+           memory_limit=transducer.WORKSPACE_LIMIT):
+    """The one-call form: Pileup(index, region, max_ins).add(res, strand, info, ops, keep, normalise) and its consensus.
+    -> (Pileup, Consensus)."""
+    p = Pileup(index, region=region, max_ins=max_ins, memory_limit=memory_limit)
+    p.add(res, strand, info, ops, keep=keep, normalise=normalise)
+    return p, p.consensus(min_depth=min_depth)
