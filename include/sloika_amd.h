@@ -1038,6 +1038,28 @@ SLK_API int slk_pileup_count_u8(const uint8_t *q, long ldq, const int32_t *qlen,
 SLK_API int slk_pileup_call_u8(const int32_t *counts, const int32_t *ins, const uint8_t *genome, long G, long lo, long hi, int max_ins,
                                int min_depth, uint8_t *letters, uint8_t *nlet, uint8_t *flags, slk_stream_t stream);
 
+/* f9, quality-weighted (design/pileup.md section 9 DEFINES the weight of a letter and of a column, the weighted tables and the
+ * weighted call, and is not repeated here).  Integer only.
+ *   slk_pileup_count_qual_u8: slk_pileup_count_u8 with qual:[B][ldq] device bytes (one quality byte per query letter, the pitch of q)
+ *     and weights:[256] device bytes.  Adds into counts / ins exactly what slk_pileup_count_u8 adds for the same input (one kernel
+ *     text) and, in the same pass, each column's weight into wcounts:[hi - lo][8] and wins:[hi - lo][max_ins][5] int32 (caller-zeroed,
+ *     only added to; same indices).  Any byte indexes `weights`, so qual needs no check.  Sums stay below 2^31 for depths up to 8.4
+ *     million (255 a letter at the most).  A pair whose row fails the checks adds nothing to any of the four tables.  A null qual,
+ *     weights, wcounts or wins gives SLK_ERR_INVALID_ARG.
+ *   slk_pileup_call_qual_u8: the weighted call per position of [lo, hi): the winner by weight (depth, for min_depth, is the plain one
+ *     of counts), letters / nlet / flags as slk_pileup_call_u8 writes them, letq:[hi - lo][1 + max_ins] the quality of every emitted
+ *     letter (unused slots 0) and posq:[hi - lo] the winner's lead over the runner-up, 0 .. qmax, written for a deletion too.  qmax
+ *     outside 1..93 gives SLK_ERR_INVALID_ARG.  counts and wcounts must be 16-byte aligned.                                      */
+SLK_API int slk_pileup_count_qual_u8(const uint8_t *q, long ldq, const int32_t *qlen, const uint8_t *qual, const int64_t *roff,
+                                     const int32_t *rows, const uint8_t *fcodes, const int64_t *ops_off, size_t ops_bytes,
+                                     const int32_t *status, const int32_t *minus, const int64_t *t0, long G, int B, long lo, long hi,
+                                     int max_ins, const uint8_t *weights, int32_t *counts, int32_t *ins, int32_t *wcounts,
+                                     int32_t *wins, slk_stream_t stream);
+SLK_API int slk_pileup_call_qual_u8(const int32_t *counts, const int32_t *ins, const int32_t *wcounts, const int32_t *wins,
+                                    const uint8_t *genome, long G, long lo, long hi, int max_ins, int min_depth, int qmax,
+                                    uint8_t *letters, uint8_t *nlet, uint8_t *flags, uint8_t *letq, uint8_t *posq,
+                                    slk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

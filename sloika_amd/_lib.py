@@ -173,6 +173,9 @@ PROTOTYPES = {
     "slk_pileup_columns_u8": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _l, _i, _i, _vp, _vp, _vp]),
     "slk_pileup_count_u8": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _l, _i, _l, _l, _i, _vp, _vp, _vp]),
     "slk_pileup_call_u8": (_i, [_vp, _vp, _vp, _l, _l, _l, _i, _i, _vp, _vp, _vp, _vp]),
+    "slk_pileup_count_qual_u8": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _l, _i, _l, _l, _i, _vp, _vp, _vp, _vp,
+                                      _vp, _vp]),
+    "slk_pileup_call_qual_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _l, _l, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

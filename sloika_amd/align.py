@@ -210,12 +210,14 @@ class Ops(object):
     negative code of TB_REASONS; touching such a pair raises a ValueError that names it.  rows: host [B, 9], every pair's row in
     the coordinates of the buffer its columns index.  q, ldq, qlen: the query buffer; parts: per strand buffer (reference buffer --
     for '-' the reverse-complemented one --, roff, the device rows that buffer's launch saw, its device status).
-    workspace_bytes: what the tracebacks needed in all."""
+    workspace_bytes: what the tracebacks needed in all.  qual: None, or a uint8 device tensor [B, ldq] with a quality byte beside
+    every letter of q (genome.Index.map(quals=) / map_paths(conf=) set it; a weighted genome.Pileup reads it)."""
 
     def __init__(self, q, ldq, qlen, parts, rows, codes, offsets, offsets_dev, status, workspace_bytes=0):
         self.q, self.ldq, self.qlen, self.parts, self.rows = q, ldq, qlen, parts, rows
         self.codes_dev, self.offsets, self.offsets_dev, self.status = codes, offsets, offsets_dev, status
         self.workspace_bytes = workspace_bytes
+        self.qual = None                                        # [B][ldq] quality bytes beside q, set by genome.Index.map / map_paths
         self._host = None
         self._qlen_host = None
 

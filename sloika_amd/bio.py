@@ -222,3 +222,33 @@ def fastq_text(names, bases, quals):
             raise ValueError("read %s: qualities must lie in 0 .. %d" % (name, PHRED_MAX))
         out.append("@%s\n%s\n+\n%s\n" % (name, seq, (q.astype(np.uint8) + 33).tobytes().decode('ascii')))
     return "".join(out)
+
+
+def fastq_records(text):
+    """The inverse of fastq_text: FASTQ text of four lines per record -> [(name, bases str, uint8 array of Phred values)].  A record
+    that is not '@name', letters, '+' (a repeated name is allowed), as many quality characters in '!' .. '~' raises a ValueError
+    that gives the record's number (from 1)."""
+    if isinstance(text, bytes):
+        text = text.decode('ascii')
+    lines = text.split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    if len(lines) % 4:
+        raise ValueError("fastq_records: record %d is cut short: %d lines are no whole number of records" % (len(lines) // 4 + 1, len(lines)))
+    out = []
+    for k in range(len(lines) // 4):
+        head, seq, plus, qual = lines[4 * k:4 * k + 4]
+        if not head.startswith("@"):
+            raise ValueError("fastq_records: record %d does not begin with '@'" % (k + 1))
+        if not plus.startswith("+") or (len(plus) > 1 and plus[1:] != head[1:]):
+            raise ValueError("fastq_records: record %d has no '+' line" % (k + 1))
+        if len(qual) != len(seq):
+            raise ValueError("fastq_records: record %d has %d qualities for %d letters" % (k + 1, len(qual), len(seq)))
+        try:
+            q = np.frombuffer(qual.encode('ascii'), dtype=np.uint8).astype(np.int16) - 33
+        except UnicodeEncodeError:
+            q = np.array([-1], dtype=np.int16)
+        if q.size and (q.min() < 0 or q.max() > PHRED_MAX):
+            raise ValueError("fastq_records: record %d has a quality character outside '!' .. '~'" % (k + 1))
+        out.append((head[1:], seq, q.astype(np.uint8)))
+    return out

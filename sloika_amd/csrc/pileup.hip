@@ -1,7 +1,7 @@
 // pileup.hip -- alignments on top of each other: per-position counts over the packed genome and the consensus they give, on the
 // device (design/pileup.md; the quantities are defined in its section 1 and nowhere else).
 //
-// Three kernels, all integer.
+// Five kernels, all integer.
 //   pileup_columns_kernel  one wave per pair: checks the pair (its row and codes are device data and are NOT trusted), copies its
 //                          columns into forward-strand order with all lanes and, when asked, moves every gap run as far to the
 //                          front as its letters allow (left-normalisation).  Runs are found 64 columns at a time from ballots of
@@ -12,6 +12,9 @@
 //                          column that is none (clz on a ballot plus the run carried in).  Adds into the tables with integer
 //                          atomics, which commute: the tables do not depend on the launch's shape or on any order.
 //   pileup_call_kernel     one thread per position: winner, insertion letters, flags.
+//   pileup_count_qual_kernel / pileup_call_qual_kernel: the same walk and the same call with a second pair of tables that hold sums
+//                          of per-letter weights (a table of 256 bytes indexed by the letter's quality byte) instead of heads, and a
+//                          quality per emitted letter (design/pileup.md section 9).
 #include "common.h"
 
 #define PILEUP_WAVES 4
@@ -154,12 +157,15 @@ __global__ void __launch_bounds__(64 * PILEUP_WAVES) pileup_columns_kernel(
     }
 }
 
-__global__ void __launch_bounds__(64 * PILEUP_WAVES) pileup_count_kernel(
-    const uint8_t *__restrict__ q, long ldq, const int32_t *__restrict__ qlen, const int64_t *__restrict__ roff,
-    const int32_t *__restrict__ rows, const uint8_t *__restrict__ fcodes,
+// The walk of both count kernels.  WEIGHTED adds each column's weight (design/pileup.md section 9) into wcounts / wins beside the 1
+// it adds into counts / ins; everything else is one text, so the plain tables of the two kernels cannot drift apart.
+template <bool WEIGHTED>
+__device__ __forceinline__ void pileup_count_body(
+    const uint8_t *__restrict__ q, long ldq, const int32_t *__restrict__ qlen, const uint8_t *__restrict__ qual,
+    const int64_t *__restrict__ roff, const int32_t *__restrict__ rows, const uint8_t *__restrict__ fcodes,
     const int64_t *__restrict__ ops_off, long long ops_bytes, const int32_t *__restrict__ status,
     const int32_t *__restrict__ minus, const int64_t *__restrict__ t0, long long G, int B, long long lo, long long hi, int S,
-    int32_t *counts, int32_t *ins)
+    const uint8_t *__restrict__ weights, int32_t *counts, int32_t *ins, int32_t *wcounts, int32_t *wins)
 {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * PILEUP_WAVES + (threadIdx.x >> 6);
@@ -174,6 +180,7 @@ __global__ void __launch_bounds__(64 * PILEUP_WAVES) pileup_count_kernel(
     const int n = row[2] - row[1], m = row[4] - row[3];
     const bool rev = minus[b] != 0;
     const uint8_t *qb = q + (size_t)b * ldq, *f = fcodes + o0;
+    const uint8_t *vb = WEIGHTED ? qual + (size_t)b * ldq : nullptr;
     const int qfirst = rev ? row[2] - 1 : row[1], step = rev ? -1 : 1;
     int ibase = 0, jbase = 0, carry = 0;                         // carry: insertion columns at the end of the columns so far
     for (int cb = 0; cb < ncol; cb += 64) {
@@ -191,24 +198,68 @@ __global__ void __launch_bounds__(64 * PILEUP_WAVES) pileup_count_kernel(
             cls = pileup_letter_class(qb[qfirst + step * i]);
             if (rev && cls < 4) cls = 3 - cls;
         }
+        int w = 0;                                               // the column's weight (section 9): any byte indexes the table
+        if (WEIGHTED) {
+            if (qc) {
+                if (i < n) w = weights[vb[qfirst + step * i]];
+            } else if (isdel) {                                  // the lighter of the query letters on either side, those that exist
+                const bool left = i - 1 >= 0 && i - 1 < n, right = i < n;
+                const int wl = left ? (int)weights[vb[qfirst + step * (i - 1)]] : 0;
+                const int wr = right ? (int)weights[vb[qfirst + step * i]] : 0;
+                w = left && right ? (wl < wr ? wl : wr) : left ? wl : wr;
+            }
+        }
         if (rc && j < m) {
             const long long p = tb + j;
             if (p >= lo && p < hi) {
                 int32_t *cp = counts + (size_t)(p - lo) * 8;
                 atomicAdd(cp + (isdel ? 5 : cls), 1);
                 if (j < m - 1) atomicAdd(cp + 7, 1);
+                if (WEIGHTED && w) {
+                    int32_t *wp = wcounts + (size_t)(p - lo) * 8;
+                    atomicAdd(wp + (isdel ? 5 : cls), w);
+                    if (j < m - 1) atomicAdd(wp + 7, w);
+                }
             }
         } else if (isins && j > 0) {                             // (an insertion in front of the first reference letter: nowhere)
             const long long p = tb + j - 1;
             if (p >= lo && p < hi) {
                 if (k == 0) atomicAdd(counts + (size_t)(p - lo) * 8 + 6, 1);
                 if (k < S) atomicAdd(ins + ((size_t)(p - lo) * S + k) * 5 + cls, 1);
+                if (WEIGHTED && w) {
+                    if (k == 0) atomicAdd(wcounts + (size_t)(p - lo) * 8 + 6, w);
+                    if (k < S) atomicAdd(wins + ((size_t)(p - lo) * S + k) * 5 + cls, w);
+                }
             }
         }
         carry = nonins ? nvalid - 1 - (63 - __clzll((long long)nonins)) : carry + nvalid;
         ibase += __popcll(mq);
         jbase += __popcll(mr);
     }
+}
+
+__global__ void __launch_bounds__(64 * PILEUP_WAVES) pileup_count_kernel(
+    const uint8_t *__restrict__ q, long ldq, const int32_t *__restrict__ qlen, const int64_t *__restrict__ roff,
+    const int32_t *__restrict__ rows, const uint8_t *__restrict__ fcodes,
+    const int64_t *__restrict__ ops_off, long long ops_bytes, const int32_t *__restrict__ status,
+    const int32_t *__restrict__ minus, const int64_t *__restrict__ t0, long long G, int B, long long lo, long long hi, int S,
+    int32_t *counts, int32_t *ins)
+{
+    pileup_count_body<false>(q, ldq, qlen, nullptr, roff, rows, fcodes, ops_off, ops_bytes, status, minus, t0, G, B, lo, hi, S, nullptr,
+                             counts, ins, nullptr, nullptr);
+}
+
+// The same walk with the Phred-weighted tables beside the plain ones.  The 256-byte weight table is read through the cache: every
+// wave reads the same 256 bytes, and LDS would cost a barrier in a kernel whose waves otherwise never meet.
+__global__ void __launch_bounds__(64 * PILEUP_WAVES) pileup_count_qual_kernel(
+    const uint8_t *__restrict__ q, long ldq, const int32_t *__restrict__ qlen, const uint8_t *__restrict__ qual,
+    const int64_t *__restrict__ roff, const int32_t *__restrict__ rows, const uint8_t *__restrict__ fcodes,
+    const int64_t *__restrict__ ops_off, long long ops_bytes, const int32_t *__restrict__ status,
+    const int32_t *__restrict__ minus, const int64_t *__restrict__ t0, long long G, int B, long long lo, long long hi, int S,
+    const uint8_t *__restrict__ weights, int32_t *counts, int32_t *ins, int32_t *wcounts, int32_t *wins)
+{
+    pileup_count_body<true>(q, ldq, qlen, qual, roff, rows, fcodes, ops_off, ops_bytes, status, minus, t0, G, B, lo, hi, S, weights,
+                            counts, ins, wcounts, wins);
 }
 
 __global__ void __launch_bounds__(PILEUP_CALL_THREADS) pileup_call_kernel(
@@ -260,6 +311,78 @@ __global__ void __launch_bounds__(PILEUP_CALL_THREADS) pileup_call_kernel(
     flags[p] = (uint8_t)fl;
 }
 
+// The weighted call of section 9: the winner by weight, a quality per emitted letter.  `depth` is the plain one of 1.4.
+__global__ void __launch_bounds__(PILEUP_CALL_THREADS) pileup_call_qual_kernel(
+    const int32_t *__restrict__ counts, const int32_t *__restrict__ wcounts, const int32_t *__restrict__ wins,
+    const uint8_t *__restrict__ genome, long long lo, long long P, int S, int min_depth, int qmax, uint8_t *__restrict__ letters,
+    uint8_t *__restrict__ nlet, uint8_t *__restrict__ flags, uint8_t *__restrict__ letq, uint8_t *__restrict__ posq)
+{
+    const long long p = (long long)blockIdx.x * PILEUP_CALL_THREADS + threadIdx.x;
+    if (p >= P) return;
+    int cn[8], wn[8];
+    {
+        const int4 a = reinterpret_cast<const int4 *>(counts)[p * 2], c = reinterpret_cast<const int4 *>(counts)[p * 2 + 1];
+        cn[0] = a.x; cn[1] = a.y; cn[2] = a.z; cn[3] = a.w;
+        cn[4] = c.x; cn[5] = c.y; cn[6] = c.z; cn[7] = c.w;
+        const int4 d = reinterpret_cast<const int4 *>(wcounts)[p * 2], e = reinterpret_cast<const int4 *>(wcounts)[p * 2 + 1];
+        wn[0] = d.x; wn[1] = d.y; wn[2] = d.z; wn[3] = d.w;
+        wn[4] = e.x; wn[5] = e.y; wn[6] = e.z; wn[7] = e.w;
+    }
+    const int refb = genome[lo + p], refc = pileup_letter_class(refb);
+    uint8_t *out = letters + (size_t)p * (1 + S), *oq = letq + (size_t)p * (1 + S);
+    const long long depth = (long long)cn[0] + cn[1] + cn[2] + cn[3] + cn[4] + cn[5];
+    int nl = 0, fl = 0, pq = 0;
+    if (depth < min_depth || (wn[0] | wn[1] | wn[2] | wn[3] | wn[5]) == 0) {
+        oq[nl] = 0;
+        out[nl++] = (uint8_t)refb;
+        fl = SLK_PILEUP_FLAG_LOW;
+    } else {
+        int best = -1, w = 0;
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            const int v = wn[k < 4 ? k : 5];
+            if (v > best) { best = v; w = k; }
+        }
+        if (refc < 4 && wn[refc] == best) w = refc;
+        int next = wn[4];                                        // the runner-up: the other four candidates and `other`
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            const int v = wn[k < 4 ? k : 5];
+            if (k != w && v > next) next = v;
+        }
+        pq = best - next < qmax ? best - next : qmax;            // (both lie in [0, 2^31): the difference cannot wrap)
+        if (pq < 0) pq = 0;
+        if (w < 4) {
+            oq[nl] = (uint8_t)pq;
+            out[nl++] = (uint8_t)("ACGT"[w]);
+        }
+        if (w == 4 || w != refc) fl |= SLK_PILEUP_FLAG_CHANGED;
+        const int32_t *ip = wins + (size_t)p * S * 5;
+        for (int k = 0; k < S; k++) {
+            long long nk = ip[k * 5 + 4];
+            int mx = 0, am = 0;
+#pragma unroll
+            for (int x = 0; x < 4; x++) {
+                const int v = ip[k * 5 + x];
+                nk += v;
+                if (v > mx) { mx = v; am = x; }
+            }
+            if (!(2ll * nk > (long long)wn[7] && mx > 0)) break;
+            const long long lead = 2ll * mx - (long long)wn[7];
+            oq[nl] = (uint8_t)(lead < 0 ? 0 : lead > qmax ? qmax : lead);
+            out[nl++] = (uint8_t)("ACGT"[am]);
+            fl |= SLK_PILEUP_FLAG_INSERTED;
+        }
+    }
+    for (int k = nl; k < 1 + S; k++) {
+        out[k] = 0;
+        oq[k] = 0;
+    }
+    nlet[p] = (uint8_t)nl;
+    flags[p] = (uint8_t)fl;
+    posq[p] = (uint8_t)pq;
+}
+
 extern "C" int slk_pileup_columns_u8(const uint8_t *q, long ldq, const int32_t *qlen, const uint8_t *r, const int64_t *roff,
                                      const int32_t *rows, const uint8_t *ops, const int64_t *ops_off, size_t ops_bytes,
                                      const int32_t *tb_status, const int32_t *minus, const uint8_t *keep, const int64_t *t0, long G,
@@ -301,5 +424,40 @@ extern "C" int slk_pileup_call_u8(const int32_t *counts, const int32_t *ins, con
     hipLaunchKernelGGL(pileup_call_kernel, dim3((unsigned)((P + PILEUP_CALL_THREADS - 1) / PILEUP_CALL_THREADS)),
                        dim3(PILEUP_CALL_THREADS), 0, slk_stream(stream), counts, ins, genome, (long long)lo, P, max_ins, min_depth,
                        letters, nlet, flags);
+    return slk_launch_status();
+}
+
+extern "C" int slk_pileup_count_qual_u8(const uint8_t *q, long ldq, const int32_t *qlen, const uint8_t *qual, const int64_t *roff,
+                                        const int32_t *rows, const uint8_t *fcodes, const int64_t *ops_off, size_t ops_bytes,
+                                        const int32_t *status, const int32_t *minus, const int64_t *t0, long G, int B, long lo,
+                                        long hi, int max_ins, const uint8_t *weights, int32_t *counts, int32_t *ins,
+                                        int32_t *wcounts, int32_t *wins, slk_stream_t stream)
+{
+    if (B < 0 || G < 0 || lo < 0 || hi < lo || hi > G || max_ins < 1 || max_ins > SLK_PILEUP_MAX_INS) return SLK_ERR_INVALID_ARG;
+    if (B == 0 || hi == lo) return SLK_OK;
+    if (!q || !qlen || !qual || !roff || !rows || !fcodes || !ops_off || !status || !minus || !t0 || !weights || !counts || !ins ||
+        !wcounts || !wins || ldq < 0)
+        return SLK_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(pileup_count_qual_kernel, dim3((B + PILEUP_WAVES - 1) / PILEUP_WAVES), dim3(64 * PILEUP_WAVES), 0,
+                       slk_stream(stream), q, ldq, qlen, qual, roff, rows, fcodes, ops_off, (long long)ops_bytes, status, minus, t0,
+                       (long long)G, B, (long long)lo, (long long)hi, max_ins, weights, counts, ins, wcounts, wins);
+    return slk_launch_status();
+}
+
+extern "C" int slk_pileup_call_qual_u8(const int32_t *counts, const int32_t *ins, const int32_t *wcounts, const int32_t *wins,
+                                       const uint8_t *genome, long G, long lo, long hi, int max_ins, int min_depth, int qmax,
+                                       uint8_t *letters, uint8_t *nlet, uint8_t *flags, uint8_t *letq, uint8_t *posq,
+                                       slk_stream_t stream)
+{
+    if (G < 0 || lo < 0 || hi < lo || hi > G || max_ins < 1 || max_ins > SLK_PILEUP_MAX_INS || qmax < 1 || qmax > 93)
+        return SLK_ERR_INVALID_ARG;
+    if (hi == lo) return SLK_OK;
+    if (!counts || !ins || !wcounts || !wins || !genome || !letters || !nlet || !flags || !letq || !posq ||
+        ((uintptr_t)counts & 15) || ((uintptr_t)wcounts & 15))
+        return SLK_ERR_INVALID_ARG;
+    const long long P = hi - lo;
+    hipLaunchKernelGGL(pileup_call_qual_kernel, dim3((unsigned)((P + PILEUP_CALL_THREADS - 1) / PILEUP_CALL_THREADS)),
+                       dim3(PILEUP_CALL_THREADS), 0, slk_stream(stream), counts, wcounts, wins, genome, (long long)lo, P, max_ins,
+                       min_depth, qmax, letters, nlet, flags, letq, posq);
     return slk_launch_status();
 }

@@ -184,7 +184,7 @@ class Index(object):
 
     # ---- map ---------------------------------------------------------------------------------------------------------------------
 
-    def _map_device(self, q, ldq, qlen, lens, max_qlen, names, drift, min_votes, scores, workspace_limit, ops=False):
+    def _map_device(self, q, ldq, qlen, lens, max_qlen, names, drift, min_votes, scores, workspace_limit, ops=False, qual=None):
         B = len(lens)
         seeds = self._seed_device(q, ldq, qlen, max_qlen)
         W = self.bin_width
@@ -222,6 +222,7 @@ class Index(object):
             rows_d = torch.cat(device_rows) if device_rows else torch.zeros((0, 9), dtype=torch.int32, device=qlen.device)
             columns = align._traceback_device(q, ldq, qlen, [(ref, roff_d, rows_d, np.ones(B, dtype=bool))], res.copy(), scores,
                                               workspace_limit)
+            columns.qual = qual                                 # [B][ldq] bytes beside the letters, or None; never fetched here
         edge = np.zeros(B, dtype=np.int32)
         for b in np.flatnonzero(res[:, 0] > 0):
             rs, re = int(res[b, 3]), int(res[b, 4])
@@ -239,7 +240,7 @@ class Index(object):
         return (res, strand, info, columns) if ops else (res, strand, info)
 
     def map(self, queries, drift=1.0 / 16, min_votes=3, match=1, mismatch=2, gap_open=2, gap_extend=1, workspace_limit=None,
-            names=None, ops=False):
+            names=None, ops=False, quals=None):
         """Place every query on the genome and align it there.  -> (res, strand, info).
 
         The strand with more votes wins (a tie goes to '+'); a query with fewer than min_votes is unmapped: its row of `res` is all
@@ -258,20 +259,42 @@ class Index(object):
 
         ops=True: one more value, the alignments' columns as an align.Ops (slk_align_traceback_batch_u8 on the windows: its rows
         are in window coordinates, for '-' against the reverse-complemented window; workspace_limit bounds the traceback's
-        workspace per launch as well).  sam_records turns them into SAM lines."""
+        workspace per launch as well).  sam_records turns them into SAM lines.
+
+        quals: one uint8 array per query, a quality per letter (FASTQ input; bio.fastq_records gives them).  They are uploaded
+        beside the letters, with the same pitch, and kept on the returned Ops as `ops.qual` for a weighted Pileup; they take no part
+        in the mapping.  An array whose length is not its query's raises a ValueError that names the read."""
         align._check_scores(match, mismatch, gap_open, gap_extend)
         queries = list(queries)
         _lib.require_gpu()
         q, ldq, qlen, lens, max_qlen = self._upload(queries)
+        qual = None
+        if quals is not None:
+            import torch
+            quals = list(quals)
+            if len(quals) != len(queries):
+                raise ValueError("genome: quals= holds %d arrays for %d queries" % (len(quals), len(queries)))
+            vh = np.zeros((len(queries), ldq), dtype=np.uint8)
+            for b, v in enumerate(quals):
+                v = np.asarray(v)
+                if v.ndim != 1 or len(v) != lens[b]:
+                    raise ValueError("genome: quals= of read %s has %d values for %d letters"
+                                     % (names[b] if names is not None else b, v.size, lens[b]))
+                vh[b, :len(v)] = v
+            qual = torch.from_numpy(vh).to(q.device)
         return self._map_device(q, ldq, qlen, lens, max_qlen, names, drift, min_votes,
-                                (int(match), int(mismatch), int(gap_open), int(gap_extend)), workspace_limit, ops)
+                                (int(match), int(mismatch), int(gap_open), int(gap_extend)), workspace_limit, ops, qual)
 
     def map_paths(self, paths, lens, kmer_len, alphabet='ACGT', drift=1.0 / 16, min_votes=3, match=1, mismatch=2, gap_open=2,
-                  gap_extend=1, workspace_limit=None, names=None, ops=False):
+                  gap_extend=1, workspace_limit=None, names=None, ops=False, conf=None, qmax=60):
         """`map` of decoded paths without the called sequences leaving the device: paths:[B, T] int32 device tensor of k-mer states
         and lens:[B] int32 device tensor, as any `call_*` returns them, become bases through slk_paths_to_bases(always_move=True)
         and that buffer is the query operand of the seed stage and of the aligner as it lies.  Only the base counts come to the
-        host.  -> (res, strand, info, nbases), with ops=True one more value, the align.Ops of `map`."""
+        host.  -> (res, strand, info, nbases), with ops=True one more value, the align.Ops of `map`.
+
+        conf: the float64 [B, T] device tensor of call_chunks_qual / decode.viterbi_marginals_batch.  The bases then come from
+        slk_paths_to_bases_qual (the same letters) and its quality buffer, Phred values capped at qmax with the pitch of the bases,
+        stays on the device as `ops.qual` for a weighted Pileup.  The rows do not depend on it."""
         import torch
         from . import device as D
         align._check_scores(match, mismatch, gap_open, gap_extend)
@@ -284,14 +307,26 @@ class Index(object):
         cap = max(kmer_len * max(Tmax, 1), kmer_len)
         bases = torch.empty((B, cap), dtype=torch.uint8, device=paths.device)
         nb = torch.empty((B,), dtype=torch.int32, device=paths.device)
-        _lib.check(_lib.lib().slk_paths_to_bases(paths.data_ptr(), paths.stride(0), lens.data_ptr(), B, kmer_len, len(alphabet), 1,
-                                                 int.from_bytes(alphabet.ljust(8, b'\0'), 'little'), bases.data_ptr(), cap,
-                                                 nb.data_ptr(), D.stream_ptr()), "paths_to_bases")
+        qual = None
+        if conf is None:
+            _lib.check(_lib.lib().slk_paths_to_bases(paths.data_ptr(), paths.stride(0), lens.data_ptr(), B, kmer_len, len(alphabet), 1,
+                                                     int.from_bytes(alphabet.ljust(8, b'\0'), 'little'), bases.data_ptr(), cap,
+                                                     nb.data_ptr(), D.stream_ptr()), "paths_to_bases")
+        else:
+            from . import bio
+            if conf.dtype != torch.float64 or conf.shape[0] != B or conf.shape[1] < Tmax or conf.stride(1) != 1:
+                raise ValueError("genome: conf= must be a float64 device tensor with one row per path and one entry per position")
+            table = torch.from_numpy(bio.phred_thresholds(qmax)).to(paths.device)
+            qual = torch.zeros((B, cap), dtype=torch.uint8, device=paths.device)
+            _lib.check(_lib.lib().slk_paths_to_bases_qual(paths.data_ptr(), paths.stride(0), lens.data_ptr(), conf.data_ptr(),
+                                                          conf.stride(0), table.data_ptr(), int(qmax), B, kmer_len, len(alphabet), 1,
+                                                          int.from_bytes(alphabet.ljust(8, b'\0'), 'little'), bases.data_ptr(),
+                                                          qual.data_ptr(), cap, nb.data_ptr(), D.stream_ptr()), "paths_to_bases_qual")
         counts = nb.cpu().numpy()
         max_qlen = int(counts.max()) if B else 0
         align._check_len(max_qlen, "a query")
         got = self._map_device(bases, cap, nb, counts, max_qlen, names, drift, min_votes,
-                               (int(match), int(mismatch), int(gap_open), int(gap_extend)), workspace_limit, ops)
+                               (int(match), int(mismatch), int(gap_open), int(gap_extend)), workspace_limit, ops, qual)
         return got[:3] + (counts,) + got[3:]
 
 
@@ -380,6 +415,14 @@ PILEUP_REASONS = {
     -6: "a byte of its columns is no column code",
     -7: "its columns of a kind are not as many as its row says",
 }
+#: the largest qmax of a weighted Pileup (bio.PHRED_MAX: Phred + 33 stays printable)
+QMAX_LIMIT = 93
+
+
+def quality_weights(min_qual=0, qmax=60):
+    """uint8 [256], the weight of a letter by its quality byte (design/pileup.md section 9): 0 below min_qual, else min(v, qmax)."""
+    v = np.arange(256)
+    return np.where(v < min_qual, 0, np.minimum(v, qmax)).astype(np.uint8)
 
 
 class Pileup(object):
@@ -388,13 +431,29 @@ class Pileup(object):
 
     region: (contig name or index, start, end) within that contig, or None for the whole genome.  max_ins: S, the insertion
     letters kept per position, 1..16.  The tables take (8 + 5 S) * 4 bytes per position; a span that needs more than memory_limit
-    raises a ValueError: pile such a genome region by region."""
+    raises a ValueError: pile such a genome region by region.
 
-    def __init__(self, index, region=None, max_ins=4, memory_limit=transducer.WORKSPACE_LIMIT):
+    weighted=True: a second pair of tables of the same shapes (wcounts_dev, wins_dev) holds sums of per-letter weights beside the
+    counts (design/pileup.md section 9), the memory check counts both pairs, and `add` needs the reads' qualities.  The weight of
+    a letter whose quality byte is v is weights[v]: 0 below min_qual, else min(v, qmax) (qmax 1..93); weights= passes a table of
+    256 bytes of the caller's own instead.  The decoder's Phred values order letters and are not calibrated error probabilities
+    (design/lattice_marginals.md section 6): a sum of them is a definition, not a likelihood."""
+
+    def __init__(self, index, region=None, max_ins=4, memory_limit=transducer.WORKSPACE_LIMIT, weighted=False, min_qual=0, qmax=60,
+                 weights=None):
         import torch
         if int(max_ins) != max_ins or max_ins < 1 or max_ins > MAX_INS:
             raise ValueError("genome: max_ins = %r outside 1..%d" % (max_ins, MAX_INS))
+        if int(qmax) != qmax or qmax < 1 or qmax > QMAX_LIMIT:
+            raise ValueError("genome: qmax = %r outside 1..%d" % (qmax, QMAX_LIMIT))
         self.index, self.S = index, int(max_ins)
+        self.weighted, self.qmax = bool(weighted), int(qmax)
+        if weights is None:
+            weights = quality_weights(min_qual, qmax)
+        weights = np.asarray(weights)
+        if weights.shape != (256,) or weights.min() < 0 or weights.max() > 255:
+            raise ValueError("genome: weights= is a table of 256 values in 0..255")
+        self.weights = weights.astype(np.uint8)
         if region is None:
             self.lo, self.hi = 0, index.G
         else:
@@ -407,27 +466,45 @@ class Pileup(object):
                 raise ValueError("genome: region=%r lies outside the contig" % (region,))
             self.lo, self.hi = int(index.offsets[c]) + int(start), int(index.offsets[c]) + int(end)
         self.P = self.hi - self.lo
-        nbytes = self.P * (8 + 5 * self.S) * 4
+        nbytes = self.P * (8 + 5 * self.S) * 4 * (2 if self.weighted else 1)
         if nbytes > memory_limit:
-            raise ValueError("genome: the tables of %d positions take %d bytes, above the limit of %d: pile it in pieces with region="
-                             % (self.P, nbytes, memory_limit))
+            raise ValueError("genome: the %stables of %d positions take %d bytes, above the limit of %d: pile it in pieces with region="
+                             % ("two pairs of " if self.weighted else "", self.P, nbytes, memory_limit))
         dev = index.genome.device
         self.counts_dev = torch.zeros((max(self.P, 1), 8), dtype=torch.int32, device=dev)
         self.ins_dev = torch.zeros((max(self.P, 1), self.S, 5), dtype=torch.int32, device=dev)
+        self.wcounts_dev = self.wins_dev = self.weights_dev = None
+        if self.weighted:
+            self.wcounts_dev, self.wins_dev = torch.zeros_like(self.counts_dev), torch.zeros_like(self.ins_dev)
+            self.weights_dev = torch.from_numpy(self.weights).to(dev)
         self.status = np.zeros(0, dtype=np.int32)
         self._fcodes = self._offsets = None
         self._names = None
 
-    def add(self, res, strand, info, ops, keep=None, normalise=True, names=None):
+    def add(self, res, strand, info, ops, keep=None, normalise=True, names=None, qual=None):
         """Add the alignments of one batch: the values Index.map / map_paths return with ops=True.  keep: bool mask of the reads to
         add (info['edge'] == 0 is the usual filter: an alignment cut by its window's end says nothing about the letters behind
         it); unmapped reads and empty alignments are skipped anyway.  normalise: move every gap as far to the front of the forward
         strand as its letters allow, so that both strands vote for the same place; off only to study the aligner's own placement.
         -> host int32 status per read: PILEUP_DONE, PILEUP_SKIPPED or a negative code of PILEUP_REASONS (then nothing of the read
-        was added; `check` / `columns` raise a ValueError that names it).  May be called any number of times."""
+        was added; `check` / `columns` raise a ValueError that names it).  May be called any number of times.
+
+        A weighted Pileup also needs a quality byte per query letter: `ops.qual`, as Index.map(quals=) and map_paths(conf=) leave
+        it, or qual=, a uint8 device tensor [B, ops.ldq]; without either it raises a ValueError.  An unweighted Pileup looks at
+        neither."""
         import torch
         from . import device as D
         B = len(ops)
+        if self.weighted:
+            if qual is None:
+                qual = getattr(ops, 'qual', None)
+            if qual is None:
+                raise ValueError("genome: a weighted pileup needs the reads' qualities: map with quals= / conf= (ops.qual) or pass "
+                                 "qual=")
+            if qual.dtype != torch.uint8 or tuple(qual.shape) != (B, ops.ldq) or not qual.is_contiguous() or \
+                    qual.device != ops.codes_dev.device:
+                raise ValueError("genome: qual= must be a contiguous uint8 device tensor of shape (%d, %d), the pitch of the queries"
+                                 % (B, ops.ldq))
         if len(res) != B or len(strand) != B:
             raise ValueError("genome: %d rows but the columns of %d reads" % (len(res), B))
         keep = np.ones(B, dtype=bool) if keep is None else np.asarray(keep, dtype=bool)
@@ -457,10 +534,18 @@ class Pileup(object):
                                            ops.codes_dev.numel(), tb_d.data_ptr(), minus_d.data_ptr(), keep_d.data_ptr(),
                                            t0_d.data_ptr(), self.index.G, B, int(bool(normalise)), fcodes.data_ptr(),
                                            st_d.data_ptr(), D.stream_ptr()), "pileup_columns")
-        _lib.check(L.slk_pileup_count_u8(ops.q.data_ptr(), ops.ldq, ops.qlen.data_ptr(), roff.data_ptr(), rows_d.data_ptr(),
-                                         fcodes.data_ptr(), ops.offsets_dev.data_ptr(), fcodes.numel(), st_d.data_ptr(),
-                                         minus_d.data_ptr(), t0_d.data_ptr(), self.index.G, B, self.lo, self.hi, self.S,
-                                         self.counts_dev.data_ptr(), self.ins_dev.data_ptr(), D.stream_ptr()), "pileup_count")
+        if self.weighted:
+            _lib.check(L.slk_pileup_count_qual_u8(ops.q.data_ptr(), ops.ldq, ops.qlen.data_ptr(), qual.data_ptr(), roff.data_ptr(),
+                                                  rows_d.data_ptr(), fcodes.data_ptr(), ops.offsets_dev.data_ptr(), fcodes.numel(),
+                                                  st_d.data_ptr(), minus_d.data_ptr(), t0_d.data_ptr(), self.index.G, B, self.lo,
+                                                  self.hi, self.S, self.weights_dev.data_ptr(), self.counts_dev.data_ptr(),
+                                                  self.ins_dev.data_ptr(), self.wcounts_dev.data_ptr(), self.wins_dev.data_ptr(),
+                                                  D.stream_ptr()), "pileup_count_qual")
+        else:
+            _lib.check(L.slk_pileup_count_u8(ops.q.data_ptr(), ops.ldq, ops.qlen.data_ptr(), roff.data_ptr(), rows_d.data_ptr(),
+                                             fcodes.data_ptr(), ops.offsets_dev.data_ptr(), fcodes.numel(), st_d.data_ptr(),
+                                             minus_d.data_ptr(), t0_d.data_ptr(), self.index.G, B, self.lo, self.hi, self.S,
+                                             self.counts_dev.data_ptr(), self.ins_dev.data_ptr(), D.stream_ptr()), "pileup_count")
         self.status = st_d.cpu().numpy()
         self._fcodes = fcodes
         return self.status
@@ -488,15 +573,44 @@ class Pileup(object):
         """Host int32 [P, max_ins, 5]: classes A C G T other of the k-th letter of an insertion behind the position."""
         return self.ins_dev[:self.P].cpu().numpy()
 
-    def consensus(self, min_depth=3):
-        """The call of every position (slk_pileup_call_u8) -> Consensus."""
+    def _need_weighted(self, what):
+        if not self.weighted:
+            raise ValueError("genome: %s needs a Pileup made with weighted=True" % what)
+
+    def weighted_counts(self):
+        """Host int32 [P, 8]: the sums of weights at the entries of `counts()`."""
+        self._need_weighted("weighted_counts()")
+        return self.wcounts_dev[:self.P].cpu().numpy()
+
+    def weighted_insertions(self):
+        """Host int32 [P, max_ins, 5]: the sums of weights at the entries of `insertions()`."""
+        self._need_weighted("weighted_insertions()")
+        return self.wins_dev[:self.P].cpu().numpy()
+
+    def consensus(self, min_depth=3, weighted=None):
+        """The call of every position -> Consensus.  weighted: None for the Pileup's own mode; True the weighted call of
+        slk_pileup_call_qual_u8 (a ValueError on a Pileup without weighted tables), whose Consensus has a quality per letter; False
+        the majority call of slk_pileup_call_u8 from the plain tables, which a weighted Pileup holds as well."""
         import torch
         from . import device as D
+        weighted = self.weighted if weighted is None else bool(weighted)
+        if weighted:
+            self._need_weighted("consensus(weighted=True)")
         dev = self.counts_dev.device
         n = max(self.P, 1)
         letters = torch.zeros((n, 1 + self.S), dtype=torch.uint8, device=dev)
         nlet = torch.zeros(n, dtype=torch.uint8, device=dev)
         flags = torch.zeros(n, dtype=torch.uint8, device=dev)
+        if weighted:
+            letq = torch.zeros((n, 1 + self.S), dtype=torch.uint8, device=dev)
+            posq = torch.zeros(n, dtype=torch.uint8, device=dev)
+            _lib.check(_lib.lib().slk_pileup_call_qual_u8(self.counts_dev.data_ptr(), self.ins_dev.data_ptr(),
+                                                          self.wcounts_dev.data_ptr(), self.wins_dev.data_ptr(),
+                                                          self.index.genome.data_ptr(), self.index.G, self.lo, self.hi, self.S,
+                                                          int(min_depth), self.qmax, letters.data_ptr(), nlet.data_ptr(),
+                                                          flags.data_ptr(), letq.data_ptr(), posq.data_ptr(), D.stream_ptr()),
+                       "pileup_call_qual")
+            return Consensus(self, letters[:self.P], nlet[:self.P], flags[:self.P], int(min_depth), letq[:self.P], posq[:self.P])
         _lib.check(_lib.lib().slk_pileup_call_u8(self.counts_dev.data_ptr(), self.ins_dev.data_ptr(), self.index.genome.data_ptr(),
                                                  self.index.G, self.lo, self.hi, self.S, int(min_depth), letters.data_ptr(),
                                                  nlet.data_ptr(), flags.data_ptr(), D.stream_ptr()), "pileup_call")
@@ -505,35 +619,62 @@ class Pileup(object):
 
 class Consensus(object):
     """The calls of a Pileup.  letters_dev:[P, 1 + max_ins] uint8, nlet_dev:[P], flags_dev:[P] on the device; `flags` the host copy
-    (FLAG_LOW: too little depth, the genome's letter was kept; FLAG_CHANGED: a substitution or a deletion; FLAG_INSERTED)."""
+    (FLAG_LOW: too little depth, the genome's letter was kept; FLAG_CHANGED: a substitution or a deletion; FLAG_INSERTED).
 
-    def __init__(self, pileup, letters, nlet, flags, min_depth):
+    A weighted call (Pileup.consensus(weighted=True)) also has letq_dev:[P, 1 + max_ins], the quality of every emitted letter, and
+    posq_dev:[P], the winner's lead over the runner-up per position (design/pileup.md section 9); `weighted` says which it is."""
+
+    def __init__(self, pileup, letters, nlet, flags, min_depth, letq=None, posq=None):
         self.pileup, self.letters_dev, self.nlet_dev, self.flags_dev, self.min_depth = pileup, letters, nlet, flags, min_depth
+        self.letq_dev, self.posq_dev, self.weighted = letq, posq, letq is not None
         self.flags = flags.cpu().numpy()
 
-    def sequences(self):
-        """[(contig name, str)]: the region's part of every contig it touches, in genome order: the selected letters in order
-        (a mask and a cumulative sum on the device)."""
+    def _selected(self, slots):
+        """The first nlet[p] entries of every row of `slots` in order, cut per contig -> [(contig name, uint8 host array)]."""
         import torch
         pl, ix = self.pileup, self.pileup.index
         if pl.P == 0:
             return []
-        width = self.letters_dev.shape[1]
+        width = slots.shape[1]
         mask = torch.arange(width, device=self.nlet_dev.device)[None, :] < self.nlet_dev[:, None]
-        text = self.letters_dev[mask].cpu().numpy().tobytes().decode('ascii')
+        flat = slots[mask].cpu().numpy()
         ends = torch.cumsum(self.nlet_dev.to(torch.int64), 0).cpu().numpy()
         out = []
         for c in range(ix.contig_of(pl.lo), ix.contig_of(pl.hi - 1) + 1):
             s, e = max(int(ix.offsets[c]), pl.lo) - pl.lo, min(int(ix.offsets[c + 1]), pl.hi) - pl.lo
             if e > s:
-                out.append((ix.names[c], text[int(ends[s - 1]) if s else 0:int(ends[e - 1])]))
+                out.append((ix.names[c], flat[int(ends[s - 1]) if s else 0:int(ends[e - 1])]))
         return out
 
-    def variants(self):
+    def sequences(self):
+        """[(contig name, str)]: the region's part of every contig it touches, in genome order: the selected letters in order
+        (a mask and a cumulative sum on the device)."""
+        return [(name, text.tobytes().decode('ascii')) for name, text in self._selected(self.letters_dev)]
+
+    def qualities(self):
+        """[(contig name, uint8 array)] of a weighted call, aligned letter for letter with `sequences()` (the same mask and
+        cumulative sum on the device)."""
+        if not self.weighted:
+            raise ValueError("genome: qualities() needs a weighted call: Pileup(weighted=True).consensus()")
+        return self._selected(self.letq_dev)
+
+    def fastq(self):
+        """FASTQ text of a weighted call, one record per contig (bio.fastq_text)."""
+        from . import bio
+        seqs, quals = self.sequences(), self.qualities()
+        return bio.fastq_text([name for name, _ in seqs], [text for _, text in seqs], [v for _, v in quals])
+
+    def variants(self, with_qual=False):
         """Host list of (contig name, position within the contig, kind, ref, alt, depth, support), in position order.  kind 'sub':
         ref and alt are letters, depth the position's depth (query letters + deletions) and support the winner's count; 'del': alt
         is '', support the deletions; 'ins': ref is '', alt the letters inserted BEHIND the position, depth its `span` entry and
-        support the reads with an insertion there.  Gaps are left-normalised: one in a repeat is reported at the repeat's front."""
+        support the reads with an insertion there.  Gaps are left-normalised: one in a repeat is reported at the repeat's front.
+
+        with_qual=True (a weighted call only) appends one value: the position's posq for 'sub' / 'del', the smallest quality among
+        the inserted letters for 'ins'.  depth and support stay the unweighted counts; in a weighted call the winner is the one by
+        weight."""
+        if with_qual and not self.weighted:
+            raise ValueError("genome: variants(with_qual=True) needs a weighted call: Pileup(weighted=True).consensus()")
         pl, ix = self.pileup, self.pileup.index
         hit = np.flatnonzero(self.flags & (FLAG_CHANGED | FLAG_INSERTED))
         if not len(hit):
@@ -542,19 +683,24 @@ class Consensus(object):
         hit_d = torch.from_numpy(hit).to(self.letters_dev.device)
         letters, nlet = self.letters_dev[hit_d].cpu().numpy(), self.nlet_dev[hit_d].cpu().numpy()
         counts, ref = pl.counts_dev[hit_d].cpu().numpy(), ix.genome[hit_d + pl.lo].cpu().numpy()
+        votes = pl.wcounts_dev[hit_d].cpu().numpy() if self.weighted else counts       # what the winner was chosen by
+        if with_qual:
+            letq, posq = self.letq_dev[hit_d].cpu().numpy(), self.posq_dev[hit_d].cpu().numpy()
         out = []
         for k, p in enumerate(hit):
             c = ix.contig_of(pl.lo + int(p))
             pos, cn, text = pl.lo + int(p) - int(ix.offsets[c]), counts[k], letters[k, :nlet[k]].tobytes().decode('ascii')
             depth = int(cn[:6].sum())
-            deleted = _deletion_wins(cn, chr(ref[k]))
+            deleted = _deletion_wins(votes[k], chr(ref[k]))
             nins = len(text) - (0 if deleted else 1)
             if deleted:
-                out.append((ix.names[c], pos, 'del', chr(ref[k]), '', depth, int(cn[5])))
+                out.append((ix.names[c], pos, 'del', chr(ref[k]), '', depth, int(cn[5])) + ((int(posq[k]),) if with_qual else ()))
             elif self.flags[p] & FLAG_CHANGED:
-                out.append((ix.names[c], pos, 'sub', chr(ref[k]), text[0], depth, int(cn["ACGT".index(text[0])])))
+                out.append((ix.names[c], pos, 'sub', chr(ref[k]), text[0], depth, int(cn["ACGT".index(text[0])]))
+                           + ((int(posq[k]),) if with_qual else ()))
             if self.flags[p] & FLAG_INSERTED:
-                out.append((ix.names[c], pos, 'ins', '', text[len(text) - nins:], int(cn[7]), int(cn[6])))
+                out.append((ix.names[c], pos, 'ins', '', text[len(text) - nins:], int(cn[7]), int(cn[6]))
+                           + ((int(letq[k, len(text) - nins:len(text)].min()),) if with_qual else ()))
         return out
 
     def summary(self):
@@ -583,9 +729,10 @@ def _deletion_wins(cn, ref):
 
 
 def pileup(index, res, strand, info, ops, region=None, max_ins=4, keep=None, normalise=True, min_depth=3,
-           memory_limit=transducer.WORKSPACE_LIMIT):
-    """The one-call form: Pileup(index, region, max_ins).add(res, strand, info, ops, keep, normalise) and its consensus.
-    -> (Pileup, Consensus)."""
-    p = Pileup(index, region=region, max_ins=max_ins, memory_limit=memory_limit)
-    p.add(res, strand, info, ops, keep=keep, normalise=normalise)
+           memory_limit=transducer.WORKSPACE_LIMIT, weighted=False, min_qual=0, qmax=60, weights=None, qual=None):
+    """The one-call form: Pileup(index, region, max_ins, ...).add(res, strand, info, ops, keep, normalise) and its consensus.
+    -> (Pileup, Consensus).  weighted, min_qual, qmax, weights: as Pileup takes them; qual: as Pileup.add."""
+    p = Pileup(index, region=region, max_ins=max_ins, memory_limit=memory_limit, weighted=weighted, min_qual=min_qual, qmax=qmax,
+               weights=weights)
+    p.add(res, strand, info, ops, keep=keep, normalise=normalise, qual=qual)
     return p, p.consensus(min_depth=min_depth)
