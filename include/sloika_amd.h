@@ -945,6 +945,41 @@ SLK_API int slk_forward_backward_batch_f64(const double *post, long ld, const in
                                            int full, double *score, double *occ, long occ_ld, int32_t *emit_row, double *emit_prob,
                                            void *workspace, size_t workspace_bytes, slk_stream_t stream);
 
+/* f10. The forward score of edited sequences (csrc/rescore_edits.hip, design/rescore_edits.md): per (posterior, sequence) pair any
+ * number of candidate edits "replace positions [start, start + ndel) by these new symbols", each scored as f6 would score the
+ * spelled-out sequence with full = 1, up to rounding, at the cost of nrow * (new symbols + 1) cells instead of nrow * npos.  One
+ * kernel stores the pair's forward and backward lattices, a second walks every candidate through them.  A candidate's result depends
+ * on its pair and on the candidate alone: not on the other candidates, their order, the batch, the layout or the launch.
+ *   post .. blank, min_prob: as for slk_forward_backward_batch_* (nstate <= 8192); full is implied, there is no free-end form.
+ *   cand_pair, cand_start, cand_ndel:[ncand] device int32: the pair, the first replaced position and how many are replaced.
+ *     Candidates come grouped by pair, pairs ascending (SLK_ERR_INVALID_ARG otherwise, or for a pair outside 0 .. nread - 1; nothing
+ *     is written); within a pair any order, ascending starts read the workspace best.  A pair may have no candidates; ncand may be 0.
+ *   cand_new_off:[ncand + 1] device int64, cand_new: int32 columns: candidate i inserts cand_new[cand_new_off[i] ..
+ *     cand_new_off[i + 1]), at most slk_rescore_edits_max_new() = SLK_RESCORE_MAX_NEW of them.  No new symbols: a deletion; ndel = 0:
+ *     an insertion.
+ *   score:[nread] float64: the pair's own full forward score (f6's value up to rounding; -inf with more positions than rows).
+ *   ll_edit:[ncand] float64, in the caller's candidate order; -inf when the edited sequence has more positions than the pair rows.
+ *   Refused with NaN, and nothing read out of bounds: a candidate with start < 0, ndel < 0, start + ndel > npos, more than
+ *     SLK_RESCORE_MAX_NEW new symbols or a new symbol that is no column (that candidate only); every candidate of a pair that was
+ *     itself refused (longer than max_npos, or a symbol that is no column: NaN score, nothing else written for the pair).
+ *   workspace: 16-byte aligned, slk_rescore_edits_workspace_bytes(nread, nrow, pos_off) bytes, computed from HOST copies of nrow and
+ *     pos_off: two offsets per pair, then 16 (nrow + 1) (ldj + 1) bytes per pair, ldj = npos + 1 rounded up to 2.  A smaller
+ *     workspace_bytes returns SLK_ERR_WORKSPACE and nothing is written.  The entry copies nrow, pos_off and cand_pair to the host, so
+ *     it synchronises with `stream` once. */
+#define SLK_RESCORE_MAX_NEW 8
+SLK_API int slk_rescore_edits_max_new(void);
+SLK_API size_t slk_rescore_edits_workspace_bytes(int nread, const int32_t *nrow, const int64_t *pos_off);
+SLK_API int slk_rescore_edits_batch_f32(const float *post, long ld, const int64_t *row_off, long row_step, const int32_t *nrow,
+                                        int nstate, const int32_t *seq, const int64_t *pos_off, int nread, int max_npos, int blank,
+                                        float min_prob, const int32_t *cand_pair, const int32_t *cand_start, const int32_t *cand_ndel,
+                                        const int64_t *cand_new_off, const int32_t *cand_new, int64_t ncand, double *score,
+                                        double *ll_edit, void *workspace, size_t workspace_bytes, slk_stream_t stream);
+SLK_API int slk_rescore_edits_batch_f64(const double *post, long ld, const int64_t *row_off, long row_step, const int32_t *nrow,
+                                        int nstate, const int32_t *seq, const int64_t *pos_off, int nread, int max_npos, int blank,
+                                        const int32_t *cand_pair, const int32_t *cand_start, const int32_t *cand_ndel,
+                                        const int64_t *cand_new_off, const int32_t *cand_new, int64_t ncand, double *score,
+                                        double *ll_edit, void *workspace, size_t workspace_bytes, slk_stream_t stream);
+
 /* f7. Where on a genome a call lies, and the reference of each read cut from it: the locating half of what misc/align.py gets from
  * `bwa mem -k14 -W20 -r10 ... genome.fa calls.fa` (align.py:46-67) and the cut of misc/get_refs_from_sam.py:40-68, on the device
  * (csrc/genome_map.hip, design/genome_map.md).  A seed-and-vote stage chooses, per query and strand, a band of diagonals; the

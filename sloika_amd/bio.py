@@ -252,3 +252,77 @@ def fastq_records(text):
             raise ValueError("fastq_records: record %d has a quality character outside '!' .. '~'" % (k + 1))
         out.append((head[1:], seq, q.astype(np.uint8)))
     return out
+
+
+#: the kinds of single_letter_edits, in the order in which a position lists them
+EDIT_KINDS = ('sub', 'del', 'ins')
+
+
+def single_letter_edits(seq, kinds=EDIT_KINDS, alphabet='ACGT'):
+    """Every single-letter edit of a base string: rows (kind, letter_pos, letter, edited_string), ordered by letter_pos, then kind
+    ('sub', 'del', 'ins'), then letter in alphabet order.  'sub' puts another letter at letter_pos, 'del' removes the letter there
+    (letter ''), 'ins' puts a letter in front of letter_pos (letter_pos = len(seq): behind the end): about 8 len(seq) rows."""
+    unknown = [k for k in kinds if k not in EDIT_KINDS]
+    if unknown:
+        raise ValueError("unknown kind of edit %r (known: %s)" % (unknown[0], ', '.join(EDIT_KINDS)))
+    rows = []
+    for pos in range(len(seq) + 1):
+        for kind in EDIT_KINDS:
+            if kind not in kinds:
+                continue
+            if kind == 'sub' and pos < len(seq):
+                rows.extend((kind, pos, c, seq[:pos] + c + seq[pos + 1:]) for c in alphabet if c != seq[pos])
+            elif kind == 'del' and pos < len(seq):
+                rows.append((kind, pos, '', seq[:pos] + seq[pos + 1:]))
+            elif kind == 'ins':
+                rows.extend((kind, pos, c, seq[:pos] + c + seq[pos:]) for c in alphabet)
+    return rows
+
+
+def apply_letter_edits(seq, edits):
+    """`seq` after the (kind, letter_pos, letter) edits of single_letter_edits, all of them positions of `seq` itself (applied from
+    the back, so that no edit moves another; at most one edit per position)."""
+    out = seq
+    for kind, pos, letter in sorted(edits, key=lambda e: -e[1]):
+        if kind == 'sub':
+            out = out[:pos] + letter + out[pos + 1:]
+        elif kind == 'del':
+            out = out[:pos] + out[pos + 1:]
+        elif kind == 'ins':
+            out = out[:pos] + letter + out[pos:]
+        else:
+            raise ValueError("unknown kind of edit %r" % (kind,))
+    return out
+
+
+def seq_to_states(seq, length, alphabet='ACGT'):
+    """The k-mer states of a base string (seq_to_kmers numbered by kmer_mapping) as int64, without building the k-mers."""
+    text = seq.encode('utf-8') if isinstance(seq, str) else bytes(seq)
+    rank = np.full(256, -1, dtype=np.int64)
+    rank[np.frombuffer(alphabet.encode('utf-8'), dtype=np.uint8)] = np.arange(len(alphabet))
+    digits = rank[np.frombuffer(text, dtype=np.uint8)]
+    if (digits < 0).any():
+        raise ValueError("letter outside the alphabet %r" % alphabet)
+    n = len(digits) - length + 1
+    if n <= 0:
+        return np.zeros(0, dtype=np.int64)
+    states = np.zeros(n, dtype=np.int64)
+    for j in range(length):
+        states = states * len(alphabet) + digits[j:j + n]
+    return states
+
+
+def edit_states(old_states, new_states):
+    """The edit that turns one state sequence into another: (start, ndel, new) with
+    new_states == old_states[:start] + new + old_states[start + ndel:], by stripping the common prefix, then the common suffix of
+    what is left.  A single-letter edit of a base string changes at most kmer_len consecutive k-mers and adds or removes one, so `new`
+    has at most kmer_len + 1 entries."""
+    old = np.asarray(old_states, dtype=np.int64).reshape(-1)
+    new = np.asarray(new_states, dtype=np.int64).reshape(-1)
+    n = min(len(old), len(new))
+    diff = np.nonzero(old[:n] != new[:n])[0]
+    pre = int(diff[0]) if diff.size else n
+    rest = n - pre
+    diff = np.nonzero(old[len(old) - rest:][::-1] != new[len(new) - rest:][::-1])[0] if rest else diff[:0]
+    suf = int(diff[0]) if diff.size else rest
+    return pre, len(old) - pre - suf, new[pre:len(new) - suf].copy()

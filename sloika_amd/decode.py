@@ -9,6 +9,8 @@
     forwards_batch(post[T,B,S] | rows + row_off, seqs)     batched extension    -> scores[B] float64, on the device
     forwards_backwards(post, seq, full=False)              the backward half    -> (score, occ, emit_row, emit_prob)
     forwards_backwards_batch(post | rows + row_off, seqs)  (csrc/forward_backward.hip, design/forward_backward.md)
+    rescore_edits_batch(post | rows + row_off, seqs, edits) the full forward score of every EDITED sequence from one stored pair of
+                                                           lattices (csrc/rescore_edits.hip, design/rescore_edits.md; polish.py)
     viterbi_marginals_batch(post[T,B,S], klen, ...)        the decoder's sum-product twin: state marginals, log Z, a confidence per
                                                            called position (csrc/lattice_marginals.hip, design/lattice_marginals.md)
 
@@ -527,6 +529,147 @@ def forwards_backwards_batch(post, seqs, lengths=None, full=False, blank=-1, min
     else:
         emit_row = emit_prob = None
     return score, occ, emit_row, emit_prob
+
+
+def rescore_max_new():
+    """The most new symbols one edit of rescore_edits_batch may insert (slk_rescore_edits_max_new)."""
+    return int(_lib.lib().slk_rescore_edits_max_new())
+
+
+class EditSet(object):
+    """Candidate edits of one sequence in the layout the kernel reads: start, ndel int32 [n]; new_off int64 [n + 1]; new int32
+    [new_off[-1]] -- edit i replaces positions start[i] .. start[i] + ndel[i] - 1 by new[new_off[i]:new_off[i + 1]].  Built once
+    (from_list) and handed to rescore_edits_batch for every pair that carries the same sequence."""
+
+    def __init__(self, start, ndel, new_off, new):
+        self.start = np.ascontiguousarray(start, dtype=np.int32).reshape(-1)
+        self.ndel = np.ascontiguousarray(ndel, dtype=np.int32).reshape(-1)
+        self.new_off = np.ascontiguousarray(new_off, dtype=np.int64).reshape(-1)
+        self.new = np.ascontiguousarray(new, dtype=np.int32).reshape(-1)
+        if len(self.ndel) != len(self.start) or len(self.new_off) != len(self.start) + 1 or self.new_off[0] != 0 or \
+                self.new_off[-1] != len(self.new) or (np.diff(self.new_off) < 0).any():
+            raise ValueError("an EditSet needs one start, one ndel and one range of new symbols per edit")
+
+    def __len__(self):
+        return len(self.start)
+
+    @classmethod
+    def from_list(cls, edits):
+        """From (start, ndel, new_symbols) rows."""
+        news = [np.asarray(e[2], dtype=np.int64).reshape(-1) for e in edits]
+        off = np.concatenate([[0], np.cumsum([len(v) for v in news])]).astype(np.int64)
+        new = np.concatenate(news) if len(news) and off[-1] else np.zeros(0, dtype=np.int64)
+        if new.size and (new.min() < -2 ** 31 or new.max() >= 2 ** 31):
+            raise ValueError("new symbols must be columns of the posterior")
+        return cls([int(e[0]) for e in edits], [int(e[1]) for e in edits], off, new)
+
+
+def rescore_edits_batch(post, seqs, edits, lengths=None, blank=-1, min_prob=None, row_off=None, workspace_limit=None):
+    """The full forward score of EDITED sequences (csrc/rescore_edits.hip, design/rescore_edits.md): for every pair and every
+    candidate edit of its sequence, what forwards_batch(full=True) gives for the spelled-out edited sequence, up to rounding, at the
+    cost of rows x (new symbols + 1) cells per candidate instead of rows x positions.
+
+    post, seqs, lengths, blank, min_prob, row_off: as in forwards_batch; at most FORWARD_BACKWARD_MAX_STATES columns.
+    edits: per pair a list of (start, ndel, new_symbols) -- replace positions start .. start + ndel - 1 of the pair's sequence by the
+    columns new_symbols (none: a deletion; ndel = 0: an insertion in front of `start`) -- or an EditSet.  A pair may have none.
+    ValueError for more than rescore_max_new() new symbols, an edit outside its sequence and a new symbol that is no column.
+
+    -> (score, ll_edit): score device float64 [B], each pair's own full forward score; ll_edit a list of B device float64 views, one
+    value per candidate in the caller's order (-inf when the edited sequence has more positions than the pair has rows).  A
+    candidate's value depends on the pair and the candidate alone.
+    The lattices of a launch live in a workspace of 16 (rows + 1) (positions + 3) bytes per pair at the most; the batch runs as
+    consecutive launches whose workspace stays within `workspace_limit` bytes (default transducer.WORKSPACE_LIMIT; no bit depends
+    on the split).  A pair that needs more on its own raises ValueError."""
+    import ctypes
+    import types
+    import torch
+    from . import device as D
+    from . import transducer
+    who = "rescore_edits_batch"
+    q = _forward_pairs(post, seqs, lengths, blank, min_prob, row_off, who)
+    pd, B, S = q.pd, q.B, q.S
+    if S > FORWARD_BACKWARD_MAX_STATES:
+        raise ValueError("a posterior of %d states is above %s's limit of %d" % (S, who, FORWARD_BACKWARD_MAX_STATES))
+    if len(edits) != B:
+        raise ValueError("%s needs one list of edits per pair (%d for %d)" % (who, len(edits), B))
+    sets = [e if isinstance(e, EditSet) else EditSet.from_list(e) for e in edits]
+    L = _lib.lib()
+    most = rescore_max_new()
+    for b, e in enumerate(sets):
+        if not len(e):
+            continue
+        if int(np.diff(e.new_off).max()) > most:
+            raise ValueError("an edit of pair %d inserts more than %d new symbols" % (b, most))
+        if e.start.min() < 0 or e.ndel.min() < 0 or int((e.start.astype(np.int64) + e.ndel).max()) > q.npos[b]:
+            raise ValueError("an edit of pair %d lies outside its sequence of %d positions" % (b, q.npos[b]))
+        if e.new.size and (e.new.min() < 0 or e.new.max() >= S):
+            raise ValueError("new symbols must be columns 0 .. %d of the posterior" % (S - 1))
+    limit = transducer.WORKSPACE_LIMIT if workspace_limit is None else int(workspace_limit)
+    lens = (q.lens if q.lens is not None else q.lens_dev.cpu().numpy()).astype(np.int32)
+
+    def need(lo, hi):
+        nrow = np.ascontiguousarray(lens[lo:hi])
+        pos = np.ascontiguousarray(q.pos_off[lo:hi + 1])
+        return int(L.slk_rescore_edits_workspace_bytes(hi - lo, nrow.ctypes.data_as(ctypes.c_void_p), pos.ctypes.data_as(ctypes.c_void_p)))
+
+    # a pair adds its lattices and 16 bytes of offsets to a launch's workspace; the offsets of n pairs take less than 16 n + 512 bytes
+    # (alone, a pair's take 256)
+    alone = [need(b, b + 1) for b in range(B)]
+    if max(alone) > limit:
+        b = int(np.argmax(alone))
+        raise ValueError("pair %d needs %d bytes of workspace, above the workspace_limit of %d" % (b, alone[b], limit))
+    runs = transducer.workspace_runs([n - 256 + 16 for n in alone], max(limit - 512, 0))
+
+    # the candidates of the whole batch, sorted by (pair, start) for the launch; `order` takes them back
+    count = np.array([len(e) for e in sets], dtype=np.int64)
+    coff = np.concatenate([[0], np.cumsum(count)]).astype(np.int64)
+    ncand = int(coff[-1])
+    dev = pd.device
+    score = D.scratch(B, torch.float64, dev, result=True)
+    ll = torch.empty(max(ncand, 1), dtype=torch.float64, device=dev)
+    cand = None
+    if ncand:
+        pair = np.repeat(np.arange(B, dtype=np.int64), count)
+        start = np.concatenate([e.start for e in sets]).astype(np.int64)
+        ndel = np.concatenate([e.ndel for e in sets])
+        nnew = np.concatenate([np.diff(e.new_off) for e in sets])
+        new = np.concatenate([e.new for e in sets])
+        first = np.concatenate([e.new_off[:-1] + o for e, o in zip(sets, np.concatenate([[0], np.cumsum([len(e.new) for e in sets])]))])
+        order = np.argsort(pair * (int(start.max()) + 1) + start, kind="stable")
+        run_lo = np.zeros(B, dtype=np.int64)
+        for lo, hi in runs:
+            run_lo[lo:hi] = lo
+        # the sorted candidates' new symbols, gathered into their new order
+        s_nnew = nnew[order]
+        s_off = np.concatenate([[0], np.cumsum(s_nnew)]).astype(np.int64)
+        take = np.repeat(first[order] - s_off[:-1], s_nnew) + np.arange(int(s_off[-1]), dtype=np.int64)
+        ints = np.concatenate([(pair - run_lo[pair])[order], start[order], ndel[order], new[take]]).astype(np.int32)
+        cand = types.SimpleNamespace(ints=torch.as_tensor(ints if ints.size else np.zeros(1, np.int32)).to(dev), off=torch.as_tensor(s_off).to(dev),
+                        order=torch.as_tensor(order).to(dev))
+    ws = torch.empty(max(need(lo, hi) for lo, hi in runs), dtype=torch.uint8, device=dev)
+    rows = float(ncand) * (float(q.nrows) if not q.packed else float(np.mean(lens)))
+    with profiler.region("rescore_edits", 20.0 * rows, 16.0 * rows):
+        for lo, hi in runs:
+            c0, c1 = int(coff[lo]), int(coff[hi])
+            head = (pd.data_ptr(), q.ld, q.offs.data_ptr() + 8 * lo, q.step, q.nrow_ptr + 4 * lo, S, q.ints.data_ptr(),
+                    q.offs.data_ptr() + 8 * (B + lo), hi - lo, max(q.npos[lo:hi]), q.blank)
+            if c1 > c0:
+                ip = cand.ints.data_ptr()
+                cands = (ip + 4 * c0, ip + 4 * (ncand + c0), ip + 4 * (2 * ncand + c0), cand.off.data_ptr() + 8 * c0, ip + 4 * 3 * ncand,
+                         c1 - c0)
+            else:
+                cands = (None, None, None, None, None, 0)
+            tail = (score.data_ptr() + 8 * lo, ll.data_ptr() + 8 * c0, ws.data_ptr(), need(lo, hi), D.stream_ptr())
+            if pd.dtype == torch.float32:
+                rc = L.slk_rescore_edits_batch_f32(*head, float(min_prob or 0.0), *cands, *tail)
+            else:
+                rc = L.slk_rescore_edits_batch_f64(*head, *cands, *tail)
+            _lib.check(rc, "decode.rescore_edits_batch")
+    if ncand:
+        back = torch.empty_like(ll)
+        back[cand.order] = ll                                  # (a permutation: every slot is written once)
+        ll = back
+    return score, [ll[coff[b]:coff[b + 1]] for b in range(B)]
 
 
 def forwards_backwards(post, seq, full=False):

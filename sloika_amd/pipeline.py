@@ -401,6 +401,40 @@ class Basecaller(object):
             post = self.posteriors(chunks, scaling)
             return decode.forwards_backwards_batch(post, cols, full=full, blank=0, min_prob=self.min_prob)
 
+    def _polish_check(self, chunks, drafts, who):
+        if not self.transducer:
+            raise NotImplementedError("%s needs a transducer model: without a blank state there is no forward score" % who)
+        if self.nbase != 4:
+            raise ValueError("%s reads drafts in the alphabet ACGT (nbase=%d)" % (who, self.nbase))
+        if len(drafts) != len(chunks):
+            raise ValueError("%s needs one draft per chunk (%d for %d)" % (who, len(drafts), len(chunks)))
+
+    def rescore_chunks(self, chunks, drafts, group=None, kinds=('sub', 'del', 'ins'), scaling=None):
+        """What would the signal gain from each single-letter edit of a draft: polish.rescore_drafts on the prepared posterior of
+        score_chunks (posteriors(), blank 0, columns state + 1, min_prob as in call_chunks; csrc/rescore_edits.hip,
+        design/rescore_edits.md).
+
+        drafts: one base string per chunk; group[b] names the draft chunk b is a read of (the chunks of one group carry the same
+        string; None: every chunk is its own group).  The edits are enumerated once per group (bio.single_letter_edits).
+        -> per group, in the order of its first chunk, a polish.Rescored: `edits` the rows (kind, letter_pos, letter, edited_string),
+        `gain` device float64 [len(edits)]: the sum over the group's chunks of (log-likelihood of the edited string - that of the
+        draft), `score` the summed log-likelihood of the draft."""
+        from . import polish
+        self._polish_check(chunks, drafts, "rescore_chunks")
+        with self._scope():
+            post = self.posteriors(chunks, scaling)
+            return polish.rescore_drafts(post, drafts, self.kmer_len, group=group, kinds=kinds, blank=0, min_prob=self.min_prob)
+
+    def polish_chunks(self, chunks, drafts, group=None, min_gain=0.0, max_rounds=8, kinds=('sub', 'del', 'ins'), scaling=None):
+        """polish.polish on the prepared posterior of the chunks (one network pass, then rounds of rescore_chunks' scoring): per group a
+        polish.Polished with the polished string, the applied edits with their gains, the rounds and the final summed score."""
+        from . import polish
+        self._polish_check(chunks, drafts, "polish_chunks")
+        with self._scope():
+            post = self.posteriors(chunks, scaling)
+            return polish.polish(post, drafts, self.kmer_len, group=group, min_gain=min_gain, max_rounds=max_rounds, kinds=kinds,
+                                 blank=0, min_prob=self.min_prob)
+
     def _sequence_columns(self, chunks, sequences, who, what):
         """The posterior columns of one sequence per chunk, each k-mer states or a base string (score_chunks): state + 1, column 0 is
         the blank (variables.nstate, transducer=True)."""
