@@ -21,7 +21,7 @@
 // posterior is staged into LDS once per workgroup (two buffers on the row's parity, one barrier per row, 16-byte loads issued one row
 // ahead into registers), each lane gathers its m + 1 emissions and p[seq[a+d]] from LDS and reads F_t[a], B_{t+1}[a+d+1] from the
 // workspace one row ahead.  g lives in registers, unrolled to SLK_RESCORE_MAX_NEW: a lane's chain takes the last m + 1 slots,
-// the slots in front of it hold zeros.  g is rescaled with its row's EF_t - EF_{t-1}; the terms of the cut sum carry the exponent EF_t + EB_{t+1} (the same for the
+// the slots in front of it hold zeros.  g is rescaled with its row's EF_t - EF_{t-1}; the terms of the cut sum carry the exponent EF_{t+1} + EB_t (the same for the
 // whole workgroup) and are added in ascending t as (mantissa, integer exponent).  One log per candidate.  Nothing a lane computes
 // depends on another lane, on the workgroup it sits in or on the launch.
 #include <cstdlib>
@@ -396,7 +396,7 @@ __global__ void __launch_bounds__(RE_CAND) rescore_cand_kernel(re_args A, int gr
     }
     double fnext = (ok && nr >= 1) ? Fa[(size_t)v.ldj] : 0.0;
     double bnext = (cut && nr >= 1) ? Bd[(size_t)v.ldj] : 0.0;
-    int64_t ef = 0, efn = nr >= 1 ? v.EF[1] : 0, ebn = nr >= 1 ? v.EB[1] : 0;
+    int64_t ef = 0, efn = nr >= 1 ? v.EF[1] : 0, ebc = v.EB[0], ebn = nr >= 1 ? v.EB[1] : 0;
     double acc = 0.0;
     int64_t acce = 0;
     if constexpr (STAGED) __syncthreads();
@@ -436,10 +436,12 @@ __global__ void __launch_bounds__(RE_CAND) rescore_cand_kernel(re_args A, int gr
         double pc[M];
 #pragma unroll
         for (int i = 0; i < M; i++) pc[i] = sym[i] >= 0 ? fs_widen(vc[i], raw, a.min_prob, a.one_m) : 0.0;
-        // the cut term of t: paths that leave state a + m with row t + 1; exponent EF_t + EB_{t+1}
+        // the cut term of t: paths that leave state a + m with row t + 1.  g carries the scale of row t of F, 2^(EF_{t+1} - EF_t) times
+        // a value below 1, B_{t+1} that of its own row, 2^(EB_t - EB_{t+1}): the product of both and of the emission leaves the normal
+        // range when neighbouring rows differ in scale, so B_{t+1} gives both scales up first (exact) and the exponent is EF_{t+1} + EB_t
         {
-            const double term = (g[M] * pn) * bnext;
-            const int64_t e = ef + ebn;
+            const double term = (g[M] * pn) * ldexp(bnext, re_clamp_shift((ef - efn) + (ebn - ebc)));
+            const int64_t e = efn + ebc;
             if (t == 0 || e > acce) {
                 acc = ldexp(acc, re_clamp_shift(acce - e)) + term;
                 acce = e;
@@ -454,6 +456,7 @@ __global__ void __launch_bounds__(RE_CAND) rescore_cand_kernel(re_args A, int gr
         bnext = b2;
         ef = efn;
         efn = ef2;
+        ebc = ebn;
         ebn = eb2;
         if constexpr (STAGED) {
             if (t + 1 < nr) st.store(re_rows + (size_t)((t + 1) & 1) * gran, rnext, a.nstate);
