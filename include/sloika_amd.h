@@ -980,6 +980,37 @@ SLK_API int slk_rescore_edits_batch_f64(const double *post, long ld, const int64
                                         const int64_t *cand_new_off, const int32_t *cand_new, int64_t ncand, double *score,
                                         double *ll_edit, void *workspace, size_t workspace_bytes, slk_stream_t stream);
 
+/* f10b. f10 for whole reads: banded lattices (csrc/rescore_band.hip, design/rescore_band.md).  A pair keeps `width` states per row
+ * instead of all npos + 1: state j exists in row t when band_lo[t] <= j < band_lo[t] + width (and 0 <= j <= npos), every other state
+ * counts as 0.  score and ll_edit are then the log-likelihoods summed over the alignments that stay inside the band: never above
+ * f10's, and f10's bits when band_lo is all 0 and width > npos.  There is no max_npos: the width chooses the kernel and npos is any
+ * int32 up to 2^31 - 16387 (SLK_ERR_UNSUPPORTED above).  Arguments as f10, and
+ *   band_lo: device int32, band_off:[nread + 1] device int64: pair b's nrow[b] + 1 entries (one per row index 0 .. nrow[b]) start at
+ *     band_off[b].  A valid band has band_lo[0] = 0, no negative entry, does not decrease and ends with band_lo[nrow] + width > npos.
+ *     A step may be of any size; one above `width` loses all mass (-inf).
+ *   width: 256, 512, 1024 or 2048 (up to slk_rescore_band_max_width()).
+ *   SLK_ERR_INVALID_ARG, nothing written: a width that is not built, band_off[b + 1] - band_off[b] != nrow[b] + 1, candidates not
+ *     grouped by pair.  NaN per candidate or per pair exactly as f10, and a NaN pair for an invalid band.
+ *   An edit's ll_edit is -inf when its column `start` exists in no row of the band, or in none before the last row of column
+ *     start + ndel + 1.
+ *   workspace: 16-byte aligned, slk_rescore_edits_banded_workspace_bytes(nread, nrow, width) bytes from a HOST copy of nrow: f10's
+ *     head, then 16 (nrow + 1) (width + 1) bytes per pair; SLK_ERR_WORKSPACE for less.  The entry copies nrow, pos_off, band_off and
+ *     cand_pair to the host, so it synchronises with `stream` once. */
+SLK_API int slk_rescore_band_max_width(void);
+SLK_API size_t slk_rescore_edits_banded_workspace_bytes(int nread, const int32_t *nrow, int width);
+SLK_API int slk_rescore_edits_banded_batch_f32(const float *post, long ld, const int64_t *row_off, long row_step, const int32_t *nrow,
+                                               int nstate, const int32_t *seq, const int64_t *pos_off, int nread, int blank,
+                                               float min_prob, const int32_t *band_lo, const int64_t *band_off, int width,
+                                               const int32_t *cand_pair, const int32_t *cand_start, const int32_t *cand_ndel,
+                                               const int64_t *cand_new_off, const int32_t *cand_new, int64_t ncand, double *score,
+                                               double *ll_edit, void *workspace, size_t workspace_bytes, slk_stream_t stream);
+SLK_API int slk_rescore_edits_banded_batch_f64(const double *post, long ld, const int64_t *row_off, long row_step, const int32_t *nrow,
+                                               int nstate, const int32_t *seq, const int64_t *pos_off, int nread, int blank,
+                                               const int32_t *band_lo, const int64_t *band_off, int width, const int32_t *cand_pair,
+                                               const int32_t *cand_start, const int32_t *cand_ndel, const int64_t *cand_new_off,
+                                               const int32_t *cand_new, int64_t ncand, double *score, double *ll_edit,
+                                               void *workspace, size_t workspace_bytes, slk_stream_t stream);
+
 /* f7. Where on a genome a call lies, and the reference of each read cut from it: the locating half of what misc/align.py gets from
  * `bwa mem -k14 -W20 -r10 ... genome.fa calls.fa` (align.py:46-67) and the cut of misc/get_refs_from_sam.py:40-68, on the device
  * (csrc/genome_map.hip, design/genome_map.md).  A seed-and-vote stage chooses, per query and strand, a band of diagonals; the

@@ -172,6 +172,12 @@ PROTOTYPES = {
                                          _vp, _vp, _sz, _vp]),
     "slk_rescore_edits_batch_f64": (_i, [_vp, _l, _vp, _l, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp,
                                          _vp, _sz, _vp]),
+    "slk_rescore_band_max_width": (_i, []),
+    "slk_rescore_edits_banded_workspace_bytes": (_sz, [_i, _vp, _i]),
+    "slk_rescore_edits_banded_batch_f32": (_i, [_vp, _l, _vp, _l, _vp, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                                C.c_int64, _vp, _vp, _vp, _sz, _vp]),
+    "slk_rescore_edits_banded_batch_f64": (_i, [_vp, _l, _vp, _l, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                                C.c_int64, _vp, _vp, _vp, _sz, _vp]),
     "slk_genome_kmer_keys_u8": (_i, [_vp, _vp, _i, _l, _i, _vp, _vp, _vp]),
     "slk_genome_seed_workspace_bytes": (_sz, [_i, _i, _l, _i]),
     "slk_genome_seed_votes_u8": (_i, [_vp, _l, _vp, _i, _i, _vp, _i, _l, _i, _i, _i, _vp, _vp, _sz, _vp]),

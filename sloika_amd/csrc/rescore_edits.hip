@@ -27,11 +27,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "forward_row.h"
-
-#define RE_MAX_STATES 8192
-#define RE_CAND 256                                           // candidates per workgroup
-#define RE_NAN __longlong_as_double(0x7ff8000000000000LL)
+#include "rescore_common.h"
 
 struct re_args {
     fs_args f;                                                // (full = 1; score_out = the pairs' scores)
@@ -62,8 +58,6 @@ __device__ __forceinline__ re_view re_pair_view(double *base, int L, int nr)
     v.EB = v.EF + (nr + 1);
     return v;
 }
-
-__device__ __forceinline__ double re_sum4(const double *w) { return ((w[0] + w[1]) + w[2]) + w[3]; }
 
 // the states j0 .. j0 + PPT - 1 of one row; columns past ldj do not exist (ldj is even, so a pair of columns is whole or absent)
 template <int PPT>
@@ -268,50 +262,6 @@ __global__ void __launch_bounds__(FS_THREADS) rescore_lattice_kernel(re_args A)
 
 // ---- the candidates ------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ int re_clamp_shift(int64_t s) { return (int)(s < -4096 ? -4096 : (s > 4096 ? 4096 : s)); }
-
-// One posterior row on its way into LDS: the row's bytes in 16-byte granules of its own alignment, granule tid + 256 k in r[k].  A
-// granule that lies wholly inside the row is one 16-byte load; the row's first and last granule are read value by value, so that
-// nothing outside the row is touched.  In LDS value c of the row sits at index c + mis (mis: the row's first value inside its granule).
-template <typename T, int NCH>
-struct re_stage {
-    static constexpr int PER = 16 / sizeof(T);
-    uint4 r[NCH];
-    __device__ __forceinline__ static int mis(const T *row) { return (int)((reinterpret_cast<uintptr_t>(row) & 15) / sizeof(T)); }
-    __device__ __forceinline__ void load(const T *row, int nstate)
-    {
-        const int ms = mis(row);
-        const T *g0 = row - ms;                               // (16-byte aligned; only values inside the row are read)
-        const int ngran = (ms + nstate + PER - 1) / PER;
-#pragma unroll
-        for (int k = 0; k < NCH; k++) {
-            const int q = threadIdx.x + FS_THREADS * k;
-            if (q >= ngran) continue;
-            const int lo = q * PER - ms;                      // the row's value at the granule's first slot
-            if (lo >= 0 && lo + PER <= nstate) r[k] = *reinterpret_cast<const uint4 *>(g0 + (size_t)q * PER);
-            else {
-                auto at = [&](int i) { return (lo + i >= 0 && lo + i < nstate) ? row[lo + i] : (T)0; };
-                if constexpr (PER == 4)
-                    r[k] = make_uint4(__float_as_uint(at(0)), __float_as_uint(at(1)), __float_as_uint(at(2)), __float_as_uint(at(3)));
-                else {
-                    const double x = at(0), y = at(1);
-                    r[k] = make_uint4((unsigned)__double2loint(x), (unsigned)__double2hiint(x), (unsigned)__double2loint(y),
-                                      (unsigned)__double2hiint(y));
-                }
-            }
-        }
-    }
-    __device__ __forceinline__ void store(uint4 *buf, const T *row, int nstate) const
-    {
-        const int ngran = (mis(row) + nstate + PER - 1) / PER;
-#pragma unroll
-        for (int k = 0; k < NCH; k++) {
-            const int q = threadIdx.x + FS_THREADS * k;
-            if (q < ngran) buf[q] = r[k];
-        }
-    }
-};
-
 // STAGED = false (the diagnostic build only, design/rescore_edits.md 7): no LDS and no barrier, every lane gathers its emissions of
 // the next row from global memory into registers instead.  The same arithmetic on the same values: the same bits.
 template <typename T, int NCH, bool STAGED>
@@ -468,9 +418,6 @@ __global__ void __launch_bounds__(RE_CAND) rescore_cand_kernel(re_args A, int gr
         else A.ll[ci] = log(g[M]) + (double)ef * FS_LN2;     // a + d = L: Z' = g_T[m]
     }
 }
-
-static inline size_t re_round256(size_t n) { return (n + 255) & ~(size_t)255; }
-static inline size_t re_head_bytes(int nread) { return re_round256(2 * (size_t)(nread + 1) * sizeof(int64_t)); }
 
 // doubles of workspace of one pair (host values): nothing for a pair the device refuses by its lengths
 static inline size_t re_pair_doubles(int64_t np, int nr)

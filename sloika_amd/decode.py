@@ -342,8 +342,9 @@ def _forward_post(post):
     return torch.from_numpy(np.ascontiguousarray(a)).to(D.device())
 
 
-def _forward_pairs(post, seqs, lengths, blank, min_prob, row_off, who):
-    """The arguments of forwards_batch / forwards_backwards_batch, checked, laid out as the kernels read them and uploaded."""
+def _forward_pairs(post, seqs, lengths, blank, min_prob, row_off, who, most=None):
+    """The arguments of forwards_batch / forwards_backwards_batch, checked, laid out as the kernels read them and uploaded.
+    most: the longest sequence `who` takes (the forward score's limit when None)."""
     import types
     import torch
     shape = tuple(post.shape)
@@ -375,8 +376,10 @@ def _forward_pairs(post, seqs, lengths, blank, min_prob, row_off, who):
         raise ValueError("blank column %d outside the %d states" % (blank, S))
     seqs = [np.asarray(q).reshape(-1) for q in seqs]
     npos = [len(q) for q in seqs]
-    limit = forward_max_positions()
+    limit = forward_max_positions() if most is None else most
     if max(npos) > limit:
+        if most is not None:
+            raise ValueError("a sequence of %d positions is above %s's limit of %d" % (max(npos), who, limit))
         raise ValueError("a sequence of %d positions is above the forward score's limit of %d" % (max(npos), limit))
     cat = np.concatenate(seqs).astype(np.int64) if sum(npos) else np.zeros(0, dtype=np.int64)
     if cat.size and (cat.min() < 0 or cat.max() >= S):
@@ -580,13 +583,18 @@ def rescore_edits_batch(post, seqs, edits, lengths=None, blank=-1, min_prob=None
     The lattices of a launch live in a workspace of 16 (rows + 1) (positions + 3) bytes per pair at the most; the batch runs as
     consecutive launches whose workspace stays within `workspace_limit` bytes (default transducer.WORKSPACE_LIMIT; no bit depends
     on the split).  A pair that needs more on its own raises ValueError."""
+    return _rescore_edits("rescore_edits_batch", post, seqs, edits, lengths, blank, min_prob, row_off, workspace_limit, None)
+
+
+def _rescore_edits(who, post, seqs, edits, lengths, blank, min_prob, row_off, workspace_limit, band):
+    """rescore_edits_batch (band None) and rescore_edits_banded_batch (band = (lo per pair, width)): one preparation of the pairs and
+    the candidates, one loop over the launches; only the workspace and the entry differ."""
     import ctypes
     import types
     import torch
     from . import device as D
     from . import transducer
-    who = "rescore_edits_batch"
-    q = _forward_pairs(post, seqs, lengths, blank, min_prob, row_off, who)
+    q = _forward_pairs(post, seqs, lengths, blank, min_prob, row_off, who, None if band is None else BAND_MAX_POSITIONS)
     pd, B, S = q.pd, q.B, q.S
     if S > FORWARD_BACKWARD_MAX_STATES:
         raise ValueError("a posterior of %d states is above %s's limit of %d" % (S, who, FORWARD_BACKWARD_MAX_STATES))
@@ -607,8 +615,39 @@ def rescore_edits_batch(post, seqs, edits, lengths=None, blank=-1, min_prob=None
     limit = transducer.WORKSPACE_LIMIT if workspace_limit is None else int(workspace_limit)
     lens = (q.lens if q.lens is not None else q.lens_dev.cpu().numpy()).astype(np.int32)
 
+    if band is not None:
+        width = int(band[1])
+        if width not in band_widths():
+            raise ValueError("a band of %d states is not built: %s" % (width, ", ".join(str(w) for w in band_widths())))
+        if len(band[0]) != B:
+            raise ValueError("%s needs one band per pair (%d for %d)" % (who, len(band[0]), B))
+        # the bands stay where they are (band_lo makes them on the device); they are checked there, one flag per pair coming back
+        los = [(v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v, dtype=np.int64))).to(pd.device).to(torch.int64).reshape(-1)
+               for v in band[0]]
+        for b, v in enumerate(los):
+            if v.numel() != int(lens[b]) + 1:
+                raise ValueError("pair %d: a band needs one entry per row index 0 .. %d, not %d" % (b, int(lens[b]), v.numel()))
+        boff = np.concatenate([[0], np.cumsum(lens.astype(np.int64) + 1)]).astype(np.int64)
+        cat = torch.cat(los)
+        boff_dev = torch.as_tensor(boff).to(pd.device)
+        first, last = boff_dev[:-1], boff_dev[1:] - 1
+        falls = torch.zeros(cat.numel(), dtype=torch.int64, device=pd.device)
+        falls[1:] = (cat[1:] < cat[:-1]).to(torch.int64)
+        falls[first] = 0                                          # (a pair's first entry has no entry before it)
+        per_pair = torch.zeros(B, dtype=torch.int64, device=pd.device).index_add_(
+            0, torch.repeat_interleave(torch.arange(B, device=pd.device), last - first + 1), falls + ((cat < 0) | (cat >= 2 ** 31)))
+        npos_dev = torch.as_tensor(np.asarray(q.npos, dtype=np.int64)).to(pd.device)
+        bad = ((cat[first] != 0) | (per_pair > 0) | (cat[last] + width <= npos_dev)).nonzero().reshape(-1).cpu().numpy()
+        if len(bad):
+            b = int(bad[0])                                       # (the pair's own values say which rule it breaks)
+            _check_band(los[b].cpu().numpy(), int(lens[b]), q.npos[b], width, "pair %d" % b)
+            raise ValueError("pair %d: no valid band" % b)
+        band_dev = cat.to(torch.int32)
+
     def need(lo, hi):
         nrow = np.ascontiguousarray(lens[lo:hi])
+        if band is not None:
+            return int(L.slk_rescore_edits_banded_workspace_bytes(hi - lo, nrow.ctypes.data_as(ctypes.c_void_p), width))
         pos = np.ascontiguousarray(q.pos_off[lo:hi + 1])
         return int(L.slk_rescore_edits_workspace_bytes(hi - lo, nrow.ctypes.data_as(ctypes.c_void_p), pos.ctypes.data_as(ctypes.c_void_p)))
 
@@ -652,7 +691,7 @@ def rescore_edits_batch(post, seqs, edits, lengths=None, blank=-1, min_prob=None
         for lo, hi in runs:
             c0, c1 = int(coff[lo]), int(coff[hi])
             head = (pd.data_ptr(), q.ld, q.offs.data_ptr() + 8 * lo, q.step, q.nrow_ptr + 4 * lo, S, q.ints.data_ptr(),
-                    q.offs.data_ptr() + 8 * (B + lo), hi - lo, max(q.npos[lo:hi]), q.blank)
+                    q.offs.data_ptr() + 8 * (B + lo), hi - lo) + ((max(q.npos[lo:hi]),) if band is None else ()) + (q.blank,)
             if c1 > c0:
                 ip = cand.ints.data_ptr()
                 cands = (ip + 4 * c0, ip + 4 * (ncand + c0), ip + 4 * (2 * ncand + c0), cand.off.data_ptr() + 8 * c0, ip + 4 * 3 * ncand,
@@ -660,16 +699,126 @@ def rescore_edits_batch(post, seqs, edits, lengths=None, blank=-1, min_prob=None
             else:
                 cands = (None, None, None, None, None, 0)
             tail = (score.data_ptr() + 8 * lo, ll.data_ptr() + 8 * c0, ws.data_ptr(), need(lo, hi), D.stream_ptr())
-            if pd.dtype == torch.float32:
+            if band is not None:
+                strip = (band_dev.data_ptr(), boff_dev.data_ptr() + 8 * lo, width)      # (offsets into the whole batch's lo)
+                if pd.dtype == torch.float32:
+                    rc = L.slk_rescore_edits_banded_batch_f32(*head, float(min_prob or 0.0), *strip, *cands, *tail)
+                else:
+                    rc = L.slk_rescore_edits_banded_batch_f64(*head, *strip, *cands, *tail)
+            elif pd.dtype == torch.float32:
                 rc = L.slk_rescore_edits_batch_f32(*head, float(min_prob or 0.0), *cands, *tail)
             else:
                 rc = L.slk_rescore_edits_batch_f64(*head, *cands, *tail)
-            _lib.check(rc, "decode.rescore_edits_batch")
+            _lib.check(rc, "decode." + who)
     if ncand:
         back = torch.empty_like(ll)
         back[cand.order] = ll                                  # (a permutation: every slot is written once)
         ll = back
     return score, [ll[coff[b]:coff[b + 1]] for b in range(B)]
+
+
+#: the longest sequence the banded kernels take (csrc/rescore_band.hip: state arithmetic in int32)
+BAND_MAX_POSITIONS = 2 ** 31 - 1 - 2 * 8192 - 2
+
+
+def band_widths():
+    """The band widths rescore_edits_banded_batch is built for: 256 states per state of a thread, up to slk_rescore_band_max_width."""
+    top = int(_lib.lib().slk_rescore_band_max_width())
+    return tuple(w for w in (256, 512, 1024, 2048, 4096, 8192) if w <= top)
+
+
+def _check_band(lo, nrow, npos, width, what):
+    """ValueError unless lo [nrow + 1] is a valid band of `width` states for `npos` positions (design/rescore_band.md 1)."""
+    if len(lo) != nrow + 1:
+        raise ValueError("%s: a band needs one entry per row index 0 .. %d, not %d" % (what, nrow, len(lo)))
+    if lo[0] != 0 or lo.min() < 0:
+        raise ValueError("%s: a band begins at state 0 and has no negative entry" % what)
+    if len(lo) > 1 and (np.diff(lo) < 0).any():
+        raise ValueError("%s: a band does not decrease" % what)
+    if int(lo[-1]) + width <= npos:
+        raise ValueError("%s: the band's last row ends at state %d, below the last of %d" % (what, int(lo[-1]) + width - 1, npos))
+
+
+def band_lo(center, npos, width):
+    """The band of `width` states whose rows are centred on `center` (one state per row index 0 .. T, any integer tensor or array):
+    clamp(center - width // 2, 0, max(0, npos + 1 - width)), then a running maximum, on the device.  -> int32 device tensor
+    [T + 1].  ValueError when that is no valid band (the centre does not begin at the sequence's start or end at its end)."""
+    import torch
+    from . import device as D
+    c = center if isinstance(center, torch.Tensor) else torch.as_tensor(np.asarray(center, dtype=np.int64))
+    c = c.to(D.device()).to(torch.int64).reshape(-1)
+    if c.numel() < 1:
+        raise ValueError("a band needs one centre per row index 0 .. T")
+    lo = torch.cummax(torch.clamp(c - int(width) // 2, 0, max(0, int(npos) + 1 - int(width))), 0)[0].to(torch.int32)
+    first, last = (int(v) for v in lo[[0, -1]].cpu())
+    if first != 0 or last + int(width) <= int(npos):
+        raise ValueError("a centre from %d to %d gives no band of %d states from state 0 to state %d"
+                         % (int(c[0]), int(c[-1]), int(width), int(npos)))
+    return lo
+
+
+def band_center_from_path(path):
+    """The centre of a band from a remap path (transducer.map_to_sequence*: the position each row sits at): center[0] = 0,
+    center[t + 1] = path[t] + 1, the state behind row t.  -> int64 device tensor [T + 1]."""
+    import torch
+    from . import device as D
+    p = path if isinstance(path, torch.Tensor) else torch.as_tensor(np.asarray(path, dtype=np.int64))
+    p = p.to(D.device()).to(torch.int64).reshape(-1)
+    return torch.cat([torch.zeros(1, dtype=torch.int64, device=p.device), p + 1])
+
+
+def band_center_from_moves(move_row, nemit, nrow, kmer_len):
+    """The centre of a band over a read's own call: move_row [n] the row at which the call's path enters each of its k-mers
+    (viterbi_marginals_batch), nemit [n] the letters each called k-mer emitted (the overlap rule of bio.py / csrc/bases.hip).  The
+    draft's k-mer j ends with letter j + k - 1, so the k-mers passed by row t are the letters emitted in rows up to t, less k - 1,
+    clipped at 0.  -> int64 device tensor [nrow + 1]."""
+    import torch
+    from . import device as D
+    dev = D.device()
+    rows = torch.as_tensor(move_row).to(dev).to(torch.int64).reshape(-1)
+    emit = torch.as_tensor(nemit).to(dev).to(torch.int64).reshape(-1)
+    if rows.numel() != emit.numel():
+        raise ValueError("band_center_from_moves needs one letter count per move")
+    per_row = torch.zeros(int(nrow) + 1, dtype=torch.int64, device=dev)
+    keep = (rows >= 0) & (rows < int(nrow))
+    per_row.index_add_(0, rows[keep] + 1, emit[keep])              # (row t's letters count from row index t + 1 on)
+    return torch.clamp(torch.cumsum(per_row, 0) - (int(kmer_len) - 1), min=0)
+
+
+def shift_center(center, edits):
+    """The centre of a band after edits were applied to its sequence: every centre value above an applied edit's start moves by
+    that edit's new symbols less its deleted positions.  edits: rows (start, ndel, number of new symbols) in state coordinates, or
+    an EditSet.  No re-alignment: the rows keep their place.  -> int64 device tensor."""
+    import torch
+    from . import device as D
+    c = center if isinstance(center, torch.Tensor) else torch.as_tensor(np.asarray(center, dtype=np.int64))
+    c = c.to(D.device()).to(torch.int64)
+    if isinstance(edits, EditSet):
+        edits = list(zip(edits.start.tolist(), edits.ndel.tolist(), np.diff(edits.new_off).tolist()))
+    if not len(edits):
+        return c.clone()
+    e = sorted((int(s), int(d), int(m)) for s, d, m in edits)
+    starts = torch.as_tensor([s for s, _, _ in e], dtype=torch.int64, device=c.device)
+    delta = torch.as_tensor([0] + [m - d for _, d, m in e], dtype=torch.int64, device=c.device).cumsum(0)
+    return c + delta[torch.bucketize(c, starts, right=False)]     # (edits whose start lies below the value)
+
+
+def rescore_edits_banded_batch(post, seqs, edits, band_lo, width, blank=-1, min_prob=None, lengths=None, row_off=None,
+                               workspace_limit=None):
+    """rescore_edits_batch for whole reads (csrc/rescore_band.hip, design/rescore_band.md): the lattices keep `width` states per
+    row, state j in row t when band_lo[t] <= j < band_lo[t] + width, so a pair costs 16 (rows + 1) (width + 1) bytes of workspace
+    whatever its sequence's length, which may be anything up to BAND_MAX_POSITIONS.
+
+    post, seqs, edits, blank, min_prob, lengths, row_off, workspace_limit: as in rescore_edits_batch.
+    band_lo: per pair one integer array or tensor [rows + 1] (decode.band_lo makes one from a centre line): it begins at 0, has no
+    negative entry, does not decrease and ends with band_lo[rows] + width above the sequence's length; ValueError otherwise.
+    width: one of band_widths().
+
+    -> (score, ll_edit) as rescore_edits_batch: the log-likelihoods summed over the alignments that stay inside the band.  They
+    never exceed the dense values, and have their bits when the band is all 0 and holds every state.  An edit whose columns the
+    band never holds in the rows it needs scores -inf."""
+    return _rescore_edits("rescore_edits_banded_batch", post, seqs, edits, lengths, blank, min_prob, row_off, workspace_limit,
+                          (band_lo, width))
 
 
 def forwards_backwards(post, seq, full=False):

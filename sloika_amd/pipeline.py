@@ -350,19 +350,9 @@ class Basecaller(object):
         with per-read lengths, then the lattice of every read over its own rows of the posterior -- each read gets what a batch-1 call
         gives.  -> (scores, paths, lens, move_row, conf, logz) as call_chunks_qual returns them, and the per-read sample counts."""
         self._qual_check("call_reads_qual")
-        net = self.network
-        if not isinstance(net, layers.Serial) or type(net.layers[-1]) is not layers.Softmax:
-            raise ValueError("call_reads_qual needs a Serial network ending in a Softmax layer")
-        if min(len(s) for s in signals) < 100:
-            raise ValueError("a read is shorter than one window of 100 samples")
-        dev, start, nsamp, flags = self._trimmed_read_set(signals, trim, open_pore_fraction, scaling)
-        for r, f in enumerate(flags):
-            if f:
-                raise ValueError(batch.read_failure(f)[2].format(r))
-        padded = batch.pack_batch(dev, start, nsamp, max(nsamp))
+        padded, nsamp = self._padded_reads(signals, trim, open_pore_fraction, scaling, "call_reads_qual")
         with self._scope():
-            lengths = layers.ragged_lengths(nsamp)
-            post, steps = self._ragged_run(batch.normalise_reads_ragged(padded, lengths), lengths)
+            post, steps = self._read_posteriors(padded, nsamp)
             return self._marginals(post, steps) + (nsamp,)
 
     def call_fastq(self, signals, names=None, trim=(0, 0), open_pore_fraction=0.0, scaling=None, alphabet='ACGT', qmax=60):
@@ -434,6 +424,98 @@ class Basecaller(object):
             post = self.posteriors(chunks, scaling)
             return polish.polish(post, drafts, self.kmer_len, group=group, min_gain=min_gain, max_rounds=max_rounds, kinds=kinds,
                                  blank=0, min_prob=self.min_prob)
+
+    def _padded_reads(self, signals, trim, open_pore_fraction, scaling, who):
+        """Whole reads on their way to the network, for call_reads_qual and rescore_reads alike: the upload, trimming and failures
+        of call_reads.  -> (zero-padded batch on the device, sample counts)."""
+        net = self.network
+        if not isinstance(net, layers.Serial) or type(net.layers[-1]) is not layers.Softmax:
+            raise ValueError("%s needs a Serial network ending in a Softmax layer" % who)
+        if min(len(s) for s in signals) < 100:
+            raise ValueError("a read is shorter than one window of 100 samples")
+        dev, start, nsamp, flags = self._trimmed_read_set(signals, trim, open_pore_fraction, scaling)
+        for r, f in enumerate(flags):
+            if f:
+                raise ValueError(batch.read_failure(f)[2].format(r))
+        return batch.pack_batch(dev, start, nsamp, max(nsamp)), nsamp
+
+    def _read_posteriors(self, padded, nsamp):
+        """The network on the zero-padded batch with per-read lengths, as call_reads_qual runs it (inside _scope): -> (post
+        [T', B, nstate], int32 device tensor of the reads' rows)."""
+        lengths = layers.ragged_lengths(nsamp)
+        return self._ragged_run(batch.normalise_reads_ragged(padded, lengths), lengths)
+
+    def _read_bands(self, post, steps, drafts, center, slip):
+        """The drafts and centre lines rescore_reads / polish_reads hand to polish: -> (drafts, [centre per read])."""
+        import numpy as np
+        import torch
+        from . import bio, device as D, transducer
+        k, B = self.kmer_len, int(post.shape[1])
+        rows = steps.cpu().numpy().astype(np.int64)
+        if drafts is None:
+            if center is not None:
+                raise ValueError("a read's own call brings its centre line from its moves: center is for given drafts")
+            _, paths, lens, move_row, _, _ = self._marginals(post, steps)
+            paths, lens, move_row = paths.cpu().numpy(), lens.cpu().numpy(), move_row.cpu().numpy()
+            drafts, centers = [], []
+            for b in range(B):
+                states = paths[b, :lens[b]].astype(np.int64)
+                if not len(states):
+                    raise ValueError("read %d has no call to polish" % b)
+                nemit = np.concatenate([[k], np.minimum(bio.moves_of_states(states, k, self.nbase, False), k)])
+                drafts.append(bio.sequence_of_states(states, k, self.nbase, nemit[1:], 'ACGT'))
+                centers.append(decode.band_center_from_moves(move_row[b, :lens[b]], nemit, int(rows[b]), k))
+            return drafts, centers
+        drafts = [d.decode('utf-8') if isinstance(d, bytes) else d for d in drafts]
+        if isinstance(center, str):
+            if center != "remap":
+                raise ValueError("center is a list of centre lines, or 'remap'")
+            # the existing remap DP on the same posterior (its cost is the remap's, not the rescoring's)
+            ev_off = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+            pc = post if post.stride(2) == 1 else post.contiguous()
+            ltrans = torch.empty((int(ev_off[-1]), int(pc.shape[2])), dtype=torch.float32, device=pc.device)
+            ev_d = torch.from_numpy(ev_off).to(pc.device)
+            _lib.check(_lib.lib().slk_remap_pack_log_post_f32(pc.data_ptr(), pc.stride(0), pc.stride(1), int(pc.shape[0]), B,
+                                                              int(pc.shape[2]), steps.data_ptr(), ev_d.data_ptr(),
+                                                              float(self.min_prob), ltrans.data_ptr(), D.stream_ptr()), "rescore_reads.pack")
+            seqs = [bio.seq_to_states(d, k) + 1 for d in drafts]
+            _, paths = transducer.map_to_sequence_packed(ltrans, ev_off, seqs, slip, long_reference=True)
+            return drafts, [decode.band_center_from_path(p) for p in paths]
+        if center is None or len(center) != B:
+            raise ValueError("given drafts need one centre line per read (center=[...]), or center='remap'")
+        return drafts, list(center)
+
+    def rescore_reads(self, signals, drafts=None, group=None, width=512, center=None, trim=(0, 0), open_pore_fraction=0.0,
+                      scaling=None, kinds=('sub', 'del', 'ins'), slip=5.0):
+        """rescore_chunks for whole reads (csrc/rescore_band.hip, design/rescore_band.md): the posterior of every read over its own
+        rows, as call_reads_qual gets it, and polish.rescore_drafts with banded lattices of `width` states per row.
+
+        drafts None: every read is rescored against its own call, the band laid round the call's moves
+        (decode.band_center_from_moves).  Given drafts (base strings, for example genome.read_references records; group as in
+        rescore_chunks) come with center=[one centre line per read] or center="remap", which aligns each read to its draft by
+        transducer.map_to_sequence_packed(long_reference=True) with slip penalty `slip` first.  Refusals are rescore_chunks'.
+        -> [polish.Rescored]; `score` and `gain` are the banded ones."""
+        from . import polish
+        self._polish_check(signals, signals if drafts is None else drafts, "rescore_reads")
+        padded, nsamp = self._padded_reads(signals, trim, open_pore_fraction, scaling, "rescore_reads")
+        with self._scope():
+            post, steps = self._read_posteriors(padded, nsamp)
+            drafts, centers = self._read_bands(post, steps, drafts, center, slip)
+            return polish.rescore_drafts(post, drafts, self.kmer_len, group=group, kinds=kinds, blank=0, min_prob=self.min_prob,
+                                         lengths=steps, band=(centers, width))
+
+    def polish_reads(self, signals, drafts=None, group=None, width=512, center=None, trim=(0, 0), open_pore_fraction=0.0,
+                     scaling=None, kinds=('sub', 'del', 'ins'), min_gain=0.0, max_rounds=8, slip=5.0):
+        """polish_chunks for whole reads: one network pass, then rounds of rescore_reads' banded scoring; the centre lines follow the
+        applied edits (polish.shifted_centers), nothing is re-aligned between rounds.  -> [polish.Polished]."""
+        from . import polish
+        self._polish_check(signals, signals if drafts is None else drafts, "polish_reads")
+        padded, nsamp = self._padded_reads(signals, trim, open_pore_fraction, scaling, "polish_reads")
+        with self._scope():
+            post, steps = self._read_posteriors(padded, nsamp)
+            drafts, centers = self._read_bands(post, steps, drafts, center, slip)
+            return polish.polish(post, drafts, self.kmer_len, group=group, min_gain=min_gain, max_rounds=max_rounds, kinds=kinds,
+                                 blank=0, min_prob=self.min_prob, lengths=steps, band=(centers, width))
 
     def _sequence_columns(self, chunks, sequences, who, what):
         """The posterior columns of one sequence per chunk, each k-mer states or a base string (score_chunks): state + 1, column 0 is

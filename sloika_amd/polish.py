@@ -59,12 +59,15 @@ def draft_edits(draft, kmer_len, kinds, alphabet, blank, nstate):
     return state_columns(old, blank, nstate), rows, decode.EditSet.from_list(trip)
 
 
-def rescore_drafts(post, drafts, kmer_len, group=None, kinds=bio.EDIT_KINDS, alphabet='ACGT', blank=-1, **kwargs):
+def rescore_drafts(post, drafts, kmer_len, group=None, kinds=bio.EDIT_KINDS, alphabet='ACGT', blank=-1, band=None, **kwargs):
     """Score every single-letter edit of each group's draft under each of the group's posteriors.
 
     post and kwargs (lengths, min_prob, row_off, workspace_limit): as decode.rescore_edits_batch.  drafts: one base string per pair;
     group[b] names the draft pair b is a read of (pairs of one group carry the same string; None: every pair is its own group).
     kinds: per group a tuple of kinds when given as a dict {name: kinds}, else the same for all.
+    band: None for the dense lattices, or (centers, width) for banded ones (decode.rescore_edits_banded_batch, whole reads): per
+    pair the k-mer of its draft each row index 0 .. rows sits at (decode.band_center_from_path / band_center_from_moves); the
+    band of `width` states is laid round it by decode.band_lo.  score and gain are then the banded ones.
     -> [Rescored] in the order of each group's first pair."""
     import torch
     shape = tuple(post.shape)
@@ -80,7 +83,14 @@ def rescore_drafts(post, drafts, kmer_len, group=None, kinds=bio.EDIT_KINDS, alp
         tables.append(rows)
         for b in pairs:
             seqs[b], edits[b] = cols, eset
-    score, ll = decode.rescore_edits_batch(post, seqs, edits, blank=blank, **kwargs)
+    if band is None:
+        score, ll = decode.rescore_edits_batch(post, seqs, edits, blank=blank, **kwargs)
+    else:
+        centers, width = band
+        if len(centers) != len(drafts):
+            raise ValueError("band needs one centre line per pair (%d for %d)" % (len(centers), len(drafts)))
+        los = [decode.band_lo(c, len(q), width) for c, q in zip(centers, seqs)]
+        score, ll = decode.rescore_edits_banded_batch(post, seqs, edits, los, width, blank=blank, **kwargs)
     out = []
     for (name, draft, pairs), rows in zip(groups, tables):
         idx = torch.as_tensor(pairs, device=score.device)
@@ -113,10 +123,23 @@ def accept_edits(rows, gain, kmer_len, min_gain=0.0):
     return taken
 
 
-def polish(post, drafts, kmer_len, group=None, min_gain=0.0, max_rounds=8, kinds=bio.EDIT_KINDS, alphabet='ACGT', blank=-1, **kwargs):
+def shifted_centers(centers, draft, taken, kmer_len, alphabet='ACGT'):
+    """The centre lines of a draft's pairs after `taken` (rows of accept_edits) were applied to it: each edit moves the values above
+    its first changed k-mer by the k-mers it adds or removes (decode.shift_center).  The rows keep their place: no re-alignment."""
+    old = bio.seq_to_states(draft, kmer_len, alphabet)
+    trip = []
+    for t in taken:
+        a, d, new = bio.edit_states(old, bio.seq_to_states(bio.apply_letter_edits(draft, [t[:3]]), kmer_len, alphabet))
+        trip.append((a, d, len(new)))
+    return [decode.shift_center(c, trip) for c in centers]
+
+
+def polish(post, drafts, kmer_len, group=None, min_gain=0.0, max_rounds=8, kinds=bio.EDIT_KINDS, alphabet='ACGT', blank=-1, band=None,
+           **kwargs):
     """Greedy polishing of draft strings against the posteriors of their reads.  Per round every group still running is rescored
     (rescore_drafts), accept_edits picks its edits, they are applied, and the group stops when none is picked; after max_rounds the
-    strings are scored once more without candidates.  post, drafts, group, kinds, blank, kwargs: as rescore_drafts.
+    strings are scored once more without candidates.  post, drafts, group, kinds, blank, band, kwargs: as rescore_drafts; with a
+    band the centre lines follow the applied edits from round to round (shifted_centers).
     -> [Polished] in the order of each group's first pair."""
     groups = groups_of(drafts, group)
     names = [g for g, _, _ in groups]
@@ -129,9 +152,11 @@ def polish(post, drafts, kmer_len, group=None, min_gain=0.0, max_rounds=8, kinds
     applied = dict((g, []) for g in names)
     rounds = dict((g, 0) for g in names)
     score = {}
+    centers = None if band is None else list(band[0])
     for r in range(max_rounds + 1):
         want = dict((g, tuple(kinds) if running[g] and r < max_rounds else ()) for g in names)
-        res = rescore_drafts(post, [text[g] for g in member], kmer_len, group=member, kinds=want, alphabet=alphabet, blank=blank, **kwargs)
+        res = rescore_drafts(post, [text[g] for g in member], kmer_len, group=member, kinds=want, alphabet=alphabet, blank=blank,
+                             band=None if band is None else (centers, band[1]), **kwargs)
         for x in res:
             score[x.name] = float(x.score.item())
             taken = accept_edits(x.edits, x.gain.cpu().numpy(), kmer_len, min_gain) if want[x.name] else []
@@ -139,6 +164,9 @@ def polish(post, drafts, kmer_len, group=None, min_gain=0.0, max_rounds=8, kinds
                 running[x.name] = False
                 continue
             text[x.name] = bio.apply_letter_edits(x.draft, [t[:3] for t in taken])
+            if band is not None:
+                for b, c in zip(x.pairs, shifted_centers([centers[b] for b in x.pairs], x.draft, taken, kmer_len, alphabet)):
+                    centers[b] = c
             applied[x.name].extend((r,) + t for t in taken)
             rounds[x.name] += 1
         if not any(running.values()):
