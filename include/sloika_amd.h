@@ -1126,6 +1126,73 @@ SLK_API int slk_pileup_call_qual_u8(const int32_t *counts, const int32_t *ins, c
                                     uint8_t *letters, uint8_t *nlet, uint8_t *flags, uint8_t *letq, uint8_t *posq,
                                     slk_stream_t stream);
 
+/* f10c. The genome half and the signal half joined (csrc/polish_genome.hip; design/polish_genome.md section 1 DEFINES the row span, the
+ * window, the centre line, the candidates' order and triples and the sum, and is not repeated here).
+ *   slk_polish_read_windows: one wave per read.  paths:[B][ldp], lens:[B], move_row:[B][ldm] as slk_viterbi_marginals_f32 left them
+ *     (T: the entries a row may hold, T <= ldp, ldm), nrow:[B] the posterior rows of each read; qlen, ldq, roff, rows, ops, ops_off,
+ *     ops_bytes, tb_status as slk_align_traceback_batch_u8 took and left them (window coordinates; a '-' read against the
+ *     reverse-complemented window); minus, keep as slk_pileup_columns_u8; wstart:[B] int64 the packed-genome position of the
+ *     mapping window's first forward letter, coff:[B] int64 the packed position of the read's contig, G the packed genome's length.
+ *     letter_row:[B][ldq] int32 work table: the posterior row of every called letter (the move_row of the k-mer that emitted it, by
+ *     the overlap rule of slk_paths_to_bases with always_move = 1).  Out, for a read with status SLK_POLISH_DONE only: row_span:
+ *     [B][2] int32 the rows [r0, r1) of the aligned part, window:[B][2] int64 the draft window [w0, w1) in CONTIG coordinates, and
+ *     r1 - r0 + 1 int32 entries at center + center_off[b] (center_off:[B + 1] device int64; a slice too short: SLK_POLISH_CENTER).
+ *     status:[B] int32: SLK_POLISH_DONE, SLK_POLISH_SKIPPED (keep[b] == 0 or tb_status[b] is not SLK_ALIGN_TB_DONE: nothing else of
+ *     the read is looked at) or a negative SLK_POLISH_* code.  Everything is device data and is not trusted: a refused read gets
+ *     its status and nothing else (its slice of the work table apart); no loop bound depends on a value that has not been checked.
+ *   slk_letter_edits_count: nwin windows (win_off: the packed position of the window's contig, [w0, w1) in contig coordinates; all
+ *     device int64) -> ncand:[nwin + 1], nkmer:[nwin + 1] int64 with entry 0 zero and entry b + 1 the candidates and the k-mers of
+ *     window b (0 for a window that is no span of the genome).  An inclusive prefix sum in place makes them cand_off and pos_off.
+ *     kmer_len 3 .. SLK_RESCORE_MAX_NEW - 1; kinds: bit 0 substitutions, bit 1 deletions, bit 2 insertions; margin >= 0.
+ *   slk_letter_edits_emit: per candidate cand_pair (its window), cand_start, cand_ndel, cand_edit = 8 * packed forward position +
+ *     slot, and the NUMBER of its new symbols in cand_new_off[i + 1] (cand_new_off[0] = 0): an inclusive prefix sum in place makes
+ *     cand_new_off.  minus:[nwin] device int32: the window is the reverse complement of its span.  A window whose share of cand_off
+ *     is not its own count is not followed: its candidates get start -1, which the scoring entries refuse with NaN.
+ *   slk_letter_edits_new: the new symbols (posterior columns: state + (state >= blank)) behind the summed cand_new_off; new_cap: the
+ *     entries cand_new holds (ncand * (kmer_len + 1) always suffices).  A k-mer with a letter that is none of A C G T is column -1.
+ *   slk_polish_window_kmers: seq:[npos] int32, the windows' own k-mer columns behind pos_off:[nwin + 1].
+ *   slk_polish_sum_gains_f64: order:[ncand] device int64, the candidates sorted by (cand_edit, cand_pair) -- the caller's sort.  Adds
+ *     into gain:[P][8] float64 and support:[P][8] int32, the cells of packed positions [region_start, region_start + P): per cell,
+ *     continuing from what it holds, ll_edit - score[cand_pair] of its candidates in that order when both are finite, and their
+ *     number; a NaN ll_edit or score makes the cell NaN.  One thread walks a cell: no floating-point atomics, no bit depends on the
+ *     launch.  The caller zeroes the tables once; launches that come in read order give the bits of one launch.                    */
+#define SLK_POLISH_DONE 0
+#define SLK_POLISH_SKIPPED 1
+#define SLK_POLISH_BAD_SPAN (-1)   /* a span outside [0, qlen] / [0, rlen], or a length beyond 65535 or the row pitch   */
+#define SLK_POLISH_BAD_COUNT (-2)  /* a negative count                                                                   */
+#define SLK_POLISH_BAD_SUM (-3)    /* the spans are not the sums of the counts                                           */
+#define SLK_POLISH_OPS (-4)        /* the read's ops slice is not its column count long, or outside `ops`                */
+#define SLK_POLISH_POSITION (-5)   /* the mapping window is not inside the genome, or in front of its contig             */
+#define SLK_POLISH_BAD_CODE (-6)   /* a code byte above 3                                                                */
+#define SLK_POLISH_CODE_COUNT (-7) /* the columns of a kind are not as many as the row says                              */
+#define SLK_POLISH_PATH (-8)       /* no call, a state that is no k-mer, or letters that are not as many as qlen says    */
+#define SLK_POLISH_MOVE_ROW (-9)   /* a move_row outside the read's rows, or one that decreases                          */
+#define SLK_POLISH_SHORT (-10)     /* the aligned window has no k-mer                                                    */
+#define SLK_POLISH_FEW_ROWS (-11)  /* the aligned part has fewer rows than the window has k-mers                         */
+#define SLK_POLISH_CENTER (-12)    /* the read's slice of `center` is shorter than its rows + 1                          */
+SLK_API int slk_polish_read_windows(const int32_t *paths, long ldp, const int32_t *lens, const int32_t *move_row, long ldm, int T,
+                                    const int32_t *nrow, const int32_t *qlen, long ldq, const int64_t *roff, const int32_t *rows,
+                                    const uint8_t *ops, const int64_t *ops_off, size_t ops_bytes, const int32_t *tb_status,
+                                    const int32_t *minus, const uint8_t *keep, const int64_t *wstart, const int64_t *coff, long G,
+                                    int B, int kmer_len, const int64_t *center_off, int32_t *letter_row, int32_t *status,
+                                    int32_t *row_span, int64_t *window, int32_t *center, slk_stream_t stream);
+SLK_API int slk_letter_edits_count(const int64_t *win_off, const int64_t *w0, const int64_t *w1, int nwin, long G, int kmer_len,
+                                   int kinds, int margin, int64_t *ncand, int64_t *nkmer, slk_stream_t stream);
+SLK_API int slk_letter_edits_emit(const uint8_t *genome, long G, const int64_t *win_off, const int64_t *w0, const int64_t *w1,
+                                  const int32_t *minus, int nwin, int kmer_len, int kinds, int margin, const int64_t *cand_off,
+                                  int64_t ncand, int32_t *cand_pair, int32_t *cand_start, int32_t *cand_ndel, int64_t *cand_new_off,
+                                  int64_t *cand_edit, slk_stream_t stream);
+SLK_API int slk_letter_edits_new(const uint8_t *genome, long G, const int64_t *win_off, const int64_t *w0, const int64_t *w1,
+                                 const int32_t *minus, int nwin, int kmer_len, int blank, int kinds, int margin,
+                                 const int64_t *cand_off, int64_t ncand, const int32_t *cand_start, const int64_t *cand_new_off,
+                                 int64_t new_cap, int32_t *cand_new, slk_stream_t stream);
+SLK_API int slk_polish_window_kmers(const uint8_t *genome, long G, const int64_t *win_off, const int64_t *w0, const int64_t *w1,
+                                    const int32_t *minus, int nwin, int kmer_len, int blank, const int64_t *pos_off, int64_t npos,
+                                    int32_t *seq, slk_stream_t stream);
+SLK_API int slk_polish_sum_gains_f64(const double *score, int nread, const double *ll_edit, const int32_t *cand_pair,
+                                     const int64_t *cand_edit, const int64_t *order, int64_t ncand, int64_t region_start, int64_t P,
+                                     double *gain, int32_t *support, slk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

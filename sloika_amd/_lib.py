@@ -188,6 +188,13 @@ PROTOTYPES = {
     "slk_pileup_count_qual_u8": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _l, _i, _l, _l, _i, _vp, _vp, _vp, _vp,
                                       _vp, _vp]),
     "slk_pileup_call_qual_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _l, _l, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "slk_polish_read_windows": (_i, [_vp, _l, _vp, _vp, _l, _i, _vp, _vp, _l, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _l, _i, _i,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "slk_letter_edits_count": (_i, [_vp, _vp, _vp, _i, _l, _i, _i, _i, _vp, _vp, _vp]),
+    "slk_letter_edits_emit": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "slk_letter_edits_new": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp]),
+    "slk_polish_window_kmers": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, C.c_int64, _vp, _vp]),
+    "slk_polish_sum_gains_f64": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -821,6 +821,98 @@ def rescore_edits_banded_batch(post, seqs, edits, band_lo, width, blank=-1, min_
                           (band_lo, width))
 
 
+def rescore_edits_banded_device(post, row_off, row_step, nrow, seq, pos_off, band_lo, width, cand_off, cand_pair, cand_start, cand_ndel,
+                                cand_new_off, cand_new, blank=0, min_prob=None, workspace_limit=None):
+    """The launch half of rescore_edits_banded_batch, on pairs and candidates that already are device arrays in the C entry's own
+    layout (design/polish_genome.md 2): nothing is listed, sorted or uploaded but the small per-pair arrays the host holds anyway.
+
+    post: float32 or float64 device tensor whose last dimension holds the states and whose rows lie stride(-2) apart; row t of pair b
+    is row row_off[b] + t * row_step of it (a [T, B, S] posterior: row_off[b] = batch index + first row * B, row_step = B).
+    row_off int64 [n], nrow int32 [n]: HOST arrays (the workspace is sized from them).  seq int32 device, pos_off int64 device
+    [n + 1]; band_lo int32 device, pair b's nrow[b] + 1 entries behind one another in pair order.  cand_off: HOST int64 [n + 1], the
+    candidates of pair b are cand_off[b] .. cand_off[b + 1]; cand_pair (the pair, 0 .. n - 1, ascending), cand_start, cand_ndel int32
+    device, cand_new_off int64 device [ncand + 1], cand_new int32 device.
+    -> (score float64 device [n], ll_edit float64 device [ncand]), the bits rescore_edits_banded_batch gives the same pairs and
+    candidates.  The same workspace arithmetic and the same cut into launches on pair boundaries by `workspace_limit`; cand_pair is
+    rebased per launch on the device."""
+    import ctypes
+    import torch
+    from . import device as D
+    from . import transducer
+    who = "rescore_edits_banded_device"
+    if post.dtype not in (torch.float32, torch.float64) or not post.is_cuda or post.stride(-1) != 1:
+        raise ValueError("%s takes a float32 or float64 device posterior with contiguous states" % who)
+    S, ld, dev = int(post.shape[-1]), int(post.stride(-2)), post.device
+    if S > FORWARD_BACKWARD_MAX_STATES:
+        raise ValueError("a posterior of %d states is above %s's limit of %d" % (S, who, FORWARD_BACKWARD_MAX_STATES))
+    if not 0 <= int(blank) < S:
+        raise ValueError("blank column %d outside the %d states" % (blank, S))
+    if int(width) not in band_widths():
+        raise ValueError("a band of %d states is not built: %s" % (width, ", ".join(str(w) for w in band_widths())))
+    if min_prob is not None and not 0.0 <= float(min_prob) < 1.0:
+        raise ValueError("min_prob must lie in [0, 1)")
+    if min_prob and post.dtype != torch.float32:
+        raise ValueError("min_prob applies to float32 posteriors (decode.prepare_post is float32 arithmetic)")
+    row_off = np.ascontiguousarray(row_off, dtype=np.int64).reshape(-1)
+    lens = np.ascontiguousarray(nrow, dtype=np.int32).reshape(-1)
+    coff = np.ascontiguousarray(cand_off, dtype=np.int64).reshape(-1)
+    n = len(lens)
+    if n < 1 or len(row_off) != n or len(coff) != n + 1 or pos_off.numel() != n + 1:
+        raise ValueError("%s needs one row_off and nrow per pair, and one entry more of pos_off and cand_off" % who)
+    rows_in_post = post.numel() // max(int(post.stride(-2)), 1) if post.is_contiguous() else None
+    if lens.min() < 0 or row_off.min() < 0 or int(row_step) < 1 or \
+            (rows_in_post is not None and int((row_off + np.maximum(lens.astype(np.int64) - 1, 0) * int(row_step)).max()) >= rows_in_post):
+        raise ValueError("a pair's rows lie outside the posterior")
+    ncand = int(coff[-1])
+    if coff[0] != 0 or (np.diff(coff) < 0).any() or cand_new_off.numel() != ncand + 1 or \
+            min(cand_pair.numel(), cand_start.numel(), cand_ndel.numel()) < ncand:
+        raise ValueError("%s: cand_off does not describe the candidate arrays" % who)
+    boff = np.concatenate([[0], np.cumsum(lens.astype(np.int64) + 1)]).astype(np.int64)
+    if band_lo.dtype != torch.int32 or band_lo.numel() != int(boff[-1]):
+        raise ValueError("%s needs nrow + 1 int32 band entries per pair (%d, not %d)" % (who, int(boff[-1]), band_lo.numel()))
+    for name, t, dt in (("seq", seq, torch.int32), ("pos_off", pos_off, torch.int64), ("cand_pair", cand_pair, torch.int32),
+                        ("cand_start", cand_start, torch.int32), ("cand_ndel", cand_ndel, torch.int32),
+                        ("cand_new_off", cand_new_off, torch.int64), ("cand_new", cand_new, torch.int32)):
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous %s device tensor" % (who, name, dt))
+    L = _lib.lib()
+    limit = transducer.WORKSPACE_LIMIT if workspace_limit is None else int(workspace_limit)
+
+    def need(lo, hi):
+        part = np.ascontiguousarray(lens[lo:hi])
+        return int(L.slk_rescore_edits_banded_workspace_bytes(hi - lo, part.ctypes.data_as(ctypes.c_void_p), int(width)))
+
+    alone = [need(b, b + 1) for b in range(n)]
+    if max(alone) > limit:
+        b = int(np.argmax(alone))
+        raise ValueError("pair %d needs %d bytes of workspace, above the workspace_limit of %d" % (b, alone[b], limit))
+    runs = transducer.workspace_runs([v - 256 + 16 for v in alone], max(limit - 512, 0))
+    roff_d, lens_d, boff_d = torch.as_tensor(row_off).to(dev), torch.as_tensor(lens).to(dev), torch.as_tensor(boff).to(dev)
+    score = torch.empty(n, dtype=torch.float64, device=dev)
+    ll = torch.empty(max(ncand, 1), dtype=torch.float64, device=dev)
+    ws = torch.empty(max(need(lo, hi) for lo, hi in runs), dtype=torch.uint8, device=dev)
+    rows = float(ncand) * float(np.mean(lens))
+    with profiler.region("rescore_edits", 20.0 * rows, 16.0 * rows):
+        for lo, hi in runs:
+            c0, c1 = int(coff[lo]), int(coff[hi])
+            head = (post.data_ptr(), ld, roff_d.data_ptr() + 8 * lo, int(row_step), lens_d.data_ptr() + 4 * lo, S, seq.data_ptr(),
+                    pos_off.data_ptr() + 8 * lo, hi - lo, int(blank))
+            strip = (band_lo.data_ptr(), boff_d.data_ptr() + 8 * lo, int(width))
+            if c1 > c0:
+                local = cand_pair[c0:c1] if lo == 0 else cand_pair[c0:c1] - lo
+                cands = (local.data_ptr(), cand_start.data_ptr() + 4 * c0, cand_ndel.data_ptr() + 4 * c0, cand_new_off.data_ptr() + 8 * c0,
+                         cand_new.data_ptr(), c1 - c0)
+            else:
+                cands = (None, None, None, None, None, 0)
+            tail = (score.data_ptr() + 8 * lo, ll.data_ptr() + 8 * c0, ws.data_ptr(), need(lo, hi), D.stream_ptr())
+            if post.dtype == torch.float32:
+                rc = L.slk_rescore_edits_banded_batch_f32(*head, float(min_prob or 0.0), *strip, *cands, *tail)
+            else:
+                rc = L.slk_rescore_edits_banded_batch_f64(*head, *strip, *cands, *tail)
+            _lib.check(rc, "decode." + who)
+    return score, ll[:ncand]
+
+
 def forwards_backwards(post, seq, full=False):
     """Forward-backward for one pair with the reference's conventions (a 2-D posterior, the blank in the last column, as
     decode.forwards): -> numpy (score float64, occ [time, nstate] with the dtype of `post`, emit_row int32 [len(seq)], emit_prob

@@ -425,6 +425,21 @@ def quality_weights(min_qual=0, qmax=60):
     return np.where(v < min_qual, 0, np.minimum(v, qmax)).astype(np.uint8)
 
 
+def region_span(index, region):
+    """region=(contig name or index, start, end) within that contig, or None for the whole genome -> (first packed position, number of
+    positions), as Pileup reads it."""
+    if region is None:
+        return 0, index.G
+    c, start, end = region
+    if not isinstance(c, (int, np.integer)):
+        if c not in index.names:
+            raise ValueError("genome: region= names the contig %r, which the index does not hold" % (c,))
+        c = index.names.index(c)
+    if c < 0 or c >= len(index.names) or start < 0 or end < start or end > index.lengths[c]:
+        raise ValueError("genome: region=%r lies outside the contig" % (region,))
+    return int(index.offsets[c]) + int(start), int(end) - int(start)
+
+
 class Pileup(object):
     """Zeroed count tables on the device for a span of the packed genome of `index`, to which batches of mapped reads are added
     (design/pileup.md section 1 defines every quantity).
@@ -701,6 +716,43 @@ class Consensus(object):
             if self.flags[p] & FLAG_INSERTED:
                 out.append((ix.names[c], pos, 'ins', '', text[len(text) - nins:], int(cn[7]), int(cn[6]))
                            + ((int(letq[k, len(text) - nins:len(text)].min()),) if with_qual else ()))
+        return out
+
+    def polish_variants(self, rescored):
+        """The rows of variants() with what the reads' signal says about exactly that edit beside them (the join of
+        design/polish_genome.md): `rescored` a polish.GenomeRescored of reads mapped to the SAME index, the reference the pileup was
+        made on.  Each row gets three more values: gain (float), support (int) and single (bool).  A substitution, a deletion and an
+        insertion of one letter are one of the 8 cells of their position -- an insertion BEHIND position p is the insertion in front
+        of p + 1 --; an insertion of more letters is not a single-letter edit: gain None, support 0, single False.  A variant outside
+        the rescored region has gain None and support 0 as well, with single True."""
+        import torch
+        ix = self.pileup.index
+        if rescored.index is not ix:
+            raise ValueError("genome: polish_variants needs reads rescored against the index the pileup was made on")
+        rows = self.variants()
+        cells = []
+        for name, pos, kind, ref, alt, _, _ in rows:
+            cell = None
+            if kind != 'ins' or len(alt) == 1:
+                try:
+                    p, slot = rescored.cell_of(name, pos + 1 if kind == 'ins' else pos, kind, alt)
+                    cell = 8 * p + slot
+                except ValueError:
+                    cell = None
+            cells.append(cell)
+        have = [c for c in cells if c is not None]
+        gain = support = []
+        if have:
+            at = torch.as_tensor(have, dtype=torch.int64, device=rescored.gain.device)
+            gain, support = rescored.gain.reshape(-1)[at].cpu().numpy(), rescored.support.reshape(-1)[at].cpu().numpy()
+        out, k = [], 0
+        for row, cell in zip(rows, cells):
+            single = row[2] != 'ins' or len(row[4]) == 1
+            if cell is None:
+                out.append(row + (None, 0, single))
+            else:
+                out.append(row + (float(gain[k]), int(support[k]), True))
+                k += 1
         return out
 
     def summary(self):

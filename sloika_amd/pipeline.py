@@ -517,6 +517,46 @@ class Basecaller(object):
             return polish.polish(post, drafts, self.kmer_len, group=group, min_gain=min_gain, max_rounds=max_rounds, kinds=kinds,
                                  blank=0, min_prob=self.min_prob, lengths=steps, band=(centers, width))
 
+    def _genome_reads(self, signals, trim, open_pore_fraction, scaling, who):
+        """Whole reads for rescore_genome / polish_genome (inside _scope): the posterior of every read over its own rows and the call
+        with its moves, as call_reads_qual makes them.  -> (post, steps, paths, lens, move_row)."""
+        self._polish_check(signals, signals, who)
+        self._qual_check(who)
+        padded, nsamp = self._padded_reads(signals, trim, open_pore_fraction, scaling, who)
+        post, steps = self._read_posteriors(padded, nsamp)
+        _, paths, lens, move_row, _, _ = self._marginals(post, steps)
+        return post, steps, paths, lens, move_row
+
+    def rescore_genome(self, signals, index, width=512, margin=None, kinds=('sub', 'del', 'ins'), keep=None, region=None, trim=(0, 0),
+                       open_pore_fraction=0.0, scaling=None, workspace_limit=None, **map_kwargs):
+        """What the signal of whole reads says about every single-letter edit of a genome (design/polish_genome.md): the reads are
+        called (call_reads_qual's posterior and moves), the calls placed on `index` (genome.Index.map_paths(ops=True, **map_kwargs)),
+        and polish.rescore_genome scores each read's window under its own rows and sums the gains on genome coordinates.
+        keep: None, a bool mask of the reads, or a function (res, strand, info) -> mask (info['edge'] == 0 is the usual filter).
+        Refusals are rescore_chunks'.  -> polish.GenomeRescored."""
+        from . import polish
+        with self._scope():
+            post, steps, paths, lens, move_row = self._genome_reads(signals, trim, open_pore_fraction, scaling, "rescore_genome")
+            got = index.map_paths(paths, lens, self.kmer_len, ops=True, **map_kwargs)
+            res, strand, info, ops = got[0], got[1], got[2], got[4]
+            mask = keep(res, strand, info) if callable(keep) else keep
+            return polish.rescore_genome(post, steps, paths, lens, move_row, index, res, strand, info, ops, self.kmer_len, width=width,
+                                         margin=margin, kinds=kinds, keep=mask, region=region, blank=0, min_prob=self.min_prob,
+                                         workspace_limit=workspace_limit)
+
+    def polish_genome(self, signals, index, width=512, margin=None, kinds=('sub', 'del', 'ins'), keep=None, min_gain=0.0,
+                      min_support=2, max_rounds=4, trim=(0, 0), open_pore_fraction=0.0, scaling=None, workspace_limit=None,
+                      **map_kwargs):
+        """polish.polish_genome on whole reads: one network pass and one decode, then rounds of mapping the same calls onto the
+        current strings, rescore_genome's sums and the edits the signal prefers.  `index` may be the reference or
+        genome.Index(dict(consensus.sequences())).  -> ([polish.GenomePolished] per contig, the last round's polish.GenomeRescored)."""
+        from . import polish
+        with self._scope():
+            post, steps, paths, lens, move_row = self._genome_reads(signals, trim, open_pore_fraction, scaling, "polish_genome")
+            return polish.polish_genome(post, steps, paths, lens, move_row, index, self.kmer_len, width=width, margin=margin,
+                                        kinds=kinds, keep=keep, min_gain=min_gain, min_support=min_support, max_rounds=max_rounds,
+                                        blank=0, min_prob=self.min_prob, workspace_limit=workspace_limit, map_kwargs=map_kwargs)
+
     def _sequence_columns(self, chunks, sequences, who, what):
         """The posterior columns of one sequence per chunk, each k-mer states or a base string (score_chunks): state + 1, column 0 is
         the blank (variables.nstate, transducer=True)."""

@@ -172,3 +172,362 @@ def polish(post, drafts, kmer_len, group=None, min_gain=0.0, max_rounds=8, kinds
         if not any(running.values()):
             break
     return [Polished(g, text[g], applied[g], rounds[g], score[g]) for g in names]
+
+
+# ---- on genome coordinates (csrc/polish_genome.hip, design/polish_genome.md) ----------------------------------------------------------
+
+#: status of a read in rescore_genome (include/sloika_amd.h: SLK_POLISH_*); READ_UNMAPPED and READ_NOT_KEPT are the host's
+READ_DONE, READ_SKIPPED, READ_UNMAPPED, READ_NOT_KEPT = 0, 1, 2, 3
+READ_REASONS = {
+    1: "no columns (an empty alignment, or a traceback that failed)", 2: "unmapped", 3: "left out by keep=",
+    -1: "a span of its row lies outside the sequences", -2: "its row has a negative count",
+    -3: "the spans of its row are not the sums of its counts", -4: "its slice of the column codes does not have the length of its alignment",
+    -5: "its mapping window is not inside the genome", -6: "a column code that is no op", -7: "the columns of a kind are not as many as its row says",
+    -8: "its call is empty, holds a state that is no k-mer or spells other letters than were aligned", -9: "a move_row outside its rows, or one that decreases",
+    -10: "its aligned window has no k-mer", -11: "its aligned part has fewer rows than the window has k-mers", -12: "no room for its centre line",
+}
+KIND_BITS = {'sub': 1, 'del': 2, 'ins': 4}
+
+
+def kinds_mask(kinds):
+    unknown = [k for k in kinds if k not in KIND_BITS]
+    if unknown:
+        raise ValueError("unknown kind of edit %r (known: %s)" % (unknown[0], ', '.join(bio.EDIT_KINDS)))
+    return sum(KIND_BITS[k] for k in set(kinds))
+
+
+def _check_kmer_len(kmer_len):
+    if int(kmer_len) != kmer_len or not 3 <= kmer_len <= decode.rescore_max_new() - 1:
+        raise ValueError("kmer_len = %r outside 3 .. %d (an edit may bring kmer_len + 1 new symbols)" % (kmer_len, decode.rescore_max_new() - 1))
+
+
+def letter_edits(genome, win_off, w0, w1, minus, kmer_len, blank=0, kinds=bio.EDIT_KINDS, margin=0):
+    """Every single-letter edit of a batch of windows of the packed genome, made on the device in the layout the rescoring entries read
+    (slk_letter_edits_count / _emit / _new, slk_polish_window_kmers).  genome: uint8 device tensor (Index.genome); win_off, w0, w1:
+    int64 device tensors [nwin], the packed position of each window's contig and the window [w0, w1) within it; minus: int32 device
+    tensor, non-zero where the window is the reverse complement of its span.  Edits lie `margin` letters from either end.
+    -> namespace: cand_off, pos_off (device int64 [nwin + 1]) and their host copies cand_off_host, pos_off_host (the one round trip);
+    cand_pair, cand_start, cand_ndel (int32), cand_new_off (int64), cand_new (int32), cand_edit (int64 = 8 * packed forward position
+    + slot: 0-2 substitutions in alphabet order without the draft's letter, 3 deletion, 4-7 insertions in front); seq (int32)."""
+    import types
+    import torch
+    from . import _lib, device as D
+    _check_kmer_len(kmer_len)
+    mask, margin, nwin, G = kinds_mask(kinds), int(margin), int(win_off.numel()), int(genome.numel())
+    if margin < 0 or blank < 0:
+        raise ValueError("margin and blank are not negative")
+    dev = genome.device
+    for name, t, dt in (("win_off", win_off, torch.int64), ("w0", w0, torch.int64), ("w1", w1, torch.int64), ("minus", minus, torch.int32)):
+        if t.dtype != dt or t.device != dev or t.numel() != nwin or not t.is_contiguous():
+            raise ValueError("letter_edits: %s must be a contiguous %s device tensor with one entry per window" % (name, dt))
+    L, st = _lib.lib(), D.stream_ptr()
+    offs = torch.empty((2, nwin + 1), dtype=torch.int64, device=dev)
+    _lib.check(L.slk_letter_edits_count(win_off.data_ptr(), w0.data_ptr(), w1.data_ptr(), nwin, G, kmer_len, mask, margin,
+                                        offs[0].data_ptr(), offs[1].data_ptr(), st), "letter_edits_count")
+    offs = torch.cumsum(offs, 1)
+    host = offs.cpu().numpy()                                     # the round trip: the totals (and the per-window counts with them)
+    ncand, npos = int(host[0, -1]), int(host[1, -1])
+    c = types.SimpleNamespace(cand_off=offs[0], pos_off=offs[1], cand_off_host=host[0].copy(), pos_off_host=host[1].copy(), ncand=ncand,
+                              npos=npos)
+    c.cand_pair = torch.empty(max(ncand, 1), dtype=torch.int32, device=dev)
+    c.cand_start, c.cand_ndel = torch.empty_like(c.cand_pair), torch.empty_like(c.cand_pair)
+    c.cand_edit = torch.empty(max(ncand, 1), dtype=torch.int64, device=dev)
+    new_off = torch.zeros(ncand + 1, dtype=torch.int64, device=dev)
+    head = (genome.data_ptr(), G, win_off.data_ptr(), w0.data_ptr(), w1.data_ptr(), minus.data_ptr(), nwin, kmer_len)
+    _lib.check(L.slk_letter_edits_emit(*head, mask, margin, c.cand_off.data_ptr(), ncand, c.cand_pair.data_ptr(), c.cand_start.data_ptr(),
+                                       c.cand_ndel.data_ptr(), new_off.data_ptr(), c.cand_edit.data_ptr(), st), "letter_edits_emit")
+    c.cand_new_off = torch.cumsum(new_off, 0)
+    cap = max(ncand * (kmer_len + 1), 1)                          # (no second round trip for the exact total)
+    c.cand_new = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+    _lib.check(L.slk_letter_edits_new(*head, int(blank), mask, margin, c.cand_off.data_ptr(), ncand, c.cand_start.data_ptr(),
+                                      c.cand_new_off.data_ptr(), cap, c.cand_new.data_ptr(), st), "letter_edits_new")
+    c.seq = torch.empty(max(npos, 1), dtype=torch.int32, device=dev)
+    _lib.check(L.slk_polish_window_kmers(*head, int(blank), c.pos_off.data_ptr(), npos, c.seq.data_ptr(), st), "polish_window_kmers")
+    c.cand_pair, c.cand_start, c.cand_ndel, c.cand_edit = c.cand_pair[:ncand], c.cand_start[:ncand], c.cand_ndel[:ncand], c.cand_edit[:ncand]
+    return c
+
+
+def sum_gains(score, ll_edit, cand_read, cand_edit, region_start, P, gain=None, support=None):
+    """The reads' gains on genome coordinates (slk_polish_sum_gains_f64): per cell (position, slot) of the packed positions
+    [region_start, region_start + P) the sum of ll_edit - score[cand_read] over the candidates of that edit, taken one after the
+    other in read order (the sort by (edit, read) is torch's, the walk the kernel's), and the number of reads counted.  Only
+    candidates whose two values are finite count; a NaN of either makes the cell NaN.  gain, support: tables to go on from (added to
+    in place) -- batches that come in read order give the bits of one call.  -> (gain float64 [P, 8], support int32 [P, 8])."""
+    import torch
+    from . import _lib, device as D
+    dev = score.device
+    P, ncand = int(P), int(ll_edit.numel())
+    if gain is None:
+        gain = torch.zeros((max(P, 1), 8), dtype=torch.float64, device=dev)
+        support = torch.zeros((max(P, 1), 8), dtype=torch.int32, device=dev)
+    if cand_read.numel() != ncand or cand_edit.numel() != ncand or cand_read.dtype != torch.int32 or cand_edit.dtype != torch.int64 or \
+            score.dtype != torch.float64 or ll_edit.dtype != torch.float64:
+        raise ValueError("sum_gains needs one int32 read, one int64 edit and one float64 value per candidate, and float64 scores")
+    if ncand and P:
+        by_read = torch.sort(cand_read, stable=True).indices
+        order = by_read[torch.sort(cand_edit[by_read], stable=True).indices].contiguous()
+        _lib.check(_lib.lib().slk_polish_sum_gains_f64(score.data_ptr(), int(score.numel()), ll_edit.contiguous().data_ptr(),
+                                                       cand_read.contiguous().data_ptr(), cand_edit.contiguous().data_ptr(),
+                                                       order.data_ptr(), ncand, int(region_start), P, gain.data_ptr(),
+                                                       support.data_ptr(), D.stream_ptr()), "polish_sum_gains")
+    return gain[:P], support[:P]
+
+
+def read_windows(paths, lens, move_row, steps, ops, strand, info, index, kmer_len, keep=None):
+    """Each mapped read's alignment and its call's moves put together (slk_polish_read_windows; design/polish_genome.md 1): paths, lens,
+    move_row as decode.viterbi_marginals_batch / call_reads_qual return them, steps the int32 device tensor of the reads' posterior
+    rows, ops / strand / info what Index.map_paths(ops=True) returned for those calls.  keep: bool mask of the reads to use.
+    -> namespace of host arrays status int32 [B] (READ_REASONS), span int32 [B, 2] (the posterior rows [r0, r1) of the aligned part),
+    window int64 [B, 2] ([w0, w1) in contig coordinates), contig, and the device tensors center (int32) and center_off (int64
+    [B + 1]): read b's r1 - r0 + 1 centre values start at center_off[b].  A read that is unmapped, not kept or refused has its
+    status and nothing else."""
+    import types
+    import torch
+    from . import _lib, device as D
+    _check_kmer_len(kmer_len)
+    B = len(ops)
+    if paths.shape[0] != B or lens.numel() != B or move_row.shape[0] != B or steps.numel() != B or len(strand) != B:
+        raise ValueError("read_windows: %d alignments but %d calls" % (B, paths.shape[0]))
+    if len(ops.parts) != 1:
+        raise ValueError("read_windows takes the columns of Index.map_paths (one reference buffer)")
+    if paths.dtype != torch.int32 or move_row.dtype != torch.int32 or paths.stride(1) != 1 or move_row.stride(1) != 1:
+        raise ValueError("read_windows: paths and move_row are int32 device tensors [reads, positions]")
+    dev = ops.codes_dev.device
+    contig = np.asarray(info['contig'], dtype=np.int64)
+    mapped = contig >= 0
+    kept = np.ones(B, dtype=bool) if keep is None else np.asarray(keep, dtype=bool)
+    if kept.shape != (B,):
+        raise ValueError("read_windows: keep= is a mask of %d reads, not of %d" % (kept.size, B))
+    ref, roff, rows_d, tb_d = ops.parts[0]
+    minus = np.asarray(strand) == '-'
+    coff = np.where(mapped, index.offsets[np.where(mapped, contig, 0)], 0).astype(np.int64)
+    wstart = np.where(mapped, np.asarray(info['window_start'], dtype=np.int64), 0)
+    steps_h = steps.cpu().numpy().astype(np.int64)
+    coff_h = np.concatenate([[0], np.cumsum(steps_h + 1)]).astype(np.int64)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    out = types.SimpleNamespace(contig=contig, center_off=up(coff_h), center_off_host=coff_h, steps_host=steps_h)
+    out.center = torch.zeros(int(coff_h[-1]), dtype=torch.int32, device=dev)
+    st_d = torch.zeros(B, dtype=torch.int32, device=dev)
+    span_d = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+    win_d = torch.zeros((B, 2), dtype=torch.int64, device=dev)
+    lrow = torch.empty((max(B, 1), max(int(ops.ldq), 1)), dtype=torch.int32, device=dev)
+    T = min(int(paths.shape[1]), int(move_row.shape[1]))
+    if B:
+        minus_d, keep_d, ws_d, co_d = up(minus.astype(np.int32)), up((kept & mapped).astype(np.uint8)), up(wstart), up(coff)
+        steps_d = steps.to(dev).to(torch.int32).contiguous()
+        _lib.check(_lib.lib().slk_polish_read_windows(
+            paths.data_ptr(), paths.stride(0), lens.data_ptr(), move_row.data_ptr(), move_row.stride(0), T, steps_d.data_ptr(),
+            ops.qlen.data_ptr(), ops.ldq, roff.data_ptr(), rows_d.data_ptr(), ops.codes_dev.data_ptr(), ops.offsets_dev.data_ptr(),
+            ops.codes_dev.numel(), tb_d.data_ptr(), minus_d.data_ptr(), keep_d.data_ptr(), ws_d.data_ptr(), co_d.data_ptr(), index.G, B,
+            int(kmer_len), out.center_off.data_ptr(), lrow.data_ptr(), st_d.data_ptr(), span_d.data_ptr(), win_d.data_ptr(),
+            out.center.data_ptr(), D.stream_ptr()), "polish_read_windows")
+    out.status = st_d.cpu().numpy()
+    out.status[~mapped] = READ_UNMAPPED
+    out.status[mapped & ~kept] = READ_NOT_KEPT
+    out.span, out.window, out.minus = span_d.cpu().numpy(), win_d.cpu().numpy(), minus
+    out.contig_off = coff
+    return out
+
+
+class GenomeRescored(object):
+    """What the signal of the mapped reads says about every single-letter edit of a genome (rescore_genome).
+
+    gain float64, support int32: device tensors [P, 8], the cells of the packed positions lo .. lo + P - 1: slots 0-2 the substitutions
+    in alphabet order without the draft's letter, 3 the deletion, 4-7 the insertions of A C G T in FRONT of the position.  gain is
+    the sum over the reads that scored the edit of (log-likelihood of the edited window - that of the window), support their number;
+    NaN where a read's candidate was refused.  status: host int32 per read, READ_DONE or why it was left out (READ_REASONS); score:
+    device float64 per read, its window's banded score (NaN for a read left out); span, window: host arrays per read, the rows
+    [r0, r1) it was scored on and its window [w0, w1) in contig coordinates.  cand_read (int32), cand_edit (int64), ll_edit
+    (float64): the candidates behind the sums, on the device."""
+
+    def __init__(self, index, lo, P, kmer_len, gain, support, status, score, span, window, cand_read, cand_edit, ll_edit):
+        self.index, self.lo, self.P, self.kmer_len, self.gain, self.support = index, int(lo), int(P), int(kmer_len), gain, support
+        self.status, self.score, self.span, self.window = status, score, span, window
+        self.cand_read, self.cand_edit, self.ll_edit = cand_read, cand_edit, ll_edit
+        self._genome = None
+
+    def cell_of(self, contig, pos, kind, letter=''):
+        """(row of gain / support, slot) of an edit: kind 'sub' puts `letter` at pos, 'del' removes the letter there, 'ins' puts
+        `letter` in front of pos (pos = the contig's length: behind its end).  ValueError outside the region."""
+        ix = self.index
+        c = ix.names.index(contig) if not isinstance(contig, (int, np.integer)) else int(contig)
+        p = int(ix.offsets[c]) + int(pos)
+        if not self.lo <= p < self.lo + self.P or pos < 0 or p > int(ix.offsets[c + 1]):
+            raise ValueError("position %r of contig %r lies outside the rescored region" % (pos, contig))
+        if kind == 'del':
+            return p - self.lo, 3
+        a = 'ACGT'.index(letter)
+        if kind == 'ins':
+            return p - self.lo, 4 + a
+        if kind != 'sub':
+            raise ValueError("unknown kind of edit %r" % (kind,))
+        d = 'ACGT'.find(self._letters()[p - self.lo])
+        if a == d:
+            raise ValueError("a substitution by the letter that stands there is no edit")
+        return p - self.lo, a - (1 if d >= 0 and a > d else 0)
+
+    def _letters(self):
+        if self._genome is None:
+            self._genome = self.index.genome[self.lo:self.lo + self.P].cpu().numpy().tobytes().decode('ascii')
+        return self._genome
+
+    def edit_of(self, position, slot):
+        """(contig name, position within the contig, kind, letter) of a cell: position a row of gain / support."""
+        ix = self.index
+        p = self.lo + int(position)
+        c = ix.contig_of(p) if p < ix.G else len(ix.names) - 1
+        pos = p - int(ix.offsets[c])
+        if slot == 3:
+            return ix.names[c], pos, 'del', ''
+        if slot > 3:
+            return ix.names[c], pos, 'ins', 'ACGT'[slot - 4]
+        d = 'ACGT'.find(self._letters()[int(position)])
+        return ix.names[c], pos, 'sub', [x for i, x in enumerate('ACGT') if i != d][slot]
+
+    def cells(self, min_gain=None, min_support=0):
+        """The cells with support >= min_support and, when given, gain > min_gain, chosen on the device and fetched alone:
+        -> [(contig, pos, kind, letter, gain, support)] in cell order."""
+        import torch
+        mask = self.support >= max(int(min_support), 0)
+        if min_gain is not None:
+            mask = mask & (self.gain > float(min_gain))            # (a NaN cell compares false)
+        hit = mask.reshape(-1).nonzero().reshape(-1)
+        g, s = self.gain.reshape(-1)[hit].cpu().numpy(), self.support.reshape(-1)[hit].cpu().numpy()
+        return [self.edit_of(int(h) // 8, int(h) % 8) + (float(gv), int(sv)) for h, gv, sv in zip(hit.cpu().numpy(), g, s)]
+
+    def edits(self):
+        """Every cell a read scored: rows (contig, pos, kind, letter, gain, support)."""
+        return self.cells(None, 1)
+
+    def top(self, n=10):
+        """The n cells of largest gain among those a read scored."""
+        return sorted((r for r in self.edits() if r[4] == r[4]), key=lambda r: (-r[4], r[0], r[1]))[:int(n)]
+
+
+def rescore_genome(post, steps, paths, lens, move_row, index, res, strand, info, ops, kmer_len, width=512, margin=None,
+                   kinds=bio.EDIT_KINDS, keep=None, region=None, blank=0, min_prob=None, workspace_limit=None):
+    """Score every single-letter edit of a genome under the signal of the reads mapped to it, and sum on genome coordinates.
+
+    post: the reads' posterior [T', B, states] on the device (float32 or float64), steps: int32 device tensor of each read's rows;
+    paths, lens, move_row: the reads' calls (decode.viterbi_marginals_batch); index: the genome.Index the calls were mapped to, and
+    res, strand, info, ops what index.map_paths(paths, lens, kmer_len, ops=True) returned.  Each read's draft is the window of its
+    contig that its alignment covers, on its own strand, its rows those of the aligned part, its band `width` states round the
+    centre line taken through the alignment (read_windows); its candidates are made on the device (letter_edits) at least `margin`
+    letters (default 2 kmer_len: both ends of a window are pinned by the global recursion, so edits near them are not that read's to
+    judge) from the window's ends, scored by the banded entry as it is (decode.rescore_edits_banded_device) and summed in read order
+    (sum_gains).  keep: bool mask of the reads to use (info['edge'] == 0 is the usual filter).  region: (contig, start, end) or None
+    for the whole genome: the cells to sum; a slice gives the slice of the whole.  A read that is unmapped, fails keep or whose band
+    cannot be laid is reported in `status`, never raised.  -> GenomeRescored."""
+    import torch
+    from . import genome as G
+    _check_kmer_len(kmer_len)
+    if post.dim() != 3 or int(post.shape[2]) != 4 ** kmer_len + 1:
+        raise ValueError("rescore_genome takes a [rows, reads, %d] transducer posterior of %d-mers" % (4 ** kmer_len + 1, kmer_len))
+    B = int(post.shape[1])
+    if len(ops) != B or len(res) != B:
+        raise ValueError("rescore_genome: %d reads in the posterior, %d alignments" % (B, len(ops)))
+    margin = 2 * int(kmer_len) if margin is None else int(margin)
+    pd = post if post.is_contiguous() else post.contiguous()
+    dev = pd.device
+    lo, P = G.region_span(index, region)
+    w = read_windows(paths, lens, move_row, steps, ops, strand, info, index, kmer_len, keep)
+    reads = np.flatnonzero(w.status == READ_DONE)
+    score = torch.full((B,), float('nan'), dtype=torch.float64, device=dev)
+    empty = lambda dt: torch.zeros(0, dtype=dt, device=dev)
+    if not len(reads):
+        gain, support = sum_gains(score, empty(torch.float64), empty(torch.int32), empty(torch.int64), lo, P)
+        return GenomeRescored(index, lo, P, kmer_len, gain, support, w.status, score, w.span, w.window, empty(torch.int32),
+                              empty(torch.int64), empty(torch.float64))
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    reads_d = up(reads.astype(np.int64))
+    c = letter_edits(index.genome, up(w.contig_off[reads]), up(w.window[reads, 0]), up(w.window[reads, 1]), up(w.minus[reads].astype(np.int32)),
+                     kmer_len, blank, kinds, margin)
+    # the bands: centre - width / 2 clamped to [0, max(0, L + 1 - width)]; the centre does not decrease, so neither does the band
+    nrow = (w.span[reads, 1] - w.span[reads, 0]).astype(np.int64)
+    npos = np.diff(c.pos_off_host)
+    src = up(np.repeat(w.center_off_host[reads] - np.concatenate([[0], np.cumsum(nrow + 1)])[:-1], nrow + 1)) + \
+        torch.arange(int((nrow + 1).sum()), device=dev)
+    top = up(np.repeat(np.maximum(npos + 1 - int(width), 0), nrow + 1))
+    band = torch.minimum(torch.clamp(w.center[src].to(torch.int64) - int(width) // 2, min=0), top).to(torch.int32)
+    row_off = reads.astype(np.int64) + w.span[reads, 0].astype(np.int64) * B
+    sc, ll = decode.rescore_edits_banded_device(pd, row_off, B, nrow.astype(np.int32), c.seq, c.pos_off, band, width, c.cand_off_host,
+                                                c.cand_pair, c.cand_start, c.cand_ndel, c.cand_new_off, c.cand_new, blank=blank,
+                                                min_prob=min_prob, workspace_limit=workspace_limit)
+    score[reads_d] = sc
+    cand_read = reads_d[c.cand_pair.to(torch.int64)].to(torch.int32)
+    gain, support = sum_gains(score, ll, cand_read, c.cand_edit, lo, P)
+    return GenomeRescored(index, lo, P, kmer_len, gain, support, w.status, score, w.span, w.window, cand_read, c.cand_edit, ll)
+
+
+#: per contig: `sequence` the polished string; `applied` rows (round, pos, kind, letter, gain, support), positions in the contig's
+#: string of that round; `rounds` the rounds that applied something to it
+GenomePolished = collections.namedtuple("GenomePolished", "name sequence applied rounds")
+
+
+def letter_triple(seq, kind, pos, letter, kmer_len):
+    """(start, ndel, new k-mer states) of a single-letter edit of a base string, as bio.edit_states gives it for the spelled-out
+    strings, from the letters round the edit alone: two edits that spell the same string have the same triple."""
+    text = bio.apply_letter_edits(seq, [(kind, pos, letter)])
+    n, n2, k = len(seq), len(text), int(kmer_len)
+    m = min(n, n2)
+    # the first letter at which the strings differ read from the front, the last of `seq` at which they differ read from the back
+    front = next((i for i in range(max(pos - 1, 0), m) if seq[i] != text[i]), None)
+    back = next((j for j in range(min(pos, n - 1), n - m - 1, -1) if seq[j] != text[j + n2 - n]), None)
+    nold, nnew = n - k + 1, n2 - k + 1
+    nmin = min(nold, nnew)
+    pre = nmin if front is None else min(max(front - k + 1, 0), nmin)
+    rest = nmin - pre
+    suf = rest if back is None else min(max(nold - 1 - back, 0), rest)
+    new = bio.seq_to_states(text[pre:nnew - suf + k - 1], k) if nnew - suf > pre else np.zeros(0, dtype=np.int64)
+    return pre, nold - pre - suf, tuple(int(v) for v in new)
+
+
+def accept_genome_edits(cells, text, kmer_len):
+    """One round's choice among the fetched cells (contig, pos, kind, letter, gain, support): accept_edits' order, (-gain, pos, kind,
+    letter), and its spacing, at least kmer_len letters from every edit already taken on the same contig; a cell whose triple
+    (letter_triple on the contig's string) an earlier cell of the round had is that edit again and is passed over."""
+    rank = dict((k, i) for i, k in enumerate(bio.EDIT_KINDS))
+    taken, seen = [], set()
+    for r in sorted(cells, key=lambda r: (-r[4], r[0], r[1], rank[r[2]], r[3])):
+        key = (r[0],) + letter_triple(text[r[0]], r[2], r[1], r[3], kmer_len)
+        if key in seen:
+            continue
+        seen.add(key)
+        if all(t[0] != r[0] or abs(t[1] - r[1]) >= kmer_len for t in taken):
+            taken.append(r)
+    return taken
+
+
+def polish_genome(post, steps, paths, lens, move_row, index, kmer_len, width=512, margin=None, kinds=bio.EDIT_KINDS, keep=None,
+                  min_gain=0.0, min_support=2, max_rounds=4, blank=0, min_prob=None, workspace_limit=None, map_kwargs=None):
+    """Greedy polishing of a genome against the signal of the reads mapped to it.  Per round: the calls are mapped onto the current
+    strings (index.map_paths(ops=True, **map_kwargs); the first round on `index` itself), rescore_genome sums the gains, the cells
+    with gain > min_gain and support >= min_support are chosen on the device and fetched alone, accept_genome_edits takes them
+    greedily, they are applied, and the next round's Index is built from the new strings (same k, bin_width, max_occ).  The
+    posterior is computed once by the caller; nothing shifts windows arithmetically.  It stops when a round takes nothing.
+    keep: None, a bool mask of the reads, or a function (res, strand, info) -> mask evaluated on every round's mapping.
+    -> ([GenomePolished] in the index's contig order, the last round's GenomeRescored)."""
+    from . import genome as G
+    kw = dict(map_kwargs or {})
+    host = index.genome.cpu().numpy().tobytes().decode('ascii')
+    text = collections.OrderedDict((n, host[int(a):int(b)]) for n, a, b in zip(index.names, index.offsets[:-1], index.offsets[1:]))
+    applied = dict((n, []) for n in text)
+    rounds = dict((n, 0) for n in text)
+    ix, last = index, None
+    for r in range(int(max_rounds)):
+        got = ix.map_paths(paths, lens, kmer_len, ops=True, **kw)
+        res, strand, info, ops = got[0], got[1], got[2], got[4]
+        mask = keep(res, strand, info) if callable(keep) else keep
+        last = rescore_genome(post, steps, paths, lens, move_row, ix, res, strand, info, ops, kmer_len, width=width, margin=margin,
+                              kinds=kinds, keep=mask, blank=blank, min_prob=min_prob, workspace_limit=workspace_limit)
+        taken = accept_genome_edits(last.cells(min_gain, min_support), text, kmer_len)
+        if not taken:
+            break
+        for name in text:
+            mine = [t for t in taken if t[0] == name]
+            if mine:
+                text[name] = bio.apply_letter_edits(text[name], [(t[2], t[1], t[3]) for t in mine])
+                applied[name].extend((r, t[1], t[2], t[3], t[4], t[5]) for t in mine)
+                rounds[name] += 1
+        ix = G.Index(list(text.items()), k=index.k, bin_width=index.bin_width, max_occ=index.max_occ)
+    return [GenomePolished(n, text[n], applied[n], rounds[n]) for n in text], last
