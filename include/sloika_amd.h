@@ -1193,6 +1193,69 @@ SLK_API int slk_polish_sum_gains_f64(const double *score, int nread, const doubl
                                      const int64_t *cand_edit, const int64_t *order, int64_t ncand, int64_t region_start, int64_t P,
                                      double *gain, int32_t *support, slk_stream_t stream);
 
+/* f10d. Proposed variants of any length on genome coordinates (csrc/polish_variants.hip; design/polish_variants.md section 1 DEFINES
+ * the variant, a window's candidates and their order, the triple, the sum and the repeat-unit proposals, and is not repeated here).
+ *   A variant list is var_off:[V] int64 (the packed position of the variant's contig), var_pos:[V] int64 (within the contig),
+ *     var_ndel:[V] int32, var_alt_off:[V + 1] int64 into var_alt:[A] uint8 letters, SORTED by (var_off, var_pos); contig_off:
+ *     [ncontig + 1] device int64, the contigs' packed starts and G.  All of it is device data and is not trusted: no address and no
+ *     loop bound depends on an unchecked value (a list that is not sorted gives some of its fitting variants, never a bad access).
+ *   slk_variant_edits_count: var_status:[V] int32 <- SLK_VARIANT_OK or a negative SLK_VARIANT_* code; a refused variant gets no
+ *     candidate anywhere and nothing of it is read beyond the check.  Then, one wave per window (win_off, w0, w1 as
+ *     slk_letter_edits_count), ncand:[nwin + 1] and nkmer:[nwin + 1] int64 with entry 0 zero and entry b + 1 the candidates (the
+ *     variants of the window's contig with w0 + margin <= var_pos, var_pos + var_ndel <= w1 - margin and a k-mer left) and the k-mers
+ *     of window b.  An inclusive prefix sum in place makes them cand_off and pos_off.  kmer_len 3 .. SLK_RESCORE_MAX_NEW - 1.
+ *   slk_variant_edits_emit: one wave per window, the count pass's walk; per candidate cand_pair (its window), cand_start, cand_ndel,
+ *     cand_var (the index into the sorted list) and the NUMBER of its new symbols in cand_new_off[i + 1] (cand_new_off[0] = 0).
+ *     Within a '+' window by ascending variant, within a '-' window (minus:[nwin] int32) by descending.  Entries of a window's share
+ *     of cand_off beyond its own count get start -1 and cand_var -1, which the scoring entries refuse with NaN.
+ *   slk_variant_edits_new: one thread per candidate, the new symbols (posterior columns, state + (state >= blank); -1 for a k-mer with
+ *     a letter that is none of A C G T) behind the summed cand_new_off; new_cap: the entries cand_new holds (ncand *
+ *     SLK_RESCORE_MAX_NEW always suffices).  The windows' own columns are slk_polish_window_kmers'.
+ *   slk_polish_sum_variant_gains_f64: order:[ncand] device int64, the candidates sorted by (cand_var, cand_read) -- the caller's sort;
+ *     read_minus:[nread] int32.  Adds into gain, support, pro:[V] and gain_strand, support_strand, pro_strand:[V][2] ('+' 0, '-' 1 by
+ *     the scoring read's strand): per cell, continuing from what it holds, ll_edit - score[cand_read] of its candidates in that order
+ *     when both are finite, their number, and how many were > 0; a NaN of either value makes the total's and that strand's gain NaN.
+ *     One thread walks a variant: no floating-point atomics, no bit depends on the launch.
+ *   slk_repeat_variants_count / _emit: one thread per packed position of [lo, lo + P).  nprop, nalt:[P + 1] int64 with entry 0 zero
+ *     and entry t + 1 the proposals and their alt letters at position lo + t; summed in place they are prop_off and alt_off, and the
+ *     emit pass writes the V = prop_off[P] variants and A = alt_off[P] letters in the list's layout, sorted as they come.  max_unit
+ *     1 .. 4, max_change 1 .. 8, min_copies >= 2.  Offsets that are not a position's own counts are not followed.                   */
+#define SLK_VARIANT_OK 0
+#define SLK_VARIANT_CONTIG (-1)    /* var_off is no contig's start                                                       */
+#define SLK_VARIANT_SPAN (-2)      /* var_pos negative, or [var_pos, var_pos + var_ndel) not inside the contig           */
+#define SLK_VARIANT_NDEL (-3)      /* a negative var_ndel                                                                */
+#define SLK_VARIANT_ALT (-4)       /* the alt slice descends, leaves var_alt or has more than MAX_NEW - kmer_len + 1     */
+#define SLK_VARIANT_EMPTY (-5)     /* nothing deleted and nothing put in                                                 */
+#define SLK_VARIANT_SAME (-6)      /* the alt is the letters that stand there                                            */
+SLK_API int slk_variant_edits_count(const uint8_t *genome, long G, const int64_t *contig_off, int ncontig, const int64_t *var_off,
+                                    const int64_t *var_pos, const int32_t *var_ndel, const int64_t *var_alt_off,
+                                    const uint8_t *var_alt, int64_t V, int64_t A, const int64_t *win_off, const int64_t *w0,
+                                    const int64_t *w1, int nwin, int kmer_len, int margin, int32_t *var_status, int64_t *ncand,
+                                    int64_t *nkmer, slk_stream_t stream);
+SLK_API int slk_variant_edits_emit(const uint8_t *genome, long G, const int64_t *var_off, const int64_t *var_pos,
+                                   const int32_t *var_ndel, const int64_t *var_alt_off, const uint8_t *var_alt, int64_t V, int64_t A,
+                                   const int32_t *var_status, const int64_t *win_off, const int64_t *w0, const int64_t *w1,
+                                   const int32_t *minus, int nwin, int kmer_len, int margin, const int64_t *cand_off, int64_t ncand,
+                                   int32_t *cand_pair, int32_t *cand_start, int32_t *cand_ndel, int32_t *cand_var,
+                                   int64_t *cand_new_off, slk_stream_t stream);
+SLK_API int slk_variant_edits_new(const uint8_t *genome, long G, const int64_t *var_off, const int64_t *var_pos,
+                                  const int32_t *var_ndel, const int64_t *var_alt_off, const uint8_t *var_alt, int64_t V, int64_t A,
+                                  const int32_t *var_status, const int64_t *win_off, const int64_t *w0, const int64_t *w1,
+                                  const int32_t *minus, int nwin, int kmer_len, int blank, int margin, int64_t ncand,
+                                  const int32_t *cand_pair, const int32_t *cand_start, const int32_t *cand_var,
+                                  const int64_t *cand_new_off, int64_t new_cap, int32_t *cand_new, slk_stream_t stream);
+SLK_API int slk_polish_sum_variant_gains_f64(const double *score, const int32_t *read_minus, int nread, const double *ll_edit,
+                                             const int32_t *cand_read, const int32_t *cand_var, const int64_t *order, int64_t ncand,
+                                             int64_t V, double *gain, int32_t *support, int32_t *pro, double *gain_strand,
+                                             int32_t *support_strand, int32_t *pro_strand, slk_stream_t stream);
+SLK_API int slk_repeat_variants_count(const uint8_t *genome, long G, const int64_t *contig_off, int ncontig, int64_t lo, int64_t P,
+                                      int kmer_len, int max_unit, int max_change, int min_copies, int64_t *nprop, int64_t *nalt,
+                                      slk_stream_t stream);
+SLK_API int slk_repeat_variants_emit(const uint8_t *genome, long G, const int64_t *contig_off, int ncontig, int64_t lo, int64_t P,
+                                     int kmer_len, int max_unit, int max_change, int min_copies, const int64_t *prop_off,
+                                     const int64_t *alt_off, int64_t V, int64_t A, int64_t *var_off, int64_t *var_pos,
+                                     int32_t *var_ndel, int64_t *var_alt_off, uint8_t *var_alt, slk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

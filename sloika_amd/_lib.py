@@ -195,6 +195,16 @@ PROTOTYPES = {
     "slk_letter_edits_new": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp]),
     "slk_polish_window_kmers": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, C.c_int64, _vp, _vp]),
     "slk_polish_sum_gains_f64": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp]),
+    "slk_variant_edits_count": (_i, [_vp, _l, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _i, _i, _i, _vp, _vp,
+                                     _vp, _vp]),
+    "slk_variant_edits_emit": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp,
+                                    C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "slk_variant_edits_new": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
+                                   C.c_int64, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
+    "slk_polish_sum_variant_gains_f64": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "slk_repeat_variants_count": (_i, [_vp, _l, _vp, _i, C.c_int64, C.c_int64, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "slk_repeat_variants_emit": (_i, [_vp, _l, _vp, _i, C.c_int64, C.c_int64, _i, _i, _i, _i, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp,
+                                      _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

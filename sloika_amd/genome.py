@@ -724,8 +724,14 @@ class Consensus(object):
         made on.  Each row gets three more values: gain (float), support (int) and single (bool).  A substitution, a deletion and an
         insertion of one letter are one of the 8 cells of their position -- an insertion BEHIND position p is the insertion in front
         of p + 1 --; an insertion of more letters is not a single-letter edit: gain None, support 0, single False.  A variant outside
-        the rescored region has gain None and support 0 as well, with single True."""
+        the rescored region has gain None and support 0 as well, with single True.
+
+        `rescored` may also be a polish.GenomeVariantsRescored of the variants `proposals()` returns, in that order
+        (design/polish_variants.md): every row then gets the gain and support of its own variant -- an insertion of several letters
+        too, and every row of a run of deleted positions those of the run's one deletion --, with `single` as above."""
         import torch
+        if hasattr(rescored, 'variants'):
+            return self._join_proposals(rescored)
         ix = self.pileup.index
         if rescored.index is not ix:
             raise ValueError("genome: polish_variants needs reads rescored against the index the pileup was made on")
@@ -755,6 +761,26 @@ class Consensus(object):
                 k += 1
         return out
 
+    def proposals(self, max_alt=None):
+        """The rows of variants() as variants (contig, pos, ndel, alt) for polish.rescore_variants (proposals_of): a substitution is
+        (pos, 1, alt), a run of consecutive 'del' rows of one contig one (pos, run, ''), an 'ins' BEHIND p is (p + 1, 0, alt).
+        max_alt: leave out insertions of more letters (polish.max_alt(kmer_len) is what an edit may bring)."""
+        return proposals_of(self.variants(), max_alt)[0]
+
+    def _join_proposals(self, rescored):
+        if rescored.index is not self.pileup.index:
+            raise ValueError("genome: polish_variants needs reads rescored against the index the pileup was made on")
+        rows = self.variants()
+        mine, which = proposals_of(rows)
+        number = dict((v, i) for i, v in reversed(list(enumerate(rescored.variants.rows()))))
+        gain, support = rescored.gain.cpu().numpy(), rescored.support.cpu().numpy()
+        out = []
+        for row, w in zip(rows, which):
+            single = row[2] != 'ins' or len(row[4]) == 1
+            v = None if w is None else number.get(mine[w])
+            out.append(row + ((None, 0, single) if v is None else (float(gain[v]), int(support[v]), single)))
+        return out
+
     def summary(self):
         """dict: `covered` (positions called, i.e. not FLAG_LOW), `substitutions`, `deleted` and `inserted` letters against the
         genome, and `identity` = 1 - their sum / covered (nan without a covered position)."""
@@ -769,6 +795,36 @@ class Consensus(object):
                 ins += len(alt)
         return {'covered': covered, 'substitutions': sub, 'deleted': dele, 'inserted': ins,
                 'identity': 1.0 - float(sub + dele + ins) / covered if covered else float('nan')}
+
+
+def proposals_of(rows, max_alt=None):
+    """Rows of Consensus.variants() -> (variants [(contig, pos, ndel, alt)] in row order, per row the number of its variant or None).
+    'sub' at p: (p, 1, alt); 'del' rows that follow one another in the list at consecutive positions of one contig: one (first
+    position, run, ''); 'ins' BEHIND p: (p + 1, 0, alt), left out (None) when it has more than max_alt letters."""
+    out, which = [], []
+    run = None                                                       # (contig, next position) of the deletion being gathered
+    for row in rows:
+        name, pos, kind, alt = row[0], int(row[1]), row[2], row[4]
+        if kind == 'del' and run == (name, pos):
+            out[-1] = (name, out[-1][1], out[-1][2] + 1, '')
+            which.append(len(out) - 1)
+            run = (name, pos + 1)
+            continue
+        run = None
+        if kind == 'ins' and max_alt is not None and len(alt) > max_alt:
+            which.append(None)
+            continue
+        if kind == 'del':
+            out.append((name, pos, 1, ''))
+            run = (name, pos + 1)
+        elif kind == 'sub':
+            out.append((name, pos, 1, alt))
+        elif kind == 'ins':
+            out.append((name, pos + 1, 0, alt))
+        else:
+            raise ValueError("genome: unknown kind of variant %r" % (kind,))
+        which.append(len(out) - 1)
+    return out, which
 
 
 def _deletion_wins(cn, ref):

@@ -544,18 +544,36 @@ class Basecaller(object):
                                          margin=margin, kinds=kinds, keep=mask, region=region, blank=0, min_prob=self.min_prob,
                                          workspace_limit=workspace_limit)
 
+    def rescore_variants(self, signals, index, variants, width=512, margin=None, keep=None, trim=(0, 0), open_pore_fraction=0.0,
+                         scaling=None, workspace_limit=None, **map_kwargs):
+        """What the signal of whole reads says about proposed variants of any length (design/polish_variants.md): rescore_genome's
+        calls, mapping and windows, each variant -- (contig, pos, ndel, alt) rows, a polish.VariantSet or 'repeats' -- put to every
+        read that covers it as ONE hypothesis (polish.rescore_variants).  keep as rescore_genome.
+        -> polish.GenomeVariantsRescored."""
+        from . import polish
+        with self._scope():
+            post, steps, paths, lens, move_row = self._genome_reads(signals, trim, open_pore_fraction, scaling, "rescore_variants")
+            got = index.map_paths(paths, lens, self.kmer_len, ops=True, **map_kwargs)
+            res, strand, info, ops = got[0], got[1], got[2], got[4]
+            mask = keep(res, strand, info) if callable(keep) else keep
+            return polish.rescore_variants(post, steps, paths, lens, move_row, index, res, strand, info, ops, self.kmer_len, variants,
+                                           width=width, margin=margin, keep=mask, blank=0, min_prob=self.min_prob,
+                                           workspace_limit=workspace_limit)
+
     def polish_genome(self, signals, index, width=512, margin=None, kinds=('sub', 'del', 'ins'), keep=None, min_gain=0.0,
                       min_support=2, max_rounds=4, trim=(0, 0), open_pore_fraction=0.0, scaling=None, workspace_limit=None,
-                      **map_kwargs):
+                      proposals=None, **map_kwargs):
         """polish.polish_genome on whole reads: one network pass and one decode, then rounds of mapping the same calls onto the
         current strings, rescore_genome's sums and the edits the signal prefers.  `index` may be the reference or
-        genome.Index(dict(consensus.sequences())).  -> ([polish.GenomePolished] per contig, the last round's polish.GenomeRescored)."""
+        genome.Index(dict(consensus.sequences())).  -> ([polish.GenomePolished] per contig, the last round's polish.GenomeRescored).
+        proposals: as polish.polish_genome takes it (variants of any length beside the cells; a third value is then returned)."""
         from . import polish
         with self._scope():
             post, steps, paths, lens, move_row = self._genome_reads(signals, trim, open_pore_fraction, scaling, "polish_genome")
+            more = {} if proposals is None else {'proposals': proposals}
             return polish.polish_genome(post, steps, paths, lens, move_row, index, self.kmer_len, width=width, margin=margin,
                                         kinds=kinds, keep=keep, min_gain=min_gain, min_support=min_support, max_rounds=max_rounds,
-                                        blank=0, min_prob=self.min_prob, workspace_limit=workspace_limit, map_kwargs=map_kwargs)
+                                        blank=0, min_prob=self.min_prob, workspace_limit=workspace_limit, map_kwargs=map_kwargs, **more)
 
     def _sequence_columns(self, chunks, sequences, who, what):
         """The posterior columns of one sequence per chunk, each k-mer states or a base string (score_chunks): state + 1, column 0 is

@@ -6,6 +6,11 @@ read (decode.rescore_edits_batch: one lattice per read, T x (m + 1) cells per ca
     rescore_drafts(post, drafts, kmer_len, group=None, ...)   -> per group the edit table, the gains and the summed score
     polish(post, drafts, kmer_len, group=None, ...)           -> per group the polished string, the applied edits, rounds and score
 
+On genome coordinates (design/polish_genome.md, design/polish_variants.md):
+
+    rescore_genome(...) / polish_genome(...)                   every single-letter edit of a genome under the reads mapped to it
+    rescore_variants(..., variants)                            proposed variants of any length, each ONE hypothesis, per read and strand
+
 A posterior column is a k-mer state with the blank's column skipped: state s sits in column s + (s >= blank), which is s + 1 for this
 project's transducers (blank 0) and s for the reference's (blank last).
 """
@@ -404,6 +409,28 @@ class GenomeRescored(object):
         return sorted((r for r in self.edits() if r[4] == r[4]), key=lambda r: (-r[4], r[0], r[1]))[:int(n)]
 
 
+def _window_tensors(w, reads, dev):
+    """(win_off, w0, w1, minus) of the reads `reads` of a read_windows result, as the candidate kernels take them."""
+    import torch
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    return up(w.contig_off[reads]), up(w.window[reads, 0]), up(w.window[reads, 1]), up(w.minus[reads].astype(np.int32))
+
+
+def _read_bands(w, reads, npos, width, B, dev):
+    """The lattices of the reads `reads` of a read_windows result whose windows have npos k-mers: (nrow int64 host, band_lo int32
+    device, row_off int64 host).  The bands: centre - width / 2 clamped to [0, max(0, L + 1 - width)]; the centre does not decrease,
+    so neither does the band."""
+    import torch
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    nrow = (w.span[reads, 1] - w.span[reads, 0]).astype(np.int64)
+    src = up(np.repeat(w.center_off_host[reads] - np.concatenate([[0], np.cumsum(nrow + 1)])[:-1], nrow + 1)) + \
+        torch.arange(int((nrow + 1).sum()), device=dev)
+    top = up(np.repeat(np.maximum(npos + 1 - int(width), 0), nrow + 1))
+    band = torch.minimum(torch.clamp(w.center[src].to(torch.int64) - int(width) // 2, min=0), top).to(torch.int32)
+    row_off = reads.astype(np.int64) + w.span[reads, 0].astype(np.int64) * B
+    return nrow, band, row_off
+
+
 def rescore_genome(post, steps, paths, lens, move_row, index, res, strand, info, ops, kmer_len, width=512, margin=None,
                    kinds=bio.EDIT_KINDS, keep=None, region=None, blank=0, min_prob=None, workspace_limit=None):
     """Score every single-letter edit of a genome under the signal of the reads mapped to it, and sum on genome coordinates.
@@ -438,18 +465,9 @@ def rescore_genome(post, steps, paths, lens, move_row, index, res, strand, info,
         gain, support = sum_gains(score, empty(torch.float64), empty(torch.int32), empty(torch.int64), lo, P)
         return GenomeRescored(index, lo, P, kmer_len, gain, support, w.status, score, w.span, w.window, empty(torch.int32),
                               empty(torch.int64), empty(torch.float64))
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    reads_d = up(reads.astype(np.int64))
-    c = letter_edits(index.genome, up(w.contig_off[reads]), up(w.window[reads, 0]), up(w.window[reads, 1]), up(w.minus[reads].astype(np.int32)),
-                     kmer_len, blank, kinds, margin)
-    # the bands: centre - width / 2 clamped to [0, max(0, L + 1 - width)]; the centre does not decrease, so neither does the band
-    nrow = (w.span[reads, 1] - w.span[reads, 0]).astype(np.int64)
-    npos = np.diff(c.pos_off_host)
-    src = up(np.repeat(w.center_off_host[reads] - np.concatenate([[0], np.cumsum(nrow + 1)])[:-1], nrow + 1)) + \
-        torch.arange(int((nrow + 1).sum()), device=dev)
-    top = up(np.repeat(np.maximum(npos + 1 - int(width), 0), nrow + 1))
-    band = torch.minimum(torch.clamp(w.center[src].to(torch.int64) - int(width) // 2, min=0), top).to(torch.int32)
-    row_off = reads.astype(np.int64) + w.span[reads, 0].astype(np.int64) * B
+    reads_d = torch.from_numpy(np.ascontiguousarray(reads.astype(np.int64))).to(dev)
+    c = letter_edits(index.genome, *_window_tensors(w, reads, dev), kmer_len, blank, kinds, margin)
+    nrow, band, row_off = _read_bands(w, reads, np.diff(c.pos_off_host), width, B, dev)
     sc, ll = decode.rescore_edits_banded_device(pd, row_off, B, nrow.astype(np.int32), c.seq, c.pos_off, band, width, c.cand_off_host,
                                                 c.cand_pair, c.cand_start, c.cand_ndel, c.cand_new_off, c.cand_new, blank=blank,
                                                 min_prob=min_prob, workspace_limit=workspace_limit)
@@ -499,14 +517,25 @@ def accept_genome_edits(cells, text, kmer_len):
 
 
 def polish_genome(post, steps, paths, lens, move_row, index, kmer_len, width=512, margin=None, kinds=bio.EDIT_KINDS, keep=None,
-                  min_gain=0.0, min_support=2, max_rounds=4, blank=0, min_prob=None, workspace_limit=None, map_kwargs=None):
+                  min_gain=0.0, min_support=2, max_rounds=4, blank=0, min_prob=None, workspace_limit=None, map_kwargs=None,
+                  proposals=None):
     """Greedy polishing of a genome against the signal of the reads mapped to it.  Per round: the calls are mapped onto the current
     strings (index.map_paths(ops=True, **map_kwargs); the first round on `index` itself), rescore_genome sums the gains, the cells
     with gain > min_gain and support >= min_support are chosen on the device and fetched alone, accept_genome_edits takes them
     greedily, they are applied, and the next round's Index is built from the new strings (same k, bin_width, max_occ).  The
     posterior is computed once by the caller; nothing shifts windows arithmetically.  It stops when a round takes nothing.
     keep: None, a bool mask of the reads, or a function (res, strand, info) -> mask evaluated on every round's mapping.
-    -> ([GenomePolished] in the index's contig order, the last round's GenomeRescored)."""
+    -> ([GenomePolished] in the index's contig order, the last round's GenomeRescored).
+
+    proposals: None, or variants of any length to put to the signal beside the single-letter cells (design/polish_variants.md):
+    'repeats' (repeat_variants of every round's index), a list of (contig, pos, ndel, alt) or a VariantSet on `index` (put in the
+    first round, whose coordinates they are), or a function index -> variants evaluated on every round's index.  Each round then also runs
+    rescore_variants on the same mapping and accept_genome_variants chooses over cells and variants together; `kinds=()` leaves the
+    variants alone.  Applied variants are rows (round, pos, 'var', (ndel, alt), gain, support).
+    -> ([GenomePolished], the last round's GenomeRescored or None without kinds, the last round's GenomeVariantsRescored)."""
+    if proposals is not None:
+        return _polish_genome_variants(post, steps, paths, lens, move_row, index, kmer_len, width, margin, kinds, keep, min_gain,
+                                       min_support, max_rounds, blank, min_prob, workspace_limit, map_kwargs, proposals)
     from . import genome as G
     kw = dict(map_kwargs or {})
     host = index.genome.cpu().numpy().tobytes().decode('ascii')
@@ -531,3 +560,409 @@ def polish_genome(post, steps, paths, lens, move_row, index, kmer_len, width=512
                 rounds[name] += 1
         ix = G.Index(list(text.items()), k=index.k, bin_width=index.bin_width, max_occ=index.max_occ)
     return [GenomePolished(n, text[n], applied[n], rounds[n]) for n in text], last
+
+
+# ---- proposed variants of any length (csrc/polish_variants.hip, design/polish_variants.md) --------------------------------------------
+
+#: var_status of a variant (include/sloika_amd.h: SLK_VARIANT_*)
+VARIANT_REASONS = {
+    -1: "its contig is none of the index's", -2: "its span is not inside its contig", -3: "a negative number of deleted letters",
+    -4: "its alt has more letters than an edit may bring, or its slice of the letters is not one", -5: "it deletes nothing and puts nothing in",
+    -6: "its alt is the letters that stand there",
+}
+
+
+def max_alt(kmer_len):
+    """The most letters a variant's alt may have: its edit then has at most SLK_RESCORE_MAX_NEW new symbols."""
+    return decode.rescore_max_new() - int(kmer_len) + 1
+
+
+def variant_triple(seq, pos, ndel, alt, kmer_len):
+    """(start, ndel, new k-mer states) of replacing seq[pos:pos + ndel] by alt, as bio.edit_states gives it for the spelled-out strings,
+    from the letters alone (design/polish_variants.md 1.3): two variants that spell the same string have the same triple.  For a
+    single-letter edit it is letter_triple."""
+    pos, ndel, k = int(pos), int(ndel), int(kmer_len)
+    text = seq[:pos] + alt + seq[pos + ndel:]
+    n, n2 = len(seq), len(text)
+    m = min(n, n2)
+    front = next((i for i in range(pos, m) if seq[i] != text[i]), None)
+    back = next((n - 1 - t for t in range(n - pos - ndel, m) if seq[n - 1 - t] != text[n2 - 1 - t]), None)
+    nold, nnew = n - k + 1, n2 - k + 1
+    nmin = min(nold, nnew)
+    pre = nmin if front is None else min(max(front - k + 1, 0), nmin)
+    rest = nmin - pre
+    suf = rest if back is None else min(max(nold - 1 - back, 0), rest)
+    new = bio.seq_to_states(text[pre:nnew - suf + k - 1], k) if nnew - suf > pre else np.zeros(0, dtype=np.int64)
+    return pre, nold - pre - suf, tuple(int(v) for v in new)
+
+
+class VariantSet(object):
+    """Variants on the device in the layout the kernels read, sorted by (contig, pos): var_off, var_pos (int64), var_ndel (int32),
+    var_alt_off (int64 [V + 1]), var_alt (uint8), contig_off (int64, the index's offsets).  order: host int64 [V], order[s] the
+    caller's number of sorted entry s (order_dev the same on the device); every result of the functions that take the set is in the
+    caller's order."""
+
+    def __init__(self, index, var_off, var_pos, var_ndel, var_alt_off, var_alt, contig_off, order=None):
+        import torch
+        self.index, self.V, self.A = index, int(var_off.numel()), int(var_alt.numel())
+        self.var_off, self.var_pos, self.var_ndel, self.var_alt_off, self.var_alt = var_off, var_pos, var_ndel, var_alt_off, var_alt
+        self.contig_off = contig_off
+        self.order = np.arange(self.V, dtype=np.int64) if order is None else np.asarray(order, dtype=np.int64)
+        self.order_dev = torch.from_numpy(self.order).to(var_off.device)
+        self._rows = None
+
+    def __len__(self):
+        return self.V
+
+    def rows(self):
+        """[(contig name, pos, ndel, alt)] in the caller's order (one fetch, kept)."""
+        if self._rows is None:
+            ix = self.index
+            off, pos, nd = self.var_off.cpu().numpy(), self.var_pos.cpu().numpy(), self.var_ndel.cpu().numpy()
+            ao, al = self.var_alt_off.cpu().numpy(), self.var_alt.cpu().numpy().tobytes().decode('ascii')
+            starts = dict((int(o), n) for n, o in zip(ix.names, ix.offsets[:-1]))
+            out = [None] * self.V
+            for s in range(self.V):
+                out[int(self.order[s])] = (starts.get(int(off[s])), int(pos[s]), int(nd[s]), al[int(ao[s]):int(ao[s + 1])])
+            self._rows = out
+        return list(self._rows)
+
+
+def _contig_offsets(index, dev):
+    import torch
+    have = getattr(index, 'offsets_dev', None)
+    return have if have is not None else torch.from_numpy(np.ascontiguousarray(index.offsets, dtype=np.int64)).to(dev)
+
+
+def upload_variants(index, variants, kmer_len=None):
+    """Rows (contig name or number, pos, ndel, alt) checked on the host, sorted by (contig, pos) stably and put on the device.
+    ValueError naming the row for: an unknown contig, a span outside it, a negative ndel, an alt with a letter that is none of ACGT or
+    with more than max_alt(kmer_len) letters (kmer_len None: of the shortest k-mers, 3), an empty edit, an alt that is the letters
+    that stand there.  -> VariantSet."""
+    import torch
+    rows = list(variants)
+    cap = max_alt(3 if kmer_len is None else kmer_len)
+    host = None
+    key, nd_h, alts = [], [], []
+    for i, row in enumerate(rows):
+        bad = lambda why: ValueError("variant %d %r: %s" % (i, tuple(row), why))               # noqa: E731
+        if len(row) != 4:
+            raise bad("a variant is (contig, pos, ndel, alt)")
+        c, pos, ndel, alt = row
+        if not isinstance(c, (int, np.integer)):
+            if c not in index.names:
+                raise bad(VARIANT_REASONS[-1])
+            c = index.names.index(c)
+        if not 0 <= c < len(index.names):
+            raise bad(VARIANT_REASONS[-1])
+        if int(ndel) < 0:
+            raise bad(VARIANT_REASONS[-3])
+        if int(pos) < 0 or int(pos) + int(ndel) > int(index.lengths[c]):
+            raise bad(VARIANT_REASONS[-2])
+        if any(ch not in 'ACGT' for ch in alt):
+            raise bad("its alt has a letter that is none of A C G T")
+        if len(alt) > cap:
+            raise bad(VARIANT_REASONS[-4])
+        if int(ndel) + len(alt) < 1:
+            raise bad(VARIANT_REASONS[-5])
+        if int(ndel) == len(alt):
+            if host is None:
+                host = index.genome.cpu().numpy().tobytes().decode('ascii')
+            p = int(index.offsets[c]) + int(pos)
+            if host[p:p + int(ndel)] == alt:
+                raise bad(VARIANT_REASONS[-6])
+        key.append((int(index.offsets[c]), int(pos)))
+        nd_h.append(int(ndel))
+        alts.append(alt)
+    order = np.array(sorted(range(len(rows)), key=lambda i: key[i]), dtype=np.int64)           # (sorted is stable)
+    dev = index.genome.device
+    up = lambda a, dt: torch.from_numpy(np.array(a, dtype=dt)).to(dev)                         # noqa: E731
+    text = ''.join(alts[i] for i in order)
+    return VariantSet(index, up([key[i][0] for i in order], np.int64), up([key[i][1] for i in order], np.int64),
+                      up([nd_h[i] for i in order], np.int32), up(np.concatenate([[0], np.cumsum([len(alts[i]) for i in order])]), np.int64),
+                      up(np.frombuffer(text.encode('ascii'), dtype=np.uint8), np.uint8), _contig_offsets(index, dev), order)
+
+
+def repeat_variants(index, kmer_len, region=None, max_unit=4, max_change=2, min_copies=2):
+    """The repeat-unit family proposed on the device (slk_repeat_variants_count / _emit; design/polish_variants.md 1.5): for every
+    leftmost tract of a primitive unit of 1 .. max_unit letters with at least min_copies copies that starts inside `region`, the
+    deletions of 1 .. max_change copies (one copy stays) and the insertions of as many (up to max_alt(kmer_len) letters), but the
+    single-letter ones.  One round trip for the totals.  -> VariantSet, sorted as it comes."""
+    import torch
+    from . import _lib, device as D, genome as G
+    _check_kmer_len(kmer_len)
+    if not 1 <= int(max_unit) <= 4 or not 1 <= int(max_change) <= 8 or int(min_copies) < 2:
+        raise ValueError("repeat_variants: max_unit 1 .. 4, max_change 1 .. 8, min_copies >= 2")
+    lo, P = G.region_span(index, region)
+    dev = index.genome.device
+    coff = _contig_offsets(index, dev)
+    L, st = _lib.lib(), D.stream_ptr()
+    head = (index.genome.data_ptr(), int(index.G), coff.data_ptr(), len(index.names), int(lo), int(P), int(kmer_len), int(max_unit),
+            int(max_change), int(min_copies))
+    offs = torch.zeros((2, P + 1), dtype=torch.int64, device=dev)
+    _lib.check(L.slk_repeat_variants_count(*head, offs[0].data_ptr(), offs[1].data_ptr(), st), "repeat_variants_count")
+    offs = torch.cumsum(offs, 1)
+    V, A = (int(v) for v in offs[:, -1].cpu().numpy())
+    var_off = torch.zeros(V, dtype=torch.int64, device=dev)
+    var_pos, var_ndel = torch.zeros_like(var_off), torch.zeros(V, dtype=torch.int32, device=dev)
+    var_alt_off, var_alt = torch.zeros(V + 1, dtype=torch.int64, device=dev), torch.zeros(A, dtype=torch.uint8, device=dev)
+    _lib.check(L.slk_repeat_variants_emit(*head, offs[0].data_ptr(), offs[1].data_ptr(), V, A, var_off.data_ptr(), var_pos.data_ptr(),
+                                          var_ndel.data_ptr(), var_alt_off.data_ptr(), var_alt.data_ptr(), st), "repeat_variants_emit")
+    return VariantSet(index, var_off, var_pos, var_ndel, var_alt_off, var_alt, coff)
+
+
+def variant_edits(genome, contig_offsets, win_off, w0, w1, minus, variants_on_device, kmer_len, blank=0, margin=0):
+    """The candidates a batch of windows of the packed genome has among a variant set, made on the device in the layout the rescoring
+    entries read (slk_variant_edits_count / _emit / _new, slk_polish_window_kmers).  genome, win_off, w0, w1, minus: as letter_edits
+    takes them; contig_offsets: int64 device tensor, the contigs' packed starts and the genome's length; variants_on_device: a
+    VariantSet.  A window's candidates are the variants of its contig that lie `margin` letters inside it.
+    -> the namespace letter_edits returns with cand_var (int32, the variant in the caller's order) in place of cand_edit, and
+    var_status (int32 device [V], caller's order: 0 or a key of VARIANT_REASONS)."""
+    import types
+    import torch
+    from . import _lib, device as D
+    _check_kmer_len(kmer_len)
+    vs, margin, nwin, G = variants_on_device, int(margin), int(win_off.numel()), int(genome.numel())
+    if margin < 0 or blank < 0:
+        raise ValueError("margin and blank are not negative")
+    dev = genome.device
+    for name, t, dt in (("win_off", win_off, torch.int64), ("w0", w0, torch.int64), ("w1", w1, torch.int64), ("minus", minus, torch.int32)):
+        if t.dtype != dt or t.device != dev or t.numel() != nwin or not t.is_contiguous():
+            raise ValueError("variant_edits: %s must be a contiguous %s device tensor with one entry per window" % (name, dt))
+    if contig_offsets.dtype != torch.int64 or contig_offsets.device != dev or contig_offsets.numel() < 2 or not contig_offsets.is_contiguous():
+        raise ValueError("variant_edits: contig_offsets must be a contiguous int64 device tensor of the contigs' starts and the genome's length")
+    L, st = _lib.lib(), D.stream_ptr()
+    lst = (vs.var_off.data_ptr(), vs.var_pos.data_ptr(), vs.var_ndel.data_ptr(), vs.var_alt_off.data_ptr(), vs.var_alt.data_ptr(), vs.V, vs.A)
+    wins = (win_off.data_ptr(), w0.data_ptr(), w1.data_ptr())
+    status = torch.zeros(max(vs.V, 1), dtype=torch.int32, device=dev)
+    offs = torch.empty((2, nwin + 1), dtype=torch.int64, device=dev)
+    _lib.check(L.slk_variant_edits_count(genome.data_ptr(), G, contig_offsets.data_ptr(), int(contig_offsets.numel()) - 1, *lst, *wins, nwin,
+                                         kmer_len, margin, status.data_ptr(), offs[0].data_ptr(), offs[1].data_ptr(), st),
+               "variant_edits_count")
+    offs = torch.cumsum(offs, 1)
+    host = offs.cpu().numpy()                                     # the round trip: the totals (and the per-window counts with them)
+    ncand, npos = int(host[0, -1]), int(host[1, -1])
+    c = types.SimpleNamespace(cand_off=offs[0], pos_off=offs[1], cand_off_host=host[0].copy(), pos_off_host=host[1].copy(), ncand=ncand,
+                              npos=npos)
+    c.cand_pair = torch.empty(max(ncand, 1), dtype=torch.int32, device=dev)
+    c.cand_start, c.cand_ndel, sorted_var = torch.empty_like(c.cand_pair), torch.empty_like(c.cand_pair), torch.empty_like(c.cand_pair)
+    new_off = torch.zeros(ncand + 1, dtype=torch.int64, device=dev)
+    head = (genome.data_ptr(), G) + lst + (status.data_ptr(),) + wins + (minus.data_ptr(), nwin, kmer_len)
+    _lib.check(L.slk_variant_edits_emit(*head, margin, c.cand_off.data_ptr(), ncand, c.cand_pair.data_ptr(), c.cand_start.data_ptr(),
+                                        c.cand_ndel.data_ptr(), sorted_var.data_ptr(), new_off.data_ptr(), st), "variant_edits_emit")
+    c.cand_new_off = torch.cumsum(new_off, 0)
+    cap = max(ncand * decode.rescore_max_new(), 1)                # (no second round trip for the exact total)
+    c.cand_new = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+    _lib.check(L.slk_variant_edits_new(*head, int(blank), margin, ncand, c.cand_pair.data_ptr(), c.cand_start.data_ptr(),
+                                       sorted_var.data_ptr(), c.cand_new_off.data_ptr(), cap, c.cand_new.data_ptr(), st), "variant_edits_new")
+    c.seq = torch.empty(max(npos, 1), dtype=torch.int32, device=dev)
+    _lib.check(L.slk_polish_window_kmers(genome.data_ptr(), G, *wins, minus.data_ptr(), nwin, kmer_len, int(blank), c.pos_off.data_ptr(),
+                                         npos, c.seq.data_ptr(), st), "polish_window_kmers")
+    c.cand_pair, c.cand_start, c.cand_ndel, sorted_var = c.cand_pair[:ncand], c.cand_start[:ncand], c.cand_ndel[:ncand], sorted_var[:ncand]
+    c.cand_var_sorted = sorted_var
+    c.cand_var = vs.order_dev[sorted_var.to(torch.int64)].to(torch.int32) if ncand else sorted_var
+    c.var_status = torch.zeros(vs.V, dtype=torch.int32, device=dev)
+    if vs.V:
+        c.var_status[vs.order_dev] = status[:vs.V]
+    return c
+
+
+VARIANT_TABLES = ("gain", "support", "pro", "gain_strand", "support_strand", "pro_strand")
+
+
+def sum_variant_gains(score, ll_edit, cand_read, cand_var, read_minus, V, tables=None):
+    """The reads' gains per variant and strand (slk_polish_sum_variant_gains_f64): per variant the sum of ll_edit - score[cand_read] over
+    its candidates, taken one after the other in read order (the sort by (variant, read) is torch's, the walk the kernel's), the
+    number of reads counted and how many of them gained; the same over the '+' reads and the '-' reads alone (read_minus: int32
+    device tensor per read).  Only candidates whose two values are finite count; a NaN of either makes the cells NaN.  tables: the six
+    tables of an earlier call to go on from (added to in place) -- batches that come in read order give the bits of one call.
+    -> (gain float64 [V], support int32 [V], pro int32 [V], gain_strand float64 [V, 2], support_strand, pro_strand int32 [V, 2])."""
+    import torch
+    from . import _lib, device as D
+    dev = score.device
+    V, ncand = int(V), int(ll_edit.numel())
+    if tables is None:
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)                          # noqa: E731
+        tables = (z(V, torch.float64), z(V, torch.int32), z(V, torch.int32), z((V, 2), torch.float64), z((V, 2), torch.int32),
+                  z((V, 2), torch.int32))
+    if cand_read.numel() != ncand or cand_var.numel() != ncand or cand_read.dtype != torch.int32 or cand_var.dtype != torch.int32 or \
+            score.dtype != torch.float64 or ll_edit.dtype != torch.float64 or read_minus.dtype != torch.int32 or \
+            read_minus.numel() != score.numel():
+        raise ValueError("sum_variant_gains needs one int32 read, one int32 variant and one float64 value per candidate, and a float64 "
+                         "score and an int32 strand per read")
+    for t, dt in zip(tables, (torch.float64, torch.int32, torch.int32, torch.float64, torch.int32, torch.int32)):
+        if t.dtype != dt or t.shape[0] != V or not t.is_contiguous():
+            raise ValueError("sum_variant_gains: tables= are the six tables of an earlier call on the same variants")
+    if ncand and V:
+        by_read = torch.sort(cand_read, stable=True).indices
+        order = by_read[torch.sort(cand_var[by_read], stable=True).indices].contiguous()
+        _lib.check(_lib.lib().slk_polish_sum_variant_gains_f64(
+            score.data_ptr(), read_minus.contiguous().data_ptr(), int(score.numel()), ll_edit.contiguous().data_ptr(),
+            cand_read.contiguous().data_ptr(), cand_var.contiguous().data_ptr(), order.data_ptr(), ncand, V,
+            *[t.data_ptr() for t in tables], D.stream_ptr()), "polish_sum_variant_gains")
+    return tuple(tables)
+
+
+class GenomeVariantsRescored(object):
+    """What the signal of the mapped reads says about proposed variants of a genome (rescore_variants).
+
+    variants: the VariantSet; every table is in the caller's order.  gain float64, support, pro int32: device tensors [V]: the sum
+    over the reads that scored the variant of (log-likelihood of the edited window - that of the window), their number, and how
+    many of them prefer the variant; gain_strand, support_strand, pro_strand [V, 2]: the same over the '+' (0) and the '-' (1)
+    reads alone.  NaN where a read's candidate was refused.  var_status: device int32 [V] (VARIANT_REASONS).  status, score, span,
+    window: per read, as GenomeRescored.  cand_read, cand_var (int32), ll_edit (float64): the candidates behind the sums."""
+
+    def __init__(self, variants, kmer_len, tables, var_status, status, score, span, window, cand_read, cand_var, ll_edit):
+        self.variants, self.index, self.kmer_len = variants, variants.index, int(kmer_len)
+        self.gain, self.support, self.pro, self.gain_strand, self.support_strand, self.pro_strand = tables
+        self.var_status, self.status, self.score, self.span, self.window = var_status, status, score, span, window
+        self.cand_read, self.cand_var, self.ll_edit = cand_read, cand_var, ll_edit
+
+    def rows(self, min_gain=None, min_support=0):
+        """The variants with support >= min_support and, when given, gain > min_gain, chosen on the device:
+        -> [(contig, pos, ndel, alt, gain, support, pro)] in the caller's order."""
+        mask = self.support >= max(int(min_support), 0)
+        if min_gain is not None:
+            mask = mask & (self.gain > float(min_gain))            # (a NaN cell compares false)
+        hit = mask.nonzero().reshape(-1)
+        g, s, p = self.gain[hit].cpu().numpy(), self.support[hit].cpu().numpy(), self.pro[hit].cpu().numpy()
+        rows = self.variants.rows()
+        return [rows[int(h)] + (float(gv), int(sv), int(pv)) for h, gv, sv, pv in zip(hit.cpu().numpy(), g, s, p)]
+
+    def top(self, n=10):
+        """The n variants of largest gain among those a read scored."""
+        return sorted((r for r in self.rows(None, 1) if r[4] == r[4]), key=lambda r: (-r[4], r[0], r[1]))[:int(n)]
+
+    def read_gains(self, v):
+        """(reads int array, gains float64 array): the per-read log-likelihood ratios of variant v (caller's number), in read order."""
+        hit = (self.cand_var == int(v)).nonzero().reshape(-1)
+        reads = self.cand_read[hit].to(self.score.device)
+        gains = self.ll_edit[hit] - self.score[reads.to(hit.dtype)]
+        order = np.argsort(reads.cpu().numpy(), kind='stable')
+        return reads.cpu().numpy()[order], gains.cpu().numpy()[order]
+
+
+def _as_variant_set(index, variants, kmer_len):
+    if isinstance(variants, VariantSet):
+        if variants.index is not index:
+            raise ValueError("rescore_variants: the variant set was made for another index")
+        return variants
+    if isinstance(variants, str):
+        if variants != 'repeats':
+            raise ValueError("unknown family of variants %r (known: 'repeats')" % (variants,))
+        return repeat_variants(index, kmer_len)
+    return upload_variants(index, variants, kmer_len)
+
+
+def rescore_variants(post, steps, paths, lens, move_row, index, res, strand, info, ops, kmer_len, variants, width=512, margin=None,
+                     keep=None, blank=0, min_prob=None, workspace_limit=None):
+    """Put proposed variants of any length to the signal of the reads mapped to a genome (design/polish_variants.md).
+
+    Everything but `variants` as rescore_genome takes it, and the reads' windows, rows, centre lines and bands are rescore_genome's.
+    variants: a list of (contig, pos, ndel, alt) -- replace the ndel letters from pos on by alt; ndel 0 an insertion in front of pos
+    --, a VariantSet (upload_variants, repeat_variants) or 'repeats'.  A read scores the variants of its contig that lie `margin`
+    letters inside its window (variant_edits), each as ONE candidate of the banded entry as it is
+    (decode.rescore_edits_banded_device), and the answers are summed per variant and strand in read order (sum_variant_gains).
+    A variant the device refuses raises ValueError.  -> GenomeVariantsRescored."""
+    import torch
+    _check_kmer_len(kmer_len)
+    if post.dim() != 3 or int(post.shape[2]) != 4 ** kmer_len + 1:
+        raise ValueError("rescore_variants takes a [rows, reads, %d] transducer posterior of %d-mers" % (4 ** kmer_len + 1, kmer_len))
+    B = int(post.shape[1])
+    if len(ops) != B or len(res) != B:
+        raise ValueError("rescore_variants: %d reads in the posterior, %d alignments" % (B, len(ops)))
+    margin = 2 * int(kmer_len) if margin is None else int(margin)
+    pd = post if post.is_contiguous() else post.contiguous()
+    dev = pd.device
+    vs = _as_variant_set(index, variants, kmer_len)
+    w = read_windows(paths, lens, move_row, steps, ops, strand, info, index, kmer_len, keep)
+    reads = np.flatnonzero(w.status == READ_DONE)
+    score = torch.full((B,), float('nan'), dtype=torch.float64, device=dev)
+    minus_d = torch.from_numpy(np.ascontiguousarray(w.minus.astype(np.int32))).to(dev)
+    empty = lambda dt: torch.zeros(0, dtype=dt, device=dev)        # noqa: E731
+    if not len(reads):
+        nothing = torch.zeros(0, dtype=torch.int64, device=dev)
+        c = variant_edits(index.genome, vs.contig_off, nothing, nothing, nothing, empty(torch.int32), vs, kmer_len, blank, margin)
+        cand_read, ll = empty(torch.int32), empty(torch.float64)
+    else:
+        reads_d = torch.from_numpy(np.ascontiguousarray(reads.astype(np.int64))).to(dev)
+        c = variant_edits(index.genome, vs.contig_off, *_window_tensors(w, reads, dev), vs, kmer_len, blank, margin)
+        nrow, band, row_off = _read_bands(w, reads, np.diff(c.pos_off_host), width, B, dev)
+        sc, ll = decode.rescore_edits_banded_device(pd, row_off, B, nrow.astype(np.int32), c.seq, c.pos_off, band, width, c.cand_off_host,
+                                                    c.cand_pair, c.cand_start, c.cand_ndel, c.cand_new_off, c.cand_new, blank=blank,
+                                                    min_prob=min_prob, workspace_limit=workspace_limit)
+        score[reads_d] = sc
+        cand_read = reads_d[c.cand_pair.to(torch.int64)].to(torch.int32)
+    bad = c.var_status.nonzero().reshape(-1)
+    if bad.numel():
+        v = int(bad[0])
+        raise ValueError("variant %d %r: %s" % (v, vs.rows()[v], VARIANT_REASONS.get(int(c.var_status[v]), "refused")))
+    tables = sum_variant_gains(score, ll, cand_read, c.cand_var, minus_d, vs.V)
+    return GenomeVariantsRescored(vs, kmer_len, tables, c.var_status, w.status, score, w.span, w.window, cand_read, c.cand_var, ll)
+
+
+def _as_replacement(kind, pos, letter):
+    """(pos, ndel, alt) of a single-letter cell."""
+    return (pos, 1, letter) if kind == 'sub' else (pos, 1, '') if kind == 'del' else (pos, 0, letter)
+
+
+def accept_genome_variants(cells, variants, text, kmer_len):
+    """One round's choice among the fetched cells (contig, pos, kind, letter, gain, support) and variants (contig, pos, ndel, alt, gain,
+    support, ...) together: by (-gain, contig, pos, kind -- cells before variants --, letter); an edit spans its first to its last
+    touched letter (an insertion touches pos alone) and is taken when at least kmer_len letters lie between it and every edit already
+    taken on its contig -- for two cells accept_genome_edits' spacing --; an edit whose variant_triple on the contig's string an
+    earlier one of the round had is that edit again and is passed over.
+    -> rows (contig, pos, kind, letter, gain, support), a variant with kind 'var' and (ndel, alt) for its letter."""
+    rank = dict((k, i) for i, k in enumerate(bio.EDIT_KINDS))
+    items = [(-r[4], r[0], r[1], rank[r[2]], r[3], _as_replacement(r[2], r[1], r[3]), tuple(r[:6])) for r in cells]
+    items += [(-r[4], r[0], r[1], len(rank), (r[2], r[3]), (r[1], r[2], r[3]), (r[0], r[1], 'var', (r[2], r[3]), r[4], r[5])) for r in variants]
+    taken, spans, seen = [], [], set()
+    for it in sorted(items, key=lambda it: it[:5]):
+        pos, ndel, alt = it[5]
+        key = (it[1],) + variant_triple(text[it[1]], pos, ndel, alt, kmer_len)
+        if key in seen:
+            continue
+        seen.add(key)
+        first, last = pos, pos + max(ndel, 1) - 1
+        if all(c != it[1] or first - b >= kmer_len or a - last >= kmer_len for c, a, b in spans):
+            taken.append(it[6])
+            spans.append((it[1], first, last))
+    return taken
+
+
+def _polish_genome_variants(post, steps, paths, lens, move_row, index, kmer_len, width, margin, kinds, keep, min_gain, min_support,
+                            max_rounds, blank, min_prob, workspace_limit, map_kwargs, proposals):
+    """polish_genome with proposals= (its docstring)."""
+    from . import genome as G
+    kw = dict(map_kwargs or {})
+    host = index.genome.cpu().numpy().tobytes().decode('ascii')
+    text = collections.OrderedDict((n, host[int(a):int(b)]) for n, a, b in zip(index.names, index.offsets[:-1], index.offsets[1:]))
+    applied = dict((n, []) for n in text)
+    rounds = dict((n, 0) for n in text)
+    ix, last, lastv = index, None, None
+    for r in range(int(max_rounds)):
+        got = ix.map_paths(paths, lens, kmer_len, ops=True, **kw)
+        res, strand, info, ops = got[0], got[1], got[2], got[4]
+        mask = keep(res, strand, info) if callable(keep) else keep
+        common = dict(width=width, margin=margin, keep=mask, blank=blank, min_prob=min_prob, workspace_limit=workspace_limit)
+        cells = []
+        if len(kinds):
+            last = rescore_genome(post, steps, paths, lens, move_row, ix, res, strand, info, ops, kmer_len, kinds=kinds, **common)
+            cells = last.cells(min_gain, min_support)
+        asked = proposals(ix) if callable(proposals) else proposals if isinstance(proposals, str) or r == 0 else []
+        lastv = rescore_variants(post, steps, paths, lens, move_row, ix, res, strand, info, ops, kmer_len, asked, **common)
+        taken = accept_genome_variants(cells, lastv.rows(min_gain, min_support), text, kmer_len)
+        if not taken:
+            break
+        for name in text:
+            mine = sorted((t for t in taken if t[0] == name), key=lambda t: t[1], reverse=True)
+            if mine:
+                s = text[name]
+                for t in mine:                                     # (from the back: the positions in front stay)
+                    pos, ndel, alt = (t[1],) + tuple(t[3]) if t[2] == 'var' else _as_replacement(t[2], t[1], t[3])
+                    s = s[:pos] + alt + s[pos + ndel:]
+                text[name] = s
+                applied[name].extend((r, t[1], t[2], t[3], t[4], t[5]) for t in sorted(mine, key=lambda t: t[1]))
+                rounds[name] += 1
+        ix = G.Index(list(text.items()), k=index.k, bin_width=index.bin_width, max_occ=index.max_occ)
+    return [GenomePolished(n, text[n], applied[n], rounds[n]) for n in text], last, lastv
