@@ -20,7 +20,7 @@
 // l computes row t - l and hands its right-hand column (H, E, carried words, the row's letter) to lane l + 1.  A reference wider
 // than one pass of ALIGN_P = 64 * ALIGN_C columns is walked in passes; the column between two passes (H, E and their carried words
 // for every query row) lives in the pair's workspace in global memory, written by lane 63 and read back 64 rows at a time.
-#include "common.h"
+#include "genome_edits.h"                       // the complement
 
 #define ALIGN_C 8
 #define ALIGN_P (64 * ALIGN_C)
@@ -31,7 +31,6 @@
 #define ALIGN_INS_ONE 0x10000ull
 #define ALIGN_MM_ONE 1ull
 
-typedef unsigned long long u64;
 
 __device__ __forceinline__ u64 align_fresh(int i, int j) { return (u64)(((unsigned)i << 16) | (unsigned)j) << 32; }
 
@@ -206,7 +205,7 @@ __global__ void __launch_bounds__(256) revcomp_kernel(const uint8_t *__restrict_
     const long long s = off[blockIdx.x], len = off[blockIdx.x + 1] - s;
     for (long long k = (long long)blockIdx.y * 256 + threadIdx.x; k < len; k += (long long)gridDim.y * 256) {
         const uint8_t c = seq[s + len - 1 - k];
-        out[s + k] = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c;
+        out[s + k] = (uint8_t)ge_comp(c);
     }
 }
 

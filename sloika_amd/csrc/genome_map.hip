@@ -23,7 +23,7 @@
 //          arrival, so no result depends on scheduling; nothing waits on another workgroup.
 //   windows  out[out_off[b] + j] = genome[start[b] + j], or complement(genome[end[b] - 1 - j]) for a '-' span (the complement of
 //          slk_revcomp_u8: A<->T, C<->G, every other byte unchanged).
-#include "common.h"
+#include "genome_edits.h"                       // the base digit and the complement
 
 #define GM_THREADS 256
 #define GM_MIN_K 8
@@ -34,10 +34,6 @@
 #define GM_MAX_OCC 4096                        // 65535 positions * 4096 occurrences * 2 bins < 2^31: no count overflows
 #define GM_MAX_GROUPS 2048
 #define GM_WORKSPACE_CAP ((size_t)4 << 30)
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ int gm_letter(uint8_t c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
 
 __global__ void __launch_bounds__(GM_THREADS) genome_keys_kernel(const uint8_t *__restrict__ genome,
                                                                  const int64_t *__restrict__ contig_off, int ncontig, long long G,
@@ -55,7 +51,7 @@ __global__ void __launch_bounds__(GM_THREADS) genome_keys_kernel(const uint8_t *
         unsigned code = 0;
         if (valid)
             for (int j = 0; j < k; j++) {
-                const int l = gm_letter(genome[p + j]);
+                const int l = ge_digit(genome[p + j]);
                 valid &= l >= 0;
                 code = (code << 2) | (unsigned)(l & 3);
             }
@@ -126,7 +122,7 @@ __global__ void __launch_bounds__(GM_THREADS) genome_seed_kernel(const uint8_t *
             unsigned fwd = 0, rev = 0;
             bool ok = true;
             for (int j = 0; j < k; j++) {
-                const int l = gm_letter(qb[i + j]);
+                const int l = ge_digit(qb[i + j]);
                 ok &= l >= 0;
                 fwd = (fwd << 2) | (unsigned)(l & 3);
                 rev |= (unsigned)(3 - (l & 3)) << (2 * j);
@@ -195,7 +191,7 @@ __global__ void __launch_bounds__(256) genome_windows_kernel(const uint8_t *__re
     const bool rc = minus[blockIdx.x] != 0;
     for (long long j = (long long)blockIdx.y * 256 + threadIdx.x; j < e - s; j += (long long)gridDim.y * 256) {
         const uint8_t c = rc ? genome[e - 1 - j] : genome[s + j];
-        out[o + j] = !rc ? c : c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c;
+        out[o + j] = rc ? (uint8_t)ge_comp(c) : c;
     }
 }
 

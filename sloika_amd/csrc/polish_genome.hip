@@ -1,28 +1,23 @@
 // polish_genome.hip -- the join of the genome half and the signal half (design/polish_genome.md; the quantities are defined in its
 // section 1 and restated as plain loops in tests/polish_genome_ref.py).
 //
-// Integer kernels but the last; no LDS, no MFMA.
+// Integer kernels but the last; no LDS, no MFMA.  Every input is device data and is NOT trusted: no loop bound and no address depends
+// on a value that has not been checked in the same kernel.
 //   polish_read_windows_kernel  one wave per read: checks the read's call and alignment (device data, NOT trusted), writes the row of
 //                               every called letter into a work table, and takes the centre line of the aligned rows through the
 //                               alignment's columns, 64 columns per step with ballots as csrc/pileup.hip walks them.
 //   letter_edits_count_kernel   one thread per window: how many candidates and k-mers it has (closed forms).
-//   letter_edits_emit_kernel    one thread per candidate: (pair, start, ndel, number of new symbols, edit); the common prefix and suffix
-//                               of the spelled-out strings are followed along a run of equal letters by a loop.
+//   letter_edits_emit_kernel    one thread per candidate: (pair, start, ndel, number of new symbols, edit).
 //   letter_edits_new_kernel     one thread per candidate: its new symbols, behind the prefix sum of their numbers.
 //   window_kmers_kernel         one thread per k-mer of a window: its posterior column.
 //   polish_sum_gains_kernel     one thread per candidate of the sorted list; the head of a segment of equal edits walks it in read
 //                               order, so a cell's bits depend on no launch shape.  No floating-point atomics.
-#include "common.h"
+// The window, the edit as a replacement, its (start, ndel, new symbols) and the pieces of the sum kernel's walk are genome_edits.h's,
+// shared with polish_variants.hip; this file keeps the read's window and centre line, the closed-form counts, which edit candidate r
+// of a window is, the edit's forward-strand cell and the cell's sum.
+#include "genome_edits.h"
 
-#define PG_WAVES 4
-#define PG_THREADS 256
 #define PG_MAX_LEN 65535                        // as the traceback: a pair has at most 2 * 65535 columns
-#define PG_NONE (-1)
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ int pg_digit(int c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
-__device__ __forceinline__ int pg_comp(int c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c; }
 
 // ---- 1. windows ------------------------------------------------------------------------------------------------------------------
 
@@ -41,7 +36,7 @@ __device__ __forceinline__ int pg_check_row(const int *row, long long nq, long l
     return SLK_POLISH_DONE;
 }
 
-__global__ void __launch_bounds__(64 * PG_WAVES) polish_read_windows_kernel(
+__global__ void __launch_bounds__(64 * GE_WAVES) polish_read_windows_kernel(
     const int32_t *__restrict__ paths, long ldp, const int32_t *__restrict__ lens, const int32_t *__restrict__ move_row, long ldm,
     int T, const int32_t *__restrict__ nrow, const int32_t *__restrict__ qlen, long ldq, const int64_t *__restrict__ roff,
     const int32_t *__restrict__ rows, const uint8_t *__restrict__ ops, const int64_t *__restrict__ ops_off, long long ops_bytes,
@@ -51,7 +46,7 @@ __global__ void __launch_bounds__(64 * PG_WAVES) polish_read_windows_kernel(
     int64_t *__restrict__ window, int32_t *center)
 {
     const int lane = threadIdx.x & 63;
-    const int b = blockIdx.x * PG_WAVES + (threadIdx.x >> 6);
+    const int b = blockIdx.x * GE_WAVES + (threadIdx.x >> 6);
     if (b >= B) return;                                          // (whole waves: nothing below synchronises across waves)
     if (keep[b] == 0 || tb_status[b] != SLK_ALIGN_TB_DONE) {
         if (lane == 0) status[b] = SLK_POLISH_SKIPPED;
@@ -240,20 +235,6 @@ __global__ void __launch_bounds__(64 * PG_WAVES) polish_read_windows_kernel(
 
 // ---- 2. candidates from letters ------------------------------------------------------------------------------------------------------
 
-struct pg_win {
-    const uint8_t *g;          // the window's first forward letter
-    int n;                     // letters
-    bool rev;
-    __device__ __forceinline__ int at(int u) const { return rev ? pg_comp(g[n - 1 - u]) : (int)g[u]; }
-};
-
-// A window's span, checked: -> letters, or -1 when it is no span of the genome the kernels take.
-__device__ __forceinline__ long long pg_window_len(long long off, long long w0, long long w1, long long G)
-{
-    if (off < 0 || w0 < 0 || w1 < w0 || off > G || w1 > G - off || w1 - w0 > 0x7ffffff0ll) return -1;
-    return w1 - w0;
-}
-
 // per position: 3 substitutions, a deletion (when the shorter string still has a k-mer), 4 insertions, each when its kind is asked for
 __device__ __forceinline__ int pg_per_position(int n, int klen, int kinds)
 {
@@ -267,40 +248,31 @@ __device__ __forceinline__ long long pg_ncand(long long n, int klen, int kinds, 
     return (hi - lo) * pg_per_position((int)n, klen, kinds) + ((kinds & 4) ? 4 : 0);
 }
 
-__global__ void __launch_bounds__(PG_THREADS) letter_edits_count_kernel(
+__global__ void __launch_bounds__(GE_THREADS) letter_edits_count_kernel(
     const int64_t *__restrict__ win_off, const int64_t *__restrict__ w0, const int64_t *__restrict__ w1, int nwin, long long G, int klen,
     int kinds, int margin, int64_t *__restrict__ ncand, int64_t *__restrict__ nkmer)
 {
-    const int b = blockIdx.x * PG_THREADS + threadIdx.x;
+    const int b = blockIdx.x * GE_THREADS + threadIdx.x;
     if (b == 0) {
         ncand[0] = 0;
         nkmer[0] = 0;
     }
     if (b >= nwin) return;
-    const long long n = pg_window_len(win_off[b], w0[b], w1[b], G);
+    const long long n = ge_window_len(win_off[b], w0[b], w1[b], G);
     ncand[b + 1] = n < 0 ? 0 : pg_ncand(n, klen, kinds, margin);
     nkmer[b + 1] = n < klen ? 0 : n - klen + 1;
 }
 
-// the window that holds entry i of a list laid out by off[0 .. nwin] (ascending, off[0] = 0): the last b with off[b] <= i
-__device__ __forceinline__ int pg_find(const int64_t *__restrict__ off, int nwin, long long i)
-{
-    int lo = 0, hi = nwin;
-    while (hi - lo > 1) {
-        const int mid = lo + (hi - lo) / 2;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 struct pg_edit {
     int kind;                  // 0 substitution, 1 deletion, 2 insertion
-    int u;                     // window position
+    int u, nd, m;              // window position; the letters it removes and puts there (genome_edits.h)
     int c;                     // the window's new letter (substitution, insertion)
+    __device__ __forceinline__ int letter(int) const { return c; }
+    __device__ __forceinline__ void set(int k, int l) { kind = k; c = l; nd = k == 2 ? 0 : 1; m = k == 1 ? 0 : 1; }
 };
 
 // candidate r of a window, in the order of bio.single_letter_edits on the window's own string
-__device__ __forceinline__ pg_edit pg_decode(const pg_win &w, long long r, int klen, int kinds, int margin)
+__device__ __forceinline__ pg_edit pg_decode(const ge_win &w, long long r, int klen, int kinds, int margin)
 {
     const int per = pg_per_position(w.n, klen, kinds), lo = margin, hi = w.n - margin;
     pg_edit e;
@@ -314,120 +286,66 @@ __device__ __forceinline__ pg_edit pg_decode(const pg_win &w, long long r, int k
     }
     if (kinds & 1) {
         if (q < 3) {
-            const int d = pg_digit(w.at(e.u));
-            e.kind = 0;
-            e.c = "ACGT"[q + (d >= 0 && q >= d ? 1 : 0)];
+            const int d = ge_digit(w.at(e.u));
+            e.set(0, "ACGT"[q + (d >= 0 && q >= d ? 1 : 0)]);
             return e;
         }
         q -= 3;
     }
     if ((kinds & 2) && w.n - 1 >= klen) {
         if (q == 0) {
-            e.kind = 1;
-            e.c = 0;
+            e.set(1, 0);
             return e;
         }
         q -= 1;
     }
-    e.kind = 2;
-    e.c = "ACGT"[q & 3];
+    e.set(2, "ACGT"[q & 3]);
     return e;
 }
 
-// letter i of the edited string
-__device__ __forceinline__ int pg_edited_at(const pg_win &w, const pg_edit &e, int i)
+// Candidate i of the list laid out by cand_off: its window and its edit.  A candidate list that is not the window's own count is not
+// followed (false).
+__device__ __forceinline__ bool pg_candidate(const uint8_t *__restrict__ genome, long long G, const int64_t *__restrict__ win_off,
+                                             const int64_t *__restrict__ w0, const int64_t *__restrict__ w1,
+                                             const int32_t *__restrict__ minus, int nwin, int klen, int kinds, int margin,
+                                             const int64_t *__restrict__ cand_off, long long i, int *b, ge_win *w, pg_edit *e)
 {
-    if (e.kind == 0) return i == e.u ? e.c : w.at(i);
-    if (e.kind == 1) return w.at(i < e.u ? i : i + 1);
-    return i < e.u ? w.at(i) : i == e.u ? e.c : w.at(i - 1);
-}
-
-// (start, ndel, number of new k-mers) of bio.edit_states for the window's string and its edit: the common prefix of the two k-mer
-// lists first, then the common suffix of the rest.  dF: the first letter at which the strings differ read from the front, dB: the
-// last letter of the OLD string at which they differ read from the back (PG_NONE: they agree as far as the shorter goes); inside a
-// run of equal letters both are found by walking along the run.
-__device__ __forceinline__ void pg_triple(const pg_win &w, const pg_edit &e, int klen, int *start, int *ndel, int *nnew)
-{
-    const int n = w.n, u = e.u;
-    int dF, dB;
-    if (e.kind == 0) {
-        dF = dB = u;
-    } else if (e.kind == 1) {
-        int x = u;
-        const int c = w.at(u);
-        while (x + 1 < n && w.at(x + 1) == c) x++;
-        dF = x == n - 1 ? PG_NONE : x;
-        x = u;
-        while (x >= 1 && w.at(x - 1) == c) x--;
-        dB = x == 0 ? PG_NONE : x;
-    } else {
-        int x = u;
-        while (x < n && w.at(x) == e.c) x++;
-        dF = x == n ? PG_NONE : x;
-        x = u;
-        while (x >= 1 && w.at(x - 1) == e.c) x--;
-        dB = x == 0 ? PG_NONE : x - 1;
-    }
-    const int n2 = e.kind == 0 ? n : e.kind == 1 ? n - 1 : n + 1;
-    const int nold = n - klen + 1, nnw = n2 - klen + 1, nmin = nold < nnw ? nold : nnw;
-    int pre = nmin;
-    if (dF != PG_NONE) {
-        pre = dF - klen + 1 > 0 ? dF - klen + 1 : 0;
-        if (pre > nmin) pre = nmin;
-    }
-    const int rest = nmin - pre;
-    int suf = rest;
-    if (dB != PG_NONE) {
-        suf = nold - 1 - dB > 0 ? nold - 1 - dB : 0;
-        if (suf > rest) suf = rest;
-    }
-    *start = pre;
-    *ndel = nold - pre - suf;
-    *nnew = nnw - pre - suf;
-}
-
-__device__ __forceinline__ bool pg_open(const uint8_t *__restrict__ genome, const int64_t *__restrict__ win_off,
-                                        const int64_t *__restrict__ w0, const int64_t *__restrict__ w1,
-                                        const int32_t *__restrict__ minus, int b, long long G, pg_win *w)
-{
-    const long long n = pg_window_len(win_off[b], w0[b], w1[b], G);
-    if (n < 0) return false;
-    w->g = genome + win_off[b] + w0[b];
-    w->n = (int)n;
-    w->rev = minus[b] != 0;
+    *b = ge_find(cand_off, nwin, i);
+    const long long first = cand_off[*b];
+    if (!ge_open(genome, win_off, w0, w1, minus, *b, G, w) || cand_off[*b + 1] - first != pg_ncand(w->n, klen, kinds, margin)) return false;
+    *e = pg_decode(*w, i - first, klen, kinds, margin);
     return true;
 }
 
-__global__ void __launch_bounds__(PG_THREADS) letter_edits_emit_kernel(
+__global__ void __launch_bounds__(GE_THREADS) letter_edits_emit_kernel(
     const uint8_t *__restrict__ genome, long long G, const int64_t *__restrict__ win_off, const int64_t *__restrict__ w0,
     const int64_t *__restrict__ w1, const int32_t *__restrict__ minus, int nwin, int klen, int kinds, int margin,
     const int64_t *__restrict__ cand_off, long long ncand, int32_t *__restrict__ cand_pair, int32_t *__restrict__ cand_start,
     int32_t *__restrict__ cand_ndel, int64_t *__restrict__ cand_new_off, int64_t *__restrict__ cand_edit)
 {
-    const long long i = (long long)blockIdx.x * PG_THREADS + threadIdx.x;
+    const long long i = (long long)blockIdx.x * GE_THREADS + threadIdx.x;
     if (i == 0) cand_new_off[0] = 0;
     if (i >= ncand) return;
-    const int b = pg_find(cand_off, nwin, i);
-    pg_win w;
-    // a candidate list that is not this window's own count is not followed: its entries stay a refused candidate (start -1)
-    int start = -1, ndel = 0, nnew = 0;
+    ge_win w;
+    pg_edit e;
+    // a candidate that is not followed stays a refused one (start -1)
+    int b, start = -1, ndel = 0, nnew = 0;
     long long edit = -1;
-    if (pg_open(genome, win_off, w0, w1, minus, b, G, &w) && cand_off[b + 1] - cand_off[b] == pg_ncand(w.n, klen, kinds, margin)) {
-        const pg_edit e = pg_decode(w, i - cand_off[b], klen, kinds, margin);
-        pg_triple(w, e, klen, &start, &ndel, &nnew);
+    if (pg_candidate(genome, G, win_off, w0, w1, minus, nwin, klen, kinds, margin, cand_off, i, &b, &w, &e)) {
+        ge_triple(w, e, klen, &start, &ndel, &nnew);
         // the edit on the forward strand: position, and the slot 0-2 substitutions, 3 deletion, 4-7 insertions in front of it
         const int fu = !w.rev ? e.u : e.kind == 2 ? w.n - e.u : w.n - 1 - e.u;
         int slot = 3;
         if (e.kind != 1) {
-            const int fl = pg_digit(w.rev ? pg_comp(e.c) : e.c);
+            const int fl = ge_digit(w.rev ? ge_comp(e.c) : e.c);
             if (e.kind == 2) slot = 4 + fl;
             else {
-                const int fd = pg_digit(w.g[fu]);
+                const int fd = ge_digit(w.g[fu]);
                 slot = fl - (fd >= 0 && fl > fd ? 1 : 0);
                 if (slot > 2) slot = 2;
             }
         }
-        edit = 8 * (win_off[b] + w0[b] + fu) + slot;
+        edit = 8 * (w.off + w.w0 + fu) + slot;
     }
     cand_pair[i] = b;
     cand_start[i] = start;
@@ -436,54 +354,35 @@ __global__ void __launch_bounds__(PG_THREADS) letter_edits_emit_kernel(
     cand_edit[i] = edit;
 }
 
-// the posterior column of the k-mer of `klen` letters read through `at`; -1 when a letter is none of A C G T
-template <typename F>
-__device__ __forceinline__ int pg_column(F at, int first, int klen, int blank)
-{
-    int s = 0;
-    bool bad = false;
-    for (int d = 0; d < klen; d++) {
-        const int x = pg_digit(at(first + d));
-        bad |= x < 0;
-        s = s * 4 + (x & 3);
-    }
-    return bad ? -1 : s + (s >= blank ? 1 : 0);
-}
-
-__global__ void __launch_bounds__(PG_THREADS) letter_edits_new_kernel(
+__global__ void __launch_bounds__(GE_THREADS) letter_edits_new_kernel(
     const uint8_t *__restrict__ genome, long long G, const int64_t *__restrict__ win_off, const int64_t *__restrict__ w0,
     const int64_t *__restrict__ w1, const int32_t *__restrict__ minus, int nwin, int klen, int blank, int kinds, int margin,
     const int64_t *__restrict__ cand_off, long long ncand, const int32_t *__restrict__ cand_start,
     const int64_t *__restrict__ cand_new_off, long long new_cap, int32_t *__restrict__ cand_new)
 {
-    const long long i = (long long)blockIdx.x * PG_THREADS + threadIdx.x;
+    const long long i = (long long)blockIdx.x * GE_THREADS + threadIdx.x;
     if (i >= ncand) return;
-    const int b = pg_find(cand_off, nwin, i);
-    pg_win w;
-    if (!pg_open(genome, win_off, w0, w1, minus, b, G, &w) || cand_off[b + 1] - cand_off[b] != pg_ncand(w.n, klen, kinds, margin)) return;
-    const pg_edit e = pg_decode(w, i - cand_off[b], klen, kinds, margin);
-    const int start = cand_start[i];
-    const long long a = cand_new_off[i], m = cand_new_off[i + 1] - a;
-    const int n2 = e.kind == 0 ? w.n : e.kind == 1 ? w.n - 1 : w.n + 1;
-    if (start < 0 || m < 0 || m > klen + 1 || a < 0 || a + m > new_cap || start + m + klen - 1 > n2) return;
-    for (int x = 0; x < (int)m; x++)
-        cand_new[a + x] = pg_column([&](int j) { return pg_edited_at(w, e, j); }, start + x, klen, blank);
+    ge_win w;
+    pg_edit e;
+    int b;
+    if (!pg_candidate(genome, G, win_off, w0, w1, minus, nwin, klen, kinds, margin, cand_off, i, &b, &w, &e)) return;
+    ge_write_new(w, e, klen, blank, cand_start[i], cand_new_off + i, new_cap, klen + 1, cand_new);
 }
 
-__global__ void __launch_bounds__(PG_THREADS) window_kmers_kernel(
+__global__ void __launch_bounds__(GE_THREADS) window_kmers_kernel(
     const uint8_t *__restrict__ genome, long long G, const int64_t *__restrict__ win_off, const int64_t *__restrict__ w0,
     const int64_t *__restrict__ w1, const int32_t *__restrict__ minus, int nwin, int klen, int blank,
     const int64_t *__restrict__ pos_off, long long npos, int32_t *__restrict__ seq)
 {
-    const long long i = (long long)blockIdx.x * PG_THREADS + threadIdx.x;
+    const long long i = (long long)blockIdx.x * GE_THREADS + threadIdx.x;
     if (i >= npos) return;
-    const int b = pg_find(pos_off, nwin, i);
-    pg_win w;
-    if (!pg_open(genome, win_off, w0, w1, minus, b, G, &w) || pos_off[b + 1] - pos_off[b] != (w.n < klen ? 0 : w.n - klen + 1)) {
+    const int b = ge_find(pos_off, nwin, i);
+    ge_win w;
+    if (!ge_open(genome, win_off, w0, w1, minus, b, G, &w) || pos_off[b + 1] - pos_off[b] != (w.n < klen ? 0 : w.n - klen + 1)) {
         seq[i] = -1;
         return;
     }
-    seq[i] = pg_column([&](int j) { return w.at(j); }, (int)(i - pos_off[b]), klen, blank);
+    seq[i] = ge_column([&](int j) { return w.at(j); }, (int)(i - pos_off[b]), klen, blank);
 }
 
 // ---- 3. the reads' gains on genome coordinates ---------------------------------------------------------------------------------------
@@ -491,31 +390,29 @@ __global__ void __launch_bounds__(PG_THREADS) window_kmers_kernel(
 // order: the candidates sorted by (edit, read), the host's sort.  The thread of a segment's first entry walks the segment: the cell's
 // sum is taken in read order whatever the launch's shape, and continues from what the cell holds (the caller zeroes once; launches
 // that come in read order give the bits of one).
-__global__ void __launch_bounds__(PG_THREADS) polish_sum_gains_kernel(
+__global__ void __launch_bounds__(GE_THREADS) polish_sum_gains_kernel(
     const double *__restrict__ score, int nread, const double *__restrict__ ll_edit, const int32_t *__restrict__ cand_pair,
     const int64_t *__restrict__ cand_edit, const int64_t *__restrict__ order, long long ncand, long long region_start, long long P,
     double *__restrict__ gain, int32_t *__restrict__ support)
 {
-    const long long i = (long long)blockIdx.x * PG_THREADS + threadIdx.x;
+    const long long i = (long long)blockIdx.x * GE_THREADS + threadIdx.x;
     if (i >= ncand) return;
     const long long ci = order[i];
-    if (ci < 0 || ci >= ncand) return;
+    if (!ge_listed(ci, ncand)) return;
     const long long edit = cand_edit[ci];
-    if (i > 0) {
-        const long long cp = order[i - 1];
-        if (cp >= 0 && cp < ncand && cand_edit[cp] == edit) return;       // (not the head of its segment)
-    }
+    if (!ge_segment_head(order, ncand, i, cand_edit, (int64_t)edit)) return;
     const long long cell = edit - 8 * region_start;
     if (edit < 0 || cell < 0 || cell >= 8 * P) return;
     double sum = gain[cell];
     int cnt = support[cell];
     for (long long x = i; x < ncand; x++) {
         const long long c = order[x];
-        if (c < 0 || c >= ncand || cand_edit[c] != edit) break;
+        if (!ge_listed(c, ncand) || cand_edit[c] != edit) break;
         const int r = cand_pair[c];
         const double l = ll_edit[c], s = r >= 0 && r < nread ? score[r] : __builtin_nan("");
-        if (l != l || s != s) sum = __builtin_nan("");           // a refused candidate or pair: the cell says so
-        else if (l - l == 0.0 && s - s == 0.0) {                 // both finite
+        const int what = ge_classify(l, s);
+        if (what == GE_PAIR_NAN) sum = __builtin_nan("");        // the cell says so
+        else if (what == GE_PAIR_FINITE) {
             sum += l - s;
             cnt++;
         }
@@ -526,11 +423,9 @@ __global__ void __launch_bounds__(PG_THREADS) polish_sum_gains_kernel(
 
 // ---- entries --------------------------------------------------------------------------------------------------------------------------
 
-static inline unsigned pg_blocks(long long n) { return (unsigned)((n + PG_THREADS - 1) / PG_THREADS); }
-
 static inline bool pg_edit_args(int nwin, long G, int klen, int kinds, int margin)
 {
-    return nwin >= 0 && G >= 0 && klen >= 3 && klen <= SLK_RESCORE_MAX_NEW - 1 && kinds >= 0 && kinds <= 7 && margin >= 0;
+    return nwin >= 0 && G >= 0 && ge_klen(klen) && kinds >= 0 && kinds <= 7 && margin >= 0;
 }
 
 extern "C" int slk_polish_read_windows(const int32_t *paths, long ldp, const int32_t *lens, const int32_t *move_row, long ldm, int T,
@@ -540,12 +435,12 @@ extern "C" int slk_polish_read_windows(const int32_t *paths, long ldp, const int
                                        int B, int kmer_len, const int64_t *center_off, int32_t *letter_row, int32_t *status,
                                        int32_t *row_span, int64_t *window, int32_t *center, slk_stream_t stream)
 {
-    if (B < 0 || G < 0 || T < 0 || kmer_len < 3 || kmer_len > SLK_RESCORE_MAX_NEW - 1) return SLK_ERR_INVALID_ARG;
+    if (B < 0 || G < 0 || T < 0 || !ge_klen(kmer_len)) return SLK_ERR_INVALID_ARG;
     if (B == 0) return SLK_OK;
     if (!paths || !lens || !move_row || !nrow || !qlen || !roff || !rows || !ops || !ops_off || !tb_status || !minus || !keep || !wstart ||
         !coff || !center_off || !letter_row || !status || !row_span || !window || !center || ldp < T || ldm < T || ldq < 0)
         return SLK_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(polish_read_windows_kernel, dim3((B + PG_WAVES - 1) / PG_WAVES), dim3(64 * PG_WAVES), 0, slk_stream(stream),
+    hipLaunchKernelGGL(polish_read_windows_kernel, dim3((B + GE_WAVES - 1) / GE_WAVES), dim3(64 * GE_WAVES), 0, slk_stream(stream),
                        paths, ldp, lens, move_row, ldm, T, nrow, qlen, ldq, roff, rows, ops, ops_off, (long long)ops_bytes, tb_status,
                        minus, keep, wstart, coff, (long long)G, B, kmer_len, center_off, letter_row, status, row_span, window, center);
     return slk_launch_status();
@@ -556,7 +451,7 @@ extern "C" int slk_letter_edits_count(const int64_t *win_off, const int64_t *w0,
 {
     if (!pg_edit_args(nwin, G, kmer_len, kinds, margin) || !ncand || !nkmer) return SLK_ERR_INVALID_ARG;
     if (nwin > 0 && (!win_off || !w0 || !w1)) return SLK_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(letter_edits_count_kernel, dim3(pg_blocks(nwin > 0 ? nwin : 1)), dim3(PG_THREADS), 0, slk_stream(stream), win_off,
+    hipLaunchKernelGGL(letter_edits_count_kernel, dim3(ge_blocks(nwin > 0 ? nwin : 1)), dim3(GE_THREADS), 0, slk_stream(stream), win_off,
                        w0, w1, nwin, (long long)G, kmer_len, kinds, margin, ncand, nkmer);
     return slk_launch_status();
 }
@@ -570,7 +465,7 @@ extern "C" int slk_letter_edits_emit(const uint8_t *genome, long G, const int64_
     if (ncand > 0 && (nwin < 1 || !genome || !win_off || !w0 || !w1 || !minus || !cand_off || !cand_pair || !cand_start || !cand_ndel ||
                       !cand_edit))
         return SLK_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(letter_edits_emit_kernel, dim3(pg_blocks(ncand > 0 ? ncand : 1)), dim3(PG_THREADS), 0, slk_stream(stream), genome,
+    hipLaunchKernelGGL(letter_edits_emit_kernel, dim3(ge_blocks(ncand > 0 ? ncand : 1)), dim3(GE_THREADS), 0, slk_stream(stream), genome,
                        (long long)G, win_off, w0, w1, minus, nwin, kmer_len, kinds, margin, cand_off, (long long)ncand, cand_pair,
                        cand_start, cand_ndel, cand_new_off, cand_edit);
     return slk_launch_status();
@@ -585,7 +480,7 @@ extern "C" int slk_letter_edits_new(const uint8_t *genome, long G, const int64_t
     if (ncand == 0) return SLK_OK;
     if (nwin < 1 || !genome || !win_off || !w0 || !w1 || !minus || !cand_off || !cand_start || !cand_new_off || !cand_new)
         return SLK_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(letter_edits_new_kernel, dim3(pg_blocks(ncand)), dim3(PG_THREADS), 0, slk_stream(stream), genome, (long long)G,
+    hipLaunchKernelGGL(letter_edits_new_kernel, dim3(ge_blocks(ncand)), dim3(GE_THREADS), 0, slk_stream(stream), genome, (long long)G,
                        win_off, w0, w1, minus, nwin, kmer_len, blank, kinds, margin, cand_off, (long long)ncand, cand_start, cand_new_off,
                        (long long)new_cap, cand_new);
     return slk_launch_status();
@@ -595,10 +490,10 @@ extern "C" int slk_polish_window_kmers(const uint8_t *genome, long G, const int6
                                        const int32_t *minus, int nwin, int kmer_len, int blank, const int64_t *pos_off, int64_t npos,
                                        int32_t *seq, slk_stream_t stream)
 {
-    if (nwin < 0 || G < 0 || kmer_len < 3 || kmer_len > SLK_RESCORE_MAX_NEW - 1 || blank < 0 || npos < 0) return SLK_ERR_INVALID_ARG;
+    if (nwin < 0 || G < 0 || !ge_klen(kmer_len) || blank < 0 || npos < 0) return SLK_ERR_INVALID_ARG;
     if (npos == 0) return SLK_OK;
     if (nwin < 1 || !genome || !win_off || !w0 || !w1 || !minus || !pos_off || !seq) return SLK_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(window_kmers_kernel, dim3(pg_blocks(npos)), dim3(PG_THREADS), 0, slk_stream(stream), genome, (long long)G, win_off,
+    hipLaunchKernelGGL(window_kmers_kernel, dim3(ge_blocks(npos)), dim3(GE_THREADS), 0, slk_stream(stream), genome, (long long)G, win_off,
                        w0, w1, minus, nwin, kmer_len, blank, pos_off, (long long)npos, seq);
     return slk_launch_status();
 }
@@ -610,7 +505,7 @@ extern "C" int slk_polish_sum_gains_f64(const double *score, int nread, const do
     if (nread < 0 || ncand < 0 || region_start < 0 || P < 0) return SLK_ERR_INVALID_ARG;
     if (ncand == 0 || P == 0) return SLK_OK;
     if (!score || !ll_edit || !cand_pair || !cand_edit || !order || !gain || !support) return SLK_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(polish_sum_gains_kernel, dim3(pg_blocks(ncand)), dim3(PG_THREADS), 0, slk_stream(stream), score, nread, ll_edit,
+    hipLaunchKernelGGL(polish_sum_gains_kernel, dim3(ge_blocks(ncand)), dim3(GE_THREADS), 0, slk_stream(stream), score, nread, ll_edit,
                        cand_pair, cand_edit, order, (long long)ncand, (long long)region_start, (long long)P, gain, support);
     return slk_launch_status();
 }

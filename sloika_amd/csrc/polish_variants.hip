@@ -1,6 +1,9 @@
 // polish_variants.hip -- proposed variants of any length put to the reads' signal (design/polish_variants.md; the quantities are defined
 // in its section 1 and restated as plain loops in tests/polish_variants_ref.py).  The scoring kernels are f10b's, unchanged; this file
 // makes their candidates from a sorted variant list, sums their answers per variant and strand, and proposes the repeat-unit family.
+// The window, the edit as a replacement, its (start, ndel, new symbols) and the pieces of the sum kernel's walk are genome_edits.h's,
+// shared with polish_genome.hip; this file keeps the variant list and its status, which variants a window has and where they sit in
+// it, the nine sums of a variant and the repeat-unit family.
 //
 // Integer kernels but the sum; no LDS, no MFMA.  Every input is device data and is NOT trusted: no loop bound and no address depends
 // on a value that has not been checked in the same kernel.
@@ -13,18 +16,10 @@
 //   variant_sum_gains_kernel     one thread per candidate of the sorted list; the head of a segment of equal variants walks it in read
 //                                order and writes the nine values of the variant.  No floating-point atomics.
 //   repeat_variants_*_kernel     one thread per packed position: the tracts that start there and what they propose.
-#include "common.h"
+#include "genome_edits.h"
 
-#define PV_WAVES 4
-#define PV_THREADS 256
-#define PV_NONE (-1)
 #define PV_MAX_UNIT 4
 #define PV_MAX_CHANGE 8
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ int pv_digit(int c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
-__device__ __forceinline__ int pv_comp(int c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c; }
 
 // the variant list as the entries take it
 struct pv_list {
@@ -39,20 +34,16 @@ struct pv_list {
 
 // ---- 1. the variants themselves ------------------------------------------------------------------------------------------------------
 
-__global__ void __launch_bounds__(PV_THREADS) variant_status_kernel(
+__global__ void __launch_bounds__(GE_THREADS) variant_status_kernel(
     pv_list L, const uint8_t *__restrict__ genome, long long G, const int64_t *__restrict__ contig_off, int ncontig,
     int32_t *__restrict__ var_status)
 {
-    const long long v = (long long)blockIdx.x * PV_THREADS + threadIdx.x;
+    const long long v = (long long)blockIdx.x * GE_THREADS + threadIdx.x;
     if (v >= L.V) return;
     const long long off = L.off[v], pos = L.pos[v], a0 = L.alt_off[v], a1 = L.alt_off[v + 1];
     const int nd = L.ndel[v];
     // the contig: the last c with contig_off[c] <= off; the table is device data too (its entries are clamped, not followed)
-    int lo = 0, hi = ncontig;
-    while (hi - lo > 1) {
-        const int mid = lo + (hi - lo) / 2;
-        if (contig_off[mid] <= off) lo = mid; else hi = mid;
-    }
+    const int lo = ge_find(contig_off, ncontig, off);
     const long long c0 = contig_off[lo], c1 = contig_off[lo + 1];
     int st = SLK_VARIANT_OK;
     if (c0 != off || c0 < 0 || c1 < c0 || c1 > G) st = SLK_VARIANT_CONTIG;
@@ -70,29 +61,6 @@ __global__ void __launch_bounds__(PV_THREADS) variant_status_kernel(
 
 // ---- 2. candidates from variants -----------------------------------------------------------------------------------------------------
 
-struct pv_win {
-    const uint8_t *g;          // the window's first forward letter
-    long long off, w0, w1;
-    int n;                     // letters
-    bool rev;
-    __device__ __forceinline__ int at(int u) const { return rev ? pv_comp(g[n - 1 - u]) : (int)g[u]; }
-};
-
-__device__ __forceinline__ bool pv_open(const uint8_t *__restrict__ genome, const int64_t *__restrict__ win_off,
-                                        const int64_t *__restrict__ w0, const int64_t *__restrict__ w1,
-                                        const int32_t *__restrict__ minus, int b, long long G, pv_win *w)
-{
-    const long long off = win_off[b], a = w0[b], e = w1[b];
-    if (off < 0 || a < 0 || e < a || off > G || e > G - off || e - a > 0x7ffffff0ll) return false;
-    w->g = genome + off + a;
-    w->off = off;
-    w->w0 = a;
-    w->w1 = e;
-    w->n = (int)(e - a);
-    w->rev = minus ? minus[b] != 0 : false;
-    return true;
-}
-
 // the first v of the sorted list with (off[v], pos[v]) >= (o, p)
 __device__ __forceinline__ long long pv_lower(const pv_list &L, long long o, long long p)
 {
@@ -107,7 +75,7 @@ __device__ __forceinline__ long long pv_lower(const pv_list &L, long long o, lon
 
 // Is variant v a candidate of window w?  Everything the emit and new kernels go on to use is checked here, whatever var_status says:
 // the variant's span inside the window's margins (so inside the genome), its alt slice inside alt and short enough, and a k-mer left.
-__device__ __forceinline__ bool pv_fits(const pv_list &L, const int32_t *__restrict__ var_status, long long v, const pv_win &w, int klen,
+__device__ __forceinline__ bool pv_fits(const pv_list &L, const int32_t *__restrict__ var_status, long long v, const ge_win &w, int klen,
                                         int margin)
 {
     if (v < 0 || v >= L.V || var_status[v] != SLK_VARIANT_OK || L.off[v] != w.off || w.n < klen) return false;
@@ -123,10 +91,10 @@ struct pv_edit {
     int u, nd, m;              // s' = s[:u] + alt + s[u + nd:]
     const uint8_t *alt;        // forward letters
     bool rev;
-    __device__ __forceinline__ int letter(int x) const { return rev ? pv_comp(alt[m - 1 - x]) : (int)alt[x]; }
+    __device__ __forceinline__ int letter(int x) const { return rev ? ge_comp(alt[m - 1 - x]) : (int)alt[x]; }
 };
 
-__device__ __forceinline__ pv_edit pv_place(const pv_list &L, long long v, const pv_win &w)
+__device__ __forceinline__ pv_edit pv_place(const pv_list &L, long long v, const ge_win &w)
 {
     pv_edit e;
     e.nd = L.ndel[v];
@@ -137,46 +105,10 @@ __device__ __forceinline__ pv_edit pv_place(const pv_list &L, long long v, const
     return e;
 }
 
-// letter i of the edited string
-__device__ __forceinline__ int pv_edited_at(const pv_win &w, const pv_edit &e, int i)
-{
-    return i < e.u ? w.at(i) : i < e.u + e.m ? e.letter(i - e.u) : w.at(i - e.m + e.nd);
-}
-
-// (start, ndel, number of new k-mers) of bio.edit_states for the window's string and its edit.  dF: the first letter at which the
-// strings differ read from the front, dB: the last letter of the OLD string at which they differ read from the back (PV_NONE: they
-// agree as far as the shorter goes).  Both searches start at the edit (the strings agree outside it by construction), run on along a
-// repeat and end at the window's ends at the latest.
-__device__ __forceinline__ void pv_triple(const pv_win &w, const pv_edit &e, int klen, int *start, int *ndel, int *nnew)
-{
-    const int n = w.n, n2 = n - e.nd + e.m, mn = n < n2 ? n : n2;
-    int i = e.u;
-    while (i < mn && w.at(i) == pv_edited_at(w, e, i)) i++;
-    const int dF = i < mn ? i : PV_NONE;
-    int t = n - e.u - e.nd;                                      // the letters behind the edit, equal in both
-    while (t < mn && w.at(n - 1 - t) == pv_edited_at(w, e, n2 - 1 - t)) t++;
-    const int dB = t < mn ? n - 1 - t : PV_NONE;
-    const int nold = n - klen + 1, nnw = n2 - klen + 1, nmin = nold < nnw ? nold : nnw;
-    int pre = nmin;
-    if (dF != PV_NONE) {
-        pre = dF - klen + 1 > 0 ? dF - klen + 1 : 0;
-        if (pre > nmin) pre = nmin;
-    }
-    const int rest = nmin - pre;
-    int suf = rest;
-    if (dB != PV_NONE) {
-        suf = nold - 1 - dB > 0 ? nold - 1 - dB : 0;
-        if (suf > rest) suf = rest;
-    }
-    *start = pre;
-    *ndel = nold - pre - suf;
-    *nnew = nnw - pre - suf;
-}
-
 // One wave walks the variants that start inside window b's margins, 64 at a time.  EMIT false: counts those that fit.  EMIT true:
 // writes them as candidates cand_off[b] .. in ascending variant order for a '+' window and descending for a '-' one.
 template <bool EMIT>
-__device__ __forceinline__ long long pv_walk(const pv_list &L, const int32_t *__restrict__ var_status, const pv_win &w, int b, int klen,
+__device__ __forceinline__ long long pv_walk(const pv_list &L, const int32_t *__restrict__ var_status, const ge_win &w, int b, int klen,
                                              int margin, long long base, long long total, int32_t *__restrict__ cand_pair,
                                              int32_t *__restrict__ cand_start, int32_t *__restrict__ cand_ndel,
                                              int32_t *__restrict__ cand_var, int64_t *__restrict__ cand_new_off)
@@ -195,7 +127,7 @@ __device__ __forceinline__ long long pv_walk(const pv_list &L, const int32_t *__
                 const long long i = base + (w.rev ? total - 1 - rank : rank);
                 const pv_edit e = pv_place(L, v, w);
                 int start, ndel, nnew;
-                pv_triple(w, e, klen, &start, &ndel, &nnew);
+                ge_triple(w, e, klen, &start, &ndel, &nnew);
                 cand_pair[i] = b;
                 cand_start[i] = start;
                 cand_ndel[i] = ndel;
@@ -208,20 +140,20 @@ __device__ __forceinline__ long long pv_walk(const pv_list &L, const int32_t *__
     return run;
 }
 
-__global__ void __launch_bounds__(64 * PV_WAVES) variant_edits_count_kernel(
+__global__ void __launch_bounds__(64 * GE_WAVES) variant_edits_count_kernel(
     pv_list L, const int32_t *__restrict__ var_status, const uint8_t *__restrict__ genome, long long G,
     const int64_t *__restrict__ win_off, const int64_t *__restrict__ w0, const int64_t *__restrict__ w1, int nwin, int klen, int margin,
     int64_t *__restrict__ ncand, int64_t *__restrict__ nkmer)
 {
-    const int b = blockIdx.x * PV_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int b = blockIdx.x * GE_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b == 0 && lane == 0) {
         ncand[0] = 0;
         nkmer[0] = 0;
     }
     if (b >= nwin) return;                                       // (whole waves)
-    pv_win w;
+    ge_win w;
     long long cnt = 0, km = 0;
-    if (pv_open(genome, win_off, w0, w1, nullptr, b, G, &w)) {
+    if (ge_open(genome, win_off, w0, w1, nullptr, b, G, &w)) {
         km = w.n < klen ? 0 : w.n - klen + 1;
         cnt = pv_walk<false>(L, var_status, w, b, klen, margin, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
     }
@@ -231,22 +163,22 @@ __global__ void __launch_bounds__(64 * PV_WAVES) variant_edits_count_kernel(
     }
 }
 
-__global__ void __launch_bounds__(64 * PV_WAVES) variant_edits_emit_kernel(
+__global__ void __launch_bounds__(64 * GE_WAVES) variant_edits_emit_kernel(
     pv_list L, const int32_t *__restrict__ var_status, const uint8_t *__restrict__ genome, long long G,
     const int64_t *__restrict__ win_off, const int64_t *__restrict__ w0, const int64_t *__restrict__ w1,
     const int32_t *__restrict__ minus, int nwin, int klen, int margin, const int64_t *__restrict__ cand_off, long long ncand,
     int32_t *__restrict__ cand_pair, int32_t *__restrict__ cand_start, int32_t *__restrict__ cand_ndel, int32_t *__restrict__ cand_var,
     int64_t *__restrict__ cand_new_off)
 {
-    const int b = blockIdx.x * PV_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int b = blockIdx.x * GE_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b == 0 && lane == 0) cand_new_off[0] = 0;
     if (b >= nwin) return;
     const long long base = cand_off[b], total = cand_off[b + 1] - base;
     if (base < 0 || total <= 0 || total > ncand - base) return;   // (its share of the list lies inside the list)
-    pv_win w;
+    ge_win w;
     long long got = 0;
     bool rev = false;
-    if (pv_open(genome, win_off, w0, w1, minus, b, G, &w)) {
+    if (ge_open(genome, win_off, w0, w1, minus, b, G, &w)) {
         rev = w.rev;
         got = pv_walk<true>(L, var_status, w, b, klen, margin, base, total, cand_pair, cand_start, cand_ndel, cand_var, cand_new_off);
     }
@@ -261,76 +193,55 @@ __global__ void __launch_bounds__(64 * PV_WAVES) variant_edits_emit_kernel(
     }
 }
 
-// the posterior column of the k-mer of `klen` letters read through `at`; -1 when a letter is none of A C G T
-template <typename F>
-__device__ __forceinline__ int pv_column(F at, int first, int klen, int blank)
-{
-    int s = 0;
-    bool bad = false;
-    for (int d = 0; d < klen; d++) {
-        const int x = pv_digit(at(first + d));
-        bad |= x < 0;
-        s = s * 4 + (x & 3);
-    }
-    return bad ? -1 : s + (s >= blank ? 1 : 0);
-}
-
-__global__ void __launch_bounds__(PV_THREADS) variant_edits_new_kernel(
+__global__ void __launch_bounds__(GE_THREADS) variant_edits_new_kernel(
     pv_list L, const int32_t *__restrict__ var_status, const uint8_t *__restrict__ genome, long long G,
     const int64_t *__restrict__ win_off, const int64_t *__restrict__ w0, const int64_t *__restrict__ w1,
     const int32_t *__restrict__ minus, int nwin, int klen, int blank, int margin, long long ncand,
     const int32_t *__restrict__ cand_pair, const int32_t *__restrict__ cand_start, const int32_t *__restrict__ cand_var,
     const int64_t *__restrict__ cand_new_off, long long new_cap, int32_t *__restrict__ cand_new)
 {
-    const long long i = (long long)blockIdx.x * PV_THREADS + threadIdx.x;
+    const long long i = (long long)blockIdx.x * GE_THREADS + threadIdx.x;
     if (i >= ncand) return;
     const int b = cand_pair[i];
     const long long v = cand_var[i];
-    pv_win w;
-    if (b < 0 || b >= nwin || !pv_open(genome, win_off, w0, w1, minus, b, G, &w) || !pv_fits(L, var_status, v, w, klen, margin)) return;
-    const pv_edit e = pv_place(L, v, w);
-    const int start = cand_start[i], n2 = w.n - e.nd + e.m;
-    const long long a = cand_new_off[i], m = cand_new_off[i + 1] - a;
-    if (start < 0 || m < 0 || m > SLK_RESCORE_MAX_NEW || a < 0 || a + m > new_cap || start + m + klen - 1 > n2) return;
-    for (int x = 0; x < (int)m; x++)
-        cand_new[a + x] = pv_column([&](int j) { return pv_edited_at(w, e, j); }, start + x, klen, blank);
+    ge_win w;
+    if (b < 0 || b >= nwin || !ge_open(genome, win_off, w0, w1, minus, b, G, &w) || !pv_fits(L, var_status, v, w, klen, margin)) return;
+    ge_write_new(w, pv_place(L, v, w), klen, blank, cand_start[i], cand_new_off + i, new_cap, SLK_RESCORE_MAX_NEW, cand_new);
 }
 
 // ---- 3. the reads' gains per variant and strand --------------------------------------------------------------------------------------
 
 // order: the candidates sorted by (variant, read), the host's sort.  The thread of a segment's first entry walks the segment: every sum
 // is taken in read order whatever the launch's shape, and continues from what the cell holds.
-__global__ void __launch_bounds__(PV_THREADS) variant_sum_gains_kernel(
+__global__ void __launch_bounds__(GE_THREADS) variant_sum_gains_kernel(
     const double *__restrict__ score, const int32_t *__restrict__ read_minus, int nread, const double *__restrict__ ll_edit,
     const int32_t *__restrict__ cand_read, const int32_t *__restrict__ cand_var, const int64_t *__restrict__ order, long long ncand,
     long long V, double *__restrict__ gain, int32_t *__restrict__ support, int32_t *__restrict__ pro, double *__restrict__ gain_strand,
     int32_t *__restrict__ support_strand, int32_t *__restrict__ pro_strand)
 {
-    const long long i = (long long)blockIdx.x * PV_THREADS + threadIdx.x;
+    const long long i = (long long)blockIdx.x * GE_THREADS + threadIdx.x;
     if (i >= ncand) return;
     const long long ci = order[i];
-    if (ci < 0 || ci >= ncand) return;
+    if (!ge_listed(ci, ncand)) return;
     const long long v = cand_var[ci];
-    if (i > 0) {
-        const long long cp = order[i - 1];
-        if (cp >= 0 && cp < ncand && cand_var[cp] == v) return;          // (not the head of its segment)
-    }
+    if (!ge_segment_head(order, ncand, i, cand_var, (int32_t)v)) return;
     if (v < 0 || v >= V) return;
     double sum = gain[v], ss0 = gain_strand[2 * v], ss1 = gain_strand[2 * v + 1];
     int cnt = support[v], np = pro[v], sc0 = support_strand[2 * v], sc1 = support_strand[2 * v + 1], sp0 = pro_strand[2 * v],
         sp1 = pro_strand[2 * v + 1];
     for (long long x = i; x < ncand; x++) {
         const long long c = order[x];
-        if (c < 0 || c >= ncand || cand_var[c] != v) break;
+        if (!ge_listed(c, ncand) || cand_var[c] != v) break;
         const int r = cand_read[c];
         const bool known = r >= 0 && r < nread;
         const double l = ll_edit[c], s = known ? score[r] : __builtin_nan("");
         const bool rev = known && read_minus[r] != 0;
-        if (l != l || s != s) {                                  // a refused candidate or pair: the cells say so
+        const int what = ge_classify(l, s);
+        if (what == GE_PAIR_NAN) {                               // the cells say so
             sum = __builtin_nan("");
             if (known && rev) ss1 = __builtin_nan("");
             else if (known) ss0 = __builtin_nan("");
-        } else if (l - l == 0.0 && s - s == 0.0) {               // both finite
+        } else if (what == GE_PAIR_FINITE) {
             const double d = l - s;
             const int up = d > 0.0 ? 1 : 0;
             sum += d;
@@ -357,7 +268,7 @@ __device__ __forceinline__ long long pv_tract(const uint8_t *__restrict__ c, lon
 {
     if (p + 2 * u > n) return 0;                                 // (i) needs two copies inside the contig
     for (int i = 0; i < u; i++)
-        if (pv_digit(c[p + i]) < 0 || c[p + i] != c[p + i + u]) return 0;
+        if (ge_digit(c[p + i]) < 0 || c[p + i] != c[p + i + u]) return 0;
     if (p > 0 && c[p - 1] == c[p - 1 + u]) return 0;             // (ii) leftmost
     if (u == 2 && c[p] == c[p + 1]) return 0;                    // (iii) primitive
     if (u == 3 && c[p] == c[p + 1] && c[p + 1] == c[p + 2]) return 0;
@@ -377,11 +288,7 @@ __device__ __forceinline__ void pv_propose(const uint8_t *__restrict__ genome, l
 {
     *nprop = 0;
     *nalt = 0;
-    int lo = 0, hi = ncontig;
-    while (hi - lo > 1) {
-        const int mid = lo + (hi - lo) / 2;
-        if (contig_off[mid] <= g) lo = mid; else hi = mid;
-    }
+    const int lo = ge_find(contig_off, ncontig, g);
     const long long c0 = contig_off[lo], c1 = contig_off[lo + 1];
     if (c0 < 0 || c0 > g || c1 <= g || c1 > G) return;            // (the table is device data: g lies in no contig it names)
     const uint8_t *c = genome + c0;
@@ -417,11 +324,11 @@ __device__ __forceinline__ void pv_propose(const uint8_t *__restrict__ genome, l
     *nalt = na;
 }
 
-__global__ void __launch_bounds__(PV_THREADS) repeat_variants_count_kernel(
+__global__ void __launch_bounds__(GE_THREADS) repeat_variants_count_kernel(
     const uint8_t *__restrict__ genome, long long G, const int64_t *__restrict__ contig_off, int ncontig, long long lo, long long P,
     int max_alt, int max_unit, int max_change, int min_copies, int64_t *__restrict__ nprop, int64_t *__restrict__ nalt)
 {
-    const long long t = (long long)blockIdx.x * PV_THREADS + threadIdx.x;
+    const long long t = (long long)blockIdx.x * GE_THREADS + threadIdx.x;
     if (t == 0) {
         nprop[0] = 0;
         nalt[0] = 0;
@@ -434,13 +341,13 @@ __global__ void __launch_bounds__(PV_THREADS) repeat_variants_count_kernel(
     nalt[t + 1] = na;
 }
 
-__global__ void __launch_bounds__(PV_THREADS) repeat_variants_emit_kernel(
+__global__ void __launch_bounds__(GE_THREADS) repeat_variants_emit_kernel(
     const uint8_t *__restrict__ genome, long long G, const int64_t *__restrict__ contig_off, int ncontig, long long lo, long long P,
     int max_alt, int max_unit, int max_change, int min_copies, const int64_t *__restrict__ prop_off, const int64_t *__restrict__ alt_off,
     long long V, long long A, int64_t *__restrict__ var_off, int64_t *__restrict__ var_pos, int32_t *__restrict__ var_ndel,
     int64_t *__restrict__ var_alt_off, uint8_t *__restrict__ var_alt)
 {
-    const long long t = (long long)blockIdx.x * PV_THREADS + threadIdx.x;
+    const long long t = (long long)blockIdx.x * GE_THREADS + threadIdx.x;
     if (t == 0) var_alt_off[0] = 0;
     if (t >= P) return;
     const long long vi = prop_off[t], ai = alt_off[t], nv = prop_off[t + 1] - vi, nl = alt_off[t + 1] - ai;
@@ -455,14 +362,10 @@ __global__ void __launch_bounds__(PV_THREADS) repeat_variants_emit_kernel(
 
 // ---- entries -------------------------------------------------------------------------------------------------------------------------
 
-static inline unsigned pv_blocks(long long n) { return (unsigned)((n + PV_THREADS - 1) / PV_THREADS); }
-
-static inline bool pv_klen(int klen) { return klen >= 3 && klen <= SLK_RESCORE_MAX_NEW - 1; }
-
 static inline bool pv_make_list(const int64_t *var_off, const int64_t *var_pos, const int32_t *var_ndel, const int64_t *var_alt_off,
                                 const uint8_t *var_alt, int64_t V, int64_t A, int klen, pv_list *L)
 {
-    if (V < 0 || A < 0 || V > 0x7ffffff0ll || !pv_klen(klen) || !var_alt_off) return false;
+    if (V < 0 || A < 0 || V > 0x7ffffff0ll || !ge_klen(klen) || !var_alt_off) return false;
     if (V > 0 && (!var_off || !var_pos || !var_ndel)) return false;
     if (A > 0 && !var_alt) return false;
     L->off = var_off;
@@ -487,11 +390,11 @@ extern "C" int slk_variant_edits_count(const uint8_t *genome, long G, const int6
     if (nwin < 0 || G < 0 || ncontig < 1 || margin < 0 || !contig_off || !ncand || !nkmer) return SLK_ERR_INVALID_ARG;
     if ((V > 0 && (!var_status || !genome)) || (nwin > 0 && (!win_off || !w0 || !w1 || !genome))) return SLK_ERR_INVALID_ARG;
     if (V > 0) {
-        hipLaunchKernelGGL(variant_status_kernel, dim3(pv_blocks(V)), dim3(PV_THREADS), 0, slk_stream(stream), L, genome, (long long)G,
+        hipLaunchKernelGGL(variant_status_kernel, dim3(ge_blocks(V)), dim3(GE_THREADS), 0, slk_stream(stream), L, genome, (long long)G,
                            contig_off, ncontig, var_status);
         if (slk_launch_status() != SLK_OK) return SLK_ERR_LAUNCH;
     }
-    hipLaunchKernelGGL(variant_edits_count_kernel, dim3(nwin > 0 ? (nwin + PV_WAVES - 1) / PV_WAVES : 1), dim3(64 * PV_WAVES), 0,
+    hipLaunchKernelGGL(variant_edits_count_kernel, dim3(nwin > 0 ? (nwin + GE_WAVES - 1) / GE_WAVES : 1), dim3(64 * GE_WAVES), 0,
                        slk_stream(stream), L, var_status, genome, (long long)G, win_off, w0, w1, nwin, kmer_len, margin, ncand, nkmer);
     return slk_launch_status();
 }
@@ -509,7 +412,7 @@ extern "C" int slk_variant_edits_emit(const uint8_t *genome, long G, const int64
     if (ncand > 0 && (nwin < 1 || V < 1 || !genome || !var_status || !win_off || !w0 || !w1 || !minus || !cand_off || !cand_pair ||
                       !cand_start || !cand_ndel || !cand_var))
         return SLK_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(variant_edits_emit_kernel, dim3(ncand > 0 ? (nwin + PV_WAVES - 1) / PV_WAVES : 1), dim3(64 * PV_WAVES), 0,
+    hipLaunchKernelGGL(variant_edits_emit_kernel, dim3(ncand > 0 ? (nwin + GE_WAVES - 1) / GE_WAVES : 1), dim3(64 * GE_WAVES), 0,
                        slk_stream(stream), L, var_status, genome, (long long)G, win_off, w0, w1, minus, ncand > 0 ? nwin : 0, kmer_len,
                        margin, cand_off, (long long)ncand, cand_pair, cand_start, cand_ndel, cand_var, cand_new_off);
     return slk_launch_status();
@@ -529,7 +432,7 @@ extern "C" int slk_variant_edits_new(const uint8_t *genome, long G, const int64_
     if (nwin < 1 || V < 1 || !genome || !var_status || !win_off || !w0 || !w1 || !minus || !cand_pair || !cand_start || !cand_var ||
         !cand_new_off || !cand_new)
         return SLK_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(variant_edits_new_kernel, dim3(pv_blocks(ncand)), dim3(PV_THREADS), 0, slk_stream(stream), L, var_status, genome,
+    hipLaunchKernelGGL(variant_edits_new_kernel, dim3(ge_blocks(ncand)), dim3(GE_THREADS), 0, slk_stream(stream), L, var_status, genome,
                        (long long)G, win_off, w0, w1, minus, nwin, kmer_len, blank, margin, (long long)ncand, cand_pair, cand_start,
                        cand_var, cand_new_off, (long long)new_cap, cand_new);
     return slk_launch_status();
@@ -545,7 +448,7 @@ extern "C" int slk_polish_sum_variant_gains_f64(const double *score, const int32
     if (!score || !read_minus || !ll_edit || !cand_read || !cand_var || !order || !gain || !support || !pro || !gain_strand ||
         !support_strand || !pro_strand)
         return SLK_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(variant_sum_gains_kernel, dim3(pv_blocks(ncand)), dim3(PV_THREADS), 0, slk_stream(stream), score, read_minus, nread,
+    hipLaunchKernelGGL(variant_sum_gains_kernel, dim3(ge_blocks(ncand)), dim3(GE_THREADS), 0, slk_stream(stream), score, read_minus, nread,
                        ll_edit, cand_read, cand_var, order, (long long)ncand, (long long)V, gain, support, pro, gain_strand,
                        support_strand, pro_strand);
     return slk_launch_status();
@@ -553,7 +456,7 @@ extern "C" int slk_polish_sum_variant_gains_f64(const double *score, const int32
 
 static inline bool pv_repeat_args(long G, int ncontig, int64_t lo, int64_t P, int klen, int max_unit, int max_change, int min_copies)
 {
-    return G >= 0 && ncontig >= 1 && lo >= 0 && P >= 0 && lo <= G && P <= G - lo && pv_klen(klen) && max_unit >= 1 &&
+    return G >= 0 && ncontig >= 1 && lo >= 0 && P >= 0 && lo <= G && P <= G - lo && ge_klen(klen) && max_unit >= 1 &&
            max_unit <= PV_MAX_UNIT && max_change >= 1 && max_change <= PV_MAX_CHANGE && min_copies >= 2;
 }
 
@@ -564,7 +467,7 @@ extern "C" int slk_repeat_variants_count(const uint8_t *genome, long G, const in
     if (!pv_repeat_args(G, ncontig, lo, P, kmer_len, max_unit, max_change, min_copies) || !contig_off || !nprop || !nalt)
         return SLK_ERR_INVALID_ARG;
     if (P > 0 && !genome) return SLK_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(repeat_variants_count_kernel, dim3(pv_blocks(P > 0 ? P : 1)), dim3(PV_THREADS), 0, slk_stream(stream), genome,
+    hipLaunchKernelGGL(repeat_variants_count_kernel, dim3(ge_blocks(P > 0 ? P : 1)), dim3(GE_THREADS), 0, slk_stream(stream), genome,
                        (long long)G, contig_off, ncontig, (long long)lo, (long long)P, SLK_RESCORE_MAX_NEW - kmer_len + 1, max_unit,
                        max_change, min_copies, nprop, nalt);
     return slk_launch_status();
@@ -579,7 +482,7 @@ extern "C" int slk_repeat_variants_emit(const uint8_t *genome, long G, const int
         return SLK_ERR_INVALID_ARG;
     if (V > 0 && (!genome || !prop_off || !alt_off || !var_off || !var_pos || !var_ndel)) return SLK_ERR_INVALID_ARG;
     if (A > 0 && !var_alt) return SLK_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(repeat_variants_emit_kernel, dim3(pv_blocks(V > 0 && P > 0 ? P : 1)), dim3(PV_THREADS), 0, slk_stream(stream),
+    hipLaunchKernelGGL(repeat_variants_emit_kernel, dim3(ge_blocks(V > 0 && P > 0 ? P : 1)), dim3(GE_THREADS), 0, slk_stream(stream),
                        genome, (long long)G, contig_off, ncontig, (long long)lo, V > 0 ? (long long)P : 0ll, SLK_RESCORE_MAX_NEW - kmer_len + 1,
                        max_unit, max_change, min_copies, prop_off, alt_off, (long long)V, (long long)A, var_off, var_pos, var_ndel,
                        var_alt_off, var_alt);

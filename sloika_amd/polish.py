@@ -206,6 +206,46 @@ def _check_kmer_len(kmer_len):
         raise ValueError("kmer_len = %r outside 3 .. %d (an edit may bring kmer_len + 1 new symbols)" % (kmer_len, decode.rescore_max_new() - 1))
 
 
+def _candidate_list(who, genome, win_off, w0, w1, minus, kmer_len, blank, margin, extra, extra_dtype, max_new, count, emit, new):
+    """What letter_edits and variant_edits share: the candidates of a batch of windows laid out as the rescoring entries read them.
+    count(L, ncand, nkmer, st), emit(L, c, new_off, st), new(L, c, cap, st) call the caller's three entries (pointers but `c`, the
+    namespace so far); `extra` names the caller's own column of the list, of `extra_dtype`; a candidate has at most max_new new
+    symbols.  One round trip, for the totals."""
+    import types
+    import torch
+    from . import _lib, device as D
+    nwin, G = int(win_off.numel()), int(genome.numel())
+    if margin < 0 or blank < 0:
+        raise ValueError("margin and blank are not negative")
+    dev = genome.device
+    for name, t, dt in (("win_off", win_off, torch.int64), ("w0", w0, torch.int64), ("w1", w1, torch.int64), ("minus", minus, torch.int32)):
+        if t.dtype != dt or t.device != dev or t.numel() != nwin or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous %s device tensor with one entry per window" % (who, name, dt))
+    L, st = _lib.lib(), D.stream_ptr()
+    offs = torch.empty((2, nwin + 1), dtype=torch.int64, device=dev)
+    _lib.check(count(L, offs[0].data_ptr(), offs[1].data_ptr(), st), who + "_count")
+    offs = torch.cumsum(offs, 1)
+    host = offs.cpu().numpy()                                     # the round trip: the totals (and the per-window counts with them)
+    ncand, npos = int(host[0, -1]), int(host[1, -1])
+    c = types.SimpleNamespace(cand_off=offs[0], pos_off=offs[1], cand_off_host=host[0].copy(), pos_off_host=host[1].copy(), ncand=ncand,
+                              npos=npos)
+    c.cand_pair = torch.empty(max(ncand, 1), dtype=torch.int32, device=dev)
+    c.cand_start, c.cand_ndel = torch.empty_like(c.cand_pair), torch.empty_like(c.cand_pair)
+    setattr(c, extra, torch.empty(max(ncand, 1), dtype=extra_dtype, device=dev))
+    new_off = torch.zeros(ncand + 1, dtype=torch.int64, device=dev)
+    _lib.check(emit(L, c, new_off.data_ptr(), st), who + "_emit")
+    c.cand_new_off = torch.cumsum(new_off, 0)
+    cap = max(ncand * max_new, 1)                                 # (no second round trip for the exact total)
+    c.cand_new = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+    _lib.check(new(L, c, cap, st), who + "_new")
+    c.seq = torch.empty(max(npos, 1), dtype=torch.int32, device=dev)
+    _lib.check(L.slk_polish_window_kmers(genome.data_ptr(), G, win_off.data_ptr(), w0.data_ptr(), w1.data_ptr(), minus.data_ptr(), nwin,
+                                         kmer_len, int(blank), c.pos_off.data_ptr(), npos, c.seq.data_ptr(), st), "polish_window_kmers")
+    for name in ("cand_pair", "cand_start", "cand_ndel", extra):
+        setattr(c, name, getattr(c, name)[:ncand])
+    return c
+
+
 def letter_edits(genome, win_off, w0, w1, minus, kmer_len, blank=0, kinds=bio.EDIT_KINDS, margin=0):
     """Every single-letter edit of a batch of windows of the packed genome, made on the device in the layout the rescoring entries read
     (slk_letter_edits_count / _emit / _new, slk_polish_window_kmers).  genome: uint8 device tensor (Index.genome); win_off, w0, w1:
@@ -214,42 +254,18 @@ def letter_edits(genome, win_off, w0, w1, minus, kmer_len, blank=0, kinds=bio.ED
     -> namespace: cand_off, pos_off (device int64 [nwin + 1]) and their host copies cand_off_host, pos_off_host (the one round trip);
     cand_pair, cand_start, cand_ndel (int32), cand_new_off (int64), cand_new (int32), cand_edit (int64 = 8 * packed forward position
     + slot: 0-2 substitutions in alphabet order without the draft's letter, 3 deletion, 4-7 insertions in front); seq (int32)."""
-    import types
     import torch
-    from . import _lib, device as D
     _check_kmer_len(kmer_len)
     mask, margin, nwin, G = kinds_mask(kinds), int(margin), int(win_off.numel()), int(genome.numel())
-    if margin < 0 or blank < 0:
-        raise ValueError("margin and blank are not negative")
-    dev = genome.device
-    for name, t, dt in (("win_off", win_off, torch.int64), ("w0", w0, torch.int64), ("w1", w1, torch.int64), ("minus", minus, torch.int32)):
-        if t.dtype != dt or t.device != dev or t.numel() != nwin or not t.is_contiguous():
-            raise ValueError("letter_edits: %s must be a contiguous %s device tensor with one entry per window" % (name, dt))
-    L, st = _lib.lib(), D.stream_ptr()
-    offs = torch.empty((2, nwin + 1), dtype=torch.int64, device=dev)
-    _lib.check(L.slk_letter_edits_count(win_off.data_ptr(), w0.data_ptr(), w1.data_ptr(), nwin, G, kmer_len, mask, margin,
-                                        offs[0].data_ptr(), offs[1].data_ptr(), st), "letter_edits_count")
-    offs = torch.cumsum(offs, 1)
-    host = offs.cpu().numpy()                                     # the round trip: the totals (and the per-window counts with them)
-    ncand, npos = int(host[0, -1]), int(host[1, -1])
-    c = types.SimpleNamespace(cand_off=offs[0], pos_off=offs[1], cand_off_host=host[0].copy(), pos_off_host=host[1].copy(), ncand=ncand,
-                              npos=npos)
-    c.cand_pair = torch.empty(max(ncand, 1), dtype=torch.int32, device=dev)
-    c.cand_start, c.cand_ndel = torch.empty_like(c.cand_pair), torch.empty_like(c.cand_pair)
-    c.cand_edit = torch.empty(max(ncand, 1), dtype=torch.int64, device=dev)
-    new_off = torch.zeros(ncand + 1, dtype=torch.int64, device=dev)
-    head = (genome.data_ptr(), G, win_off.data_ptr(), w0.data_ptr(), w1.data_ptr(), minus.data_ptr(), nwin, kmer_len)
-    _lib.check(L.slk_letter_edits_emit(*head, mask, margin, c.cand_off.data_ptr(), ncand, c.cand_pair.data_ptr(), c.cand_start.data_ptr(),
-                                       c.cand_ndel.data_ptr(), new_off.data_ptr(), c.cand_edit.data_ptr(), st), "letter_edits_emit")
-    c.cand_new_off = torch.cumsum(new_off, 0)
-    cap = max(ncand * (kmer_len + 1), 1)                          # (no second round trip for the exact total)
-    c.cand_new = torch.full((cap,), -1, dtype=torch.int32, device=dev)
-    _lib.check(L.slk_letter_edits_new(*head, int(blank), mask, margin, c.cand_off.data_ptr(), ncand, c.cand_start.data_ptr(),
-                                      c.cand_new_off.data_ptr(), cap, c.cand_new.data_ptr(), st), "letter_edits_new")
-    c.seq = torch.empty(max(npos, 1), dtype=torch.int32, device=dev)
-    _lib.check(L.slk_polish_window_kmers(*head, int(blank), c.pos_off.data_ptr(), npos, c.seq.data_ptr(), st), "polish_window_kmers")
-    c.cand_pair, c.cand_start, c.cand_ndel, c.cand_edit = c.cand_pair[:ncand], c.cand_start[:ncand], c.cand_ndel[:ncand], c.cand_edit[:ncand]
-    return c
+    wins = (win_off.data_ptr(), w0.data_ptr(), w1.data_ptr())
+    head = (genome.data_ptr(), G) + wins + (minus.data_ptr(), nwin, kmer_len)
+    return _candidate_list(
+        "letter_edits", genome, win_off, w0, w1, minus, kmer_len, blank, margin, "cand_edit", torch.int64, kmer_len + 1,
+        lambda L, ncand, nkmer, st: L.slk_letter_edits_count(*wins, nwin, G, kmer_len, mask, margin, ncand, nkmer, st),
+        lambda L, c, new_off, st: L.slk_letter_edits_emit(*head, mask, margin, c.cand_off.data_ptr(), c.ncand, c.cand_pair.data_ptr(),
+                                                          c.cand_start.data_ptr(), c.cand_ndel.data_ptr(), new_off, c.cand_edit.data_ptr(), st),
+        lambda L, c, cap, st: L.slk_letter_edits_new(*head, int(blank), mask, margin, c.cand_off.data_ptr(), c.ncand, c.cand_start.data_ptr(),
+                                                     c.cand_new_off.data_ptr(), cap, c.cand_new.data_ptr(), st))
 
 
 def sum_gains(score, ll_edit, cand_read, cand_edit, region_start, P, gain=None, support=None):
@@ -431,6 +447,37 @@ def _read_bands(w, reads, npos, width, B, dev):
     return nrow, band, row_off
 
 
+def _rescore_windows(who, post, steps, paths, lens, move_row, index, res, strand, info, ops, kmer_len, width, margin, keep, blank,
+                     min_prob, workspace_limit, candidates):
+    """What rescore_genome and rescore_variants share: the reads' windows (read_windows), the candidates of those that have one --
+    candidates(win_off, w0, w1, minus, margin=) -> letter_edits' or variant_edits' namespace --, their bands and the banded entry.
+    -> (w the read_windows result, score float64 [B], NaN for a read left out, c, cand_read int32, ll_edit float64); without a read
+    to score the candidates of no window and no values."""
+    import torch
+    _check_kmer_len(kmer_len)
+    if post.dim() != 3 or int(post.shape[2]) != 4 ** kmer_len + 1:
+        raise ValueError("%s takes a [rows, reads, %d] transducer posterior of %d-mers" % (who, 4 ** kmer_len + 1, kmer_len))
+    B = int(post.shape[1])
+    if len(ops) != B or len(res) != B:
+        raise ValueError("%s: %d reads in the posterior, %d alignments" % (who, B, len(ops)))
+    margin = 2 * int(kmer_len) if margin is None else int(margin)
+    pd = post if post.is_contiguous() else post.contiguous()
+    dev = pd.device
+    w = read_windows(paths, lens, move_row, steps, ops, strand, info, index, kmer_len, keep)
+    reads = np.flatnonzero(w.status == READ_DONE)
+    score = torch.full((B,), float('nan'), dtype=torch.float64, device=dev)
+    c = candidates(*_window_tensors(w, reads, dev), margin=margin)
+    if not len(reads):
+        return w, score, c, torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.float64, device=dev)
+    reads_d = torch.from_numpy(np.ascontiguousarray(reads.astype(np.int64))).to(dev)
+    nrow, band, row_off = _read_bands(w, reads, np.diff(c.pos_off_host), width, B, dev)
+    sc, ll = decode.rescore_edits_banded_device(pd, row_off, B, nrow.astype(np.int32), c.seq, c.pos_off, band, width, c.cand_off_host,
+                                                c.cand_pair, c.cand_start, c.cand_ndel, c.cand_new_off, c.cand_new, blank=blank,
+                                                min_prob=min_prob, workspace_limit=workspace_limit)
+    score[reads_d] = sc
+    return w, score, c, reads_d[c.cand_pair.to(torch.int64)].to(torch.int32), ll
+
+
 def rescore_genome(post, steps, paths, lens, move_row, index, res, strand, info, ops, kmer_len, width=512, margin=None,
                    kinds=bio.EDIT_KINDS, keep=None, region=None, blank=0, min_prob=None, workspace_limit=None):
     """Score every single-letter edit of a genome under the signal of the reads mapped to it, and sum on genome coordinates.
@@ -445,34 +492,11 @@ def rescore_genome(post, steps, paths, lens, move_row, index, res, strand, info,
     (sum_gains).  keep: bool mask of the reads to use (info['edge'] == 0 is the usual filter).  region: (contig, start, end) or None
     for the whole genome: the cells to sum; a slice gives the slice of the whole.  A read that is unmapped, fails keep or whose band
     cannot be laid is reported in `status`, never raised.  -> GenomeRescored."""
-    import torch
     from . import genome as G
-    _check_kmer_len(kmer_len)
-    if post.dim() != 3 or int(post.shape[2]) != 4 ** kmer_len + 1:
-        raise ValueError("rescore_genome takes a [rows, reads, %d] transducer posterior of %d-mers" % (4 ** kmer_len + 1, kmer_len))
-    B = int(post.shape[1])
-    if len(ops) != B or len(res) != B:
-        raise ValueError("rescore_genome: %d reads in the posterior, %d alignments" % (B, len(ops)))
-    margin = 2 * int(kmer_len) if margin is None else int(margin)
-    pd = post if post.is_contiguous() else post.contiguous()
-    dev = pd.device
     lo, P = G.region_span(index, region)
-    w = read_windows(paths, lens, move_row, steps, ops, strand, info, index, kmer_len, keep)
-    reads = np.flatnonzero(w.status == READ_DONE)
-    score = torch.full((B,), float('nan'), dtype=torch.float64, device=dev)
-    empty = lambda dt: torch.zeros(0, dtype=dt, device=dev)
-    if not len(reads):
-        gain, support = sum_gains(score, empty(torch.float64), empty(torch.int32), empty(torch.int64), lo, P)
-        return GenomeRescored(index, lo, P, kmer_len, gain, support, w.status, score, w.span, w.window, empty(torch.int32),
-                              empty(torch.int64), empty(torch.float64))
-    reads_d = torch.from_numpy(np.ascontiguousarray(reads.astype(np.int64))).to(dev)
-    c = letter_edits(index.genome, *_window_tensors(w, reads, dev), kmer_len, blank, kinds, margin)
-    nrow, band, row_off = _read_bands(w, reads, np.diff(c.pos_off_host), width, B, dev)
-    sc, ll = decode.rescore_edits_banded_device(pd, row_off, B, nrow.astype(np.int32), c.seq, c.pos_off, band, width, c.cand_off_host,
-                                                c.cand_pair, c.cand_start, c.cand_ndel, c.cand_new_off, c.cand_new, blank=blank,
-                                                min_prob=min_prob, workspace_limit=workspace_limit)
-    score[reads_d] = sc
-    cand_read = reads_d[c.cand_pair.to(torch.int64)].to(torch.int32)
+    w, score, c, cand_read, ll = _rescore_windows(
+        "rescore_genome", post, steps, paths, lens, move_row, index, res, strand, info, ops, kmer_len, width, margin, keep, blank, min_prob,
+        workspace_limit, lambda *wins, margin: letter_edits(index.genome, *wins, kmer_len, blank, kinds, margin))
     gain, support = sum_gains(score, ll, cand_read, c.cand_edit, lo, P)
     return GenomeRescored(index, lo, P, kmer_len, gain, support, w.status, score, w.span, w.window, cand_read, c.cand_edit, ll)
 
@@ -485,35 +509,14 @@ GenomePolished = collections.namedtuple("GenomePolished", "name sequence applied
 def letter_triple(seq, kind, pos, letter, kmer_len):
     """(start, ndel, new k-mer states) of a single-letter edit of a base string, as bio.edit_states gives it for the spelled-out
     strings, from the letters round the edit alone: two edits that spell the same string have the same triple."""
-    text = bio.apply_letter_edits(seq, [(kind, pos, letter)])
-    n, n2, k = len(seq), len(text), int(kmer_len)
-    m = min(n, n2)
-    # the first letter at which the strings differ read from the front, the last of `seq` at which they differ read from the back
-    front = next((i for i in range(max(pos - 1, 0), m) if seq[i] != text[i]), None)
-    back = next((j for j in range(min(pos, n - 1), n - m - 1, -1) if seq[j] != text[j + n2 - n]), None)
-    nold, nnew = n - k + 1, n2 - k + 1
-    nmin = min(nold, nnew)
-    pre = nmin if front is None else min(max(front - k + 1, 0), nmin)
-    rest = nmin - pre
-    suf = rest if back is None else min(max(nold - 1 - back, 0), rest)
-    new = bio.seq_to_states(text[pre:nnew - suf + k - 1], k) if nnew - suf > pre else np.zeros(0, dtype=np.int64)
-    return pre, nold - pre - suf, tuple(int(v) for v in new)
+    return variant_triple(seq, *_as_replacement(kind, pos, letter), kmer_len)
 
 
 def accept_genome_edits(cells, text, kmer_len):
     """One round's choice among the fetched cells (contig, pos, kind, letter, gain, support): accept_edits' order, (-gain, pos, kind,
     letter), and its spacing, at least kmer_len letters from every edit already taken on the same contig; a cell whose triple
     (letter_triple on the contig's string) an earlier cell of the round had is that edit again and is passed over."""
-    rank = dict((k, i) for i, k in enumerate(bio.EDIT_KINDS))
-    taken, seen = [], set()
-    for r in sorted(cells, key=lambda r: (-r[4], r[0], r[1], rank[r[2]], r[3])):
-        key = (r[0],) + letter_triple(text[r[0]], r[2], r[1], r[3], kmer_len)
-        if key in seen:
-            continue
-        seen.add(key)
-        if all(t[0] != r[0] or abs(t[1] - r[1]) >= kmer_len for t in taken):
-            taken.append(r)
-    return taken
+    return accept_genome_variants(cells, [], text, kmer_len)
 
 
 def polish_genome(post, steps, paths, lens, move_row, index, kmer_len, width=512, margin=None, kinds=bio.EDIT_KINDS, keep=None,
@@ -533,33 +536,44 @@ def polish_genome(post, steps, paths, lens, move_row, index, kmer_len, width=512
     rescore_variants on the same mapping and accept_genome_variants chooses over cells and variants together; `kinds=()` leaves the
     variants alone.  Applied variants are rows (round, pos, 'var', (ndel, alt), gain, support).
     -> ([GenomePolished], the last round's GenomeRescored or None without kinds, the last round's GenomeVariantsRescored)."""
-    if proposals is not None:
-        return _polish_genome_variants(post, steps, paths, lens, move_row, index, kmer_len, width, margin, kinds, keep, min_gain,
-                                       min_support, max_rounds, blank, min_prob, workspace_limit, map_kwargs, proposals)
     from . import genome as G
     kw = dict(map_kwargs or {})
     host = index.genome.cpu().numpy().tobytes().decode('ascii')
     text = collections.OrderedDict((n, host[int(a):int(b)]) for n, a, b in zip(index.names, index.offsets[:-1], index.offsets[1:]))
     applied = dict((n, []) for n in text)
     rounds = dict((n, 0) for n in text)
-    ix, last = index, None
+    ix, last, lastv = index, None, None
     for r in range(int(max_rounds)):
         got = ix.map_paths(paths, lens, kmer_len, ops=True, **kw)
         res, strand, info, ops = got[0], got[1], got[2], got[4]
         mask = keep(res, strand, info) if callable(keep) else keep
-        last = rescore_genome(post, steps, paths, lens, move_row, ix, res, strand, info, ops, kmer_len, width=width, margin=margin,
-                              kinds=kinds, keep=mask, blank=blank, min_prob=min_prob, workspace_limit=workspace_limit)
-        taken = accept_genome_edits(last.cells(min_gain, min_support), text, kmer_len)
+        common = dict(width=width, margin=margin, keep=mask, blank=blank, min_prob=min_prob, workspace_limit=workspace_limit)
+        cells, rows = [], []
+        if proposals is None or len(kinds):
+            last = rescore_genome(post, steps, paths, lens, move_row, ix, res, strand, info, ops, kmer_len, kinds=kinds, **common)
+            cells = last.cells(min_gain, min_support)
+        if proposals is not None:
+            asked = proposals(ix) if callable(proposals) else proposals if isinstance(proposals, str) or r == 0 else []
+            lastv = rescore_variants(post, steps, paths, lens, move_row, ix, res, strand, info, ops, kmer_len, asked, **common)
+            rows = lastv.rows(min_gain, min_support)
+        taken = accept_genome_variants(cells, rows, text, kmer_len)
         if not taken:
             break
         for name in text:
             mine = [t for t in taken if t[0] == name]
             if mine:
-                text[name] = bio.apply_letter_edits(text[name], [(t[2], t[1], t[3]) for t in mine])
+                s = text[name]
+                for t in sorted(mine, key=lambda t: t[1], reverse=True):    # (from the back: the positions in front stay)
+                    pos, ndel, alt = (t[1],) + tuple(t[3]) if t[2] == 'var' else _as_replacement(t[2], t[1], t[3])
+                    s = s[:pos] + alt + s[pos + ndel:]
+                text[name] = s
+                if proposals is not None:                          # (rows by position there, in the order taken here: as ever)
+                    mine.sort(key=lambda t: t[1])
                 applied[name].extend((r, t[1], t[2], t[3], t[4], t[5]) for t in mine)
                 rounds[name] += 1
         ix = G.Index(list(text.items()), k=index.k, bin_width=index.bin_width, max_occ=index.max_occ)
-    return [GenomePolished(n, text[n], applied[n], rounds[n]) for n in text], last
+    out = [GenomePolished(n, text[n], applied[n], rounds[n]) for n in text]
+    return (out, last) if proposals is None else (out, last, lastv)
 
 
 # ---- proposed variants of any length (csrc/polish_variants.hip, design/polish_variants.md) --------------------------------------------
@@ -718,49 +732,26 @@ def variant_edits(genome, contig_offsets, win_off, w0, w1, minus, variants_on_de
     VariantSet.  A window's candidates are the variants of its contig that lie `margin` letters inside it.
     -> the namespace letter_edits returns with cand_var (int32, the variant in the caller's order) in place of cand_edit, and
     var_status (int32 device [V], caller's order: 0 or a key of VARIANT_REASONS)."""
-    import types
     import torch
-    from . import _lib, device as D
     _check_kmer_len(kmer_len)
     vs, margin, nwin, G = variants_on_device, int(margin), int(win_off.numel()), int(genome.numel())
-    if margin < 0 or blank < 0:
-        raise ValueError("margin and blank are not negative")
     dev = genome.device
-    for name, t, dt in (("win_off", win_off, torch.int64), ("w0", w0, torch.int64), ("w1", w1, torch.int64), ("minus", minus, torch.int32)):
-        if t.dtype != dt or t.device != dev or t.numel() != nwin or not t.is_contiguous():
-            raise ValueError("variant_edits: %s must be a contiguous %s device tensor with one entry per window" % (name, dt))
     if contig_offsets.dtype != torch.int64 or contig_offsets.device != dev or contig_offsets.numel() < 2 or not contig_offsets.is_contiguous():
         raise ValueError("variant_edits: contig_offsets must be a contiguous int64 device tensor of the contigs' starts and the genome's length")
-    L, st = _lib.lib(), D.stream_ptr()
     lst = (vs.var_off.data_ptr(), vs.var_pos.data_ptr(), vs.var_ndel.data_ptr(), vs.var_alt_off.data_ptr(), vs.var_alt.data_ptr(), vs.V, vs.A)
     wins = (win_off.data_ptr(), w0.data_ptr(), w1.data_ptr())
     status = torch.zeros(max(vs.V, 1), dtype=torch.int32, device=dev)
-    offs = torch.empty((2, nwin + 1), dtype=torch.int64, device=dev)
-    _lib.check(L.slk_variant_edits_count(genome.data_ptr(), G, contig_offsets.data_ptr(), int(contig_offsets.numel()) - 1, *lst, *wins, nwin,
-                                         kmer_len, margin, status.data_ptr(), offs[0].data_ptr(), offs[1].data_ptr(), st),
-               "variant_edits_count")
-    offs = torch.cumsum(offs, 1)
-    host = offs.cpu().numpy()                                     # the round trip: the totals (and the per-window counts with them)
-    ncand, npos = int(host[0, -1]), int(host[1, -1])
-    c = types.SimpleNamespace(cand_off=offs[0], pos_off=offs[1], cand_off_host=host[0].copy(), pos_off_host=host[1].copy(), ncand=ncand,
-                              npos=npos)
-    c.cand_pair = torch.empty(max(ncand, 1), dtype=torch.int32, device=dev)
-    c.cand_start, c.cand_ndel, sorted_var = torch.empty_like(c.cand_pair), torch.empty_like(c.cand_pair), torch.empty_like(c.cand_pair)
-    new_off = torch.zeros(ncand + 1, dtype=torch.int64, device=dev)
     head = (genome.data_ptr(), G) + lst + (status.data_ptr(),) + wins + (minus.data_ptr(), nwin, kmer_len)
-    _lib.check(L.slk_variant_edits_emit(*head, margin, c.cand_off.data_ptr(), ncand, c.cand_pair.data_ptr(), c.cand_start.data_ptr(),
-                                        c.cand_ndel.data_ptr(), sorted_var.data_ptr(), new_off.data_ptr(), st), "variant_edits_emit")
-    c.cand_new_off = torch.cumsum(new_off, 0)
-    cap = max(ncand * decode.rescore_max_new(), 1)                # (no second round trip for the exact total)
-    c.cand_new = torch.full((cap,), -1, dtype=torch.int32, device=dev)
-    _lib.check(L.slk_variant_edits_new(*head, int(blank), margin, ncand, c.cand_pair.data_ptr(), c.cand_start.data_ptr(),
-                                       sorted_var.data_ptr(), c.cand_new_off.data_ptr(), cap, c.cand_new.data_ptr(), st), "variant_edits_new")
-    c.seq = torch.empty(max(npos, 1), dtype=torch.int32, device=dev)
-    _lib.check(L.slk_polish_window_kmers(genome.data_ptr(), G, *wins, minus.data_ptr(), nwin, kmer_len, int(blank), c.pos_off.data_ptr(),
-                                         npos, c.seq.data_ptr(), st), "polish_window_kmers")
-    c.cand_pair, c.cand_start, c.cand_ndel, sorted_var = c.cand_pair[:ncand], c.cand_start[:ncand], c.cand_ndel[:ncand], sorted_var[:ncand]
-    c.cand_var_sorted = sorted_var
-    c.cand_var = vs.order_dev[sorted_var.to(torch.int64)].to(torch.int32) if ncand else sorted_var
+    c = _candidate_list(
+        "variant_edits", genome, win_off, w0, w1, minus, kmer_len, blank, margin, "cand_var_sorted", torch.int32, decode.rescore_max_new(),
+        lambda L, ncand, nkmer, st: L.slk_variant_edits_count(genome.data_ptr(), G, contig_offsets.data_ptr(), int(contig_offsets.numel()) - 1,
+                                                              *lst, *wins, nwin, kmer_len, margin, status.data_ptr(), ncand, nkmer, st),
+        lambda L, c, new_off, st: L.slk_variant_edits_emit(*head, margin, c.cand_off.data_ptr(), c.ncand, c.cand_pair.data_ptr(),
+                                                           c.cand_start.data_ptr(), c.cand_ndel.data_ptr(), c.cand_var_sorted.data_ptr(),
+                                                           new_off, st),
+        lambda L, c, cap, st: L.slk_variant_edits_new(*head, int(blank), margin, c.ncand, c.cand_pair.data_ptr(), c.cand_start.data_ptr(),
+                                                      c.cand_var_sorted.data_ptr(), c.cand_new_off.data_ptr(), cap, c.cand_new.data_ptr(), st))
+    c.cand_var = vs.order_dev[c.cand_var_sorted.to(torch.int64)].to(torch.int32) if c.ncand else c.cand_var_sorted
     c.var_status = torch.zeros(vs.V, dtype=torch.int32, device=dev)
     if vs.V:
         c.var_status[vs.order_dev] = status[:vs.V]
@@ -866,33 +857,11 @@ def rescore_variants(post, steps, paths, lens, move_row, index, res, strand, inf
     A variant the device refuses raises ValueError.  -> GenomeVariantsRescored."""
     import torch
     _check_kmer_len(kmer_len)
-    if post.dim() != 3 or int(post.shape[2]) != 4 ** kmer_len + 1:
-        raise ValueError("rescore_variants takes a [rows, reads, %d] transducer posterior of %d-mers" % (4 ** kmer_len + 1, kmer_len))
-    B = int(post.shape[1])
-    if len(ops) != B or len(res) != B:
-        raise ValueError("rescore_variants: %d reads in the posterior, %d alignments" % (B, len(ops)))
-    margin = 2 * int(kmer_len) if margin is None else int(margin)
-    pd = post if post.is_contiguous() else post.contiguous()
-    dev = pd.device
     vs = _as_variant_set(index, variants, kmer_len)
-    w = read_windows(paths, lens, move_row, steps, ops, strand, info, index, kmer_len, keep)
-    reads = np.flatnonzero(w.status == READ_DONE)
-    score = torch.full((B,), float('nan'), dtype=torch.float64, device=dev)
-    minus_d = torch.from_numpy(np.ascontiguousarray(w.minus.astype(np.int32))).to(dev)
-    empty = lambda dt: torch.zeros(0, dtype=dt, device=dev)        # noqa: E731
-    if not len(reads):
-        nothing = torch.zeros(0, dtype=torch.int64, device=dev)
-        c = variant_edits(index.genome, vs.contig_off, nothing, nothing, nothing, empty(torch.int32), vs, kmer_len, blank, margin)
-        cand_read, ll = empty(torch.int32), empty(torch.float64)
-    else:
-        reads_d = torch.from_numpy(np.ascontiguousarray(reads.astype(np.int64))).to(dev)
-        c = variant_edits(index.genome, vs.contig_off, *_window_tensors(w, reads, dev), vs, kmer_len, blank, margin)
-        nrow, band, row_off = _read_bands(w, reads, np.diff(c.pos_off_host), width, B, dev)
-        sc, ll = decode.rescore_edits_banded_device(pd, row_off, B, nrow.astype(np.int32), c.seq, c.pos_off, band, width, c.cand_off_host,
-                                                    c.cand_pair, c.cand_start, c.cand_ndel, c.cand_new_off, c.cand_new, blank=blank,
-                                                    min_prob=min_prob, workspace_limit=workspace_limit)
-        score[reads_d] = sc
-        cand_read = reads_d[c.cand_pair.to(torch.int64)].to(torch.int32)
+    w, score, c, cand_read, ll = _rescore_windows(
+        "rescore_variants", post, steps, paths, lens, move_row, index, res, strand, info, ops, kmer_len, width, margin, keep, blank,
+        min_prob, workspace_limit, lambda *wins, margin: variant_edits(index.genome, vs.contig_off, *wins, vs, kmer_len, blank, margin))
+    minus_d = torch.from_numpy(np.ascontiguousarray(w.minus.astype(np.int32))).to(score.device)
     bad = c.var_status.nonzero().reshape(-1)
     if bad.numel():
         v = int(bad[0])
@@ -928,41 +897,3 @@ def accept_genome_variants(cells, variants, text, kmer_len):
             taken.append(it[6])
             spans.append((it[1], first, last))
     return taken
-
-
-def _polish_genome_variants(post, steps, paths, lens, move_row, index, kmer_len, width, margin, kinds, keep, min_gain, min_support,
-                            max_rounds, blank, min_prob, workspace_limit, map_kwargs, proposals):
-    """polish_genome with proposals= (its docstring)."""
-    from . import genome as G
-    kw = dict(map_kwargs or {})
-    host = index.genome.cpu().numpy().tobytes().decode('ascii')
-    text = collections.OrderedDict((n, host[int(a):int(b)]) for n, a, b in zip(index.names, index.offsets[:-1], index.offsets[1:]))
-    applied = dict((n, []) for n in text)
-    rounds = dict((n, 0) for n in text)
-    ix, last, lastv = index, None, None
-    for r in range(int(max_rounds)):
-        got = ix.map_paths(paths, lens, kmer_len, ops=True, **kw)
-        res, strand, info, ops = got[0], got[1], got[2], got[4]
-        mask = keep(res, strand, info) if callable(keep) else keep
-        common = dict(width=width, margin=margin, keep=mask, blank=blank, min_prob=min_prob, workspace_limit=workspace_limit)
-        cells = []
-        if len(kinds):
-            last = rescore_genome(post, steps, paths, lens, move_row, ix, res, strand, info, ops, kmer_len, kinds=kinds, **common)
-            cells = last.cells(min_gain, min_support)
-        asked = proposals(ix) if callable(proposals) else proposals if isinstance(proposals, str) or r == 0 else []
-        lastv = rescore_variants(post, steps, paths, lens, move_row, ix, res, strand, info, ops, kmer_len, asked, **common)
-        taken = accept_genome_variants(cells, lastv.rows(min_gain, min_support), text, kmer_len)
-        if not taken:
-            break
-        for name in text:
-            mine = sorted((t for t in taken if t[0] == name), key=lambda t: t[1], reverse=True)
-            if mine:
-                s = text[name]
-                for t in mine:                                     # (from the back: the positions in front stay)
-                    pos, ndel, alt = (t[1],) + tuple(t[3]) if t[2] == 'var' else _as_replacement(t[2], t[1], t[3])
-                    s = s[:pos] + alt + s[pos + ndel:]
-                text[name] = s
-                applied[name].extend((r, t[1], t[2], t[3], t[4], t[5]) for t in sorted(mine, key=lambda t: t[1]))
-                rounds[name] += 1
-        ix = G.Index(list(text.items()), k=index.k, bin_width=index.bin_width, max_occ=index.max_occ)
-    return [GenomePolished(n, text[n], applied[n], rounds[n]) for n in text], last, lastv
