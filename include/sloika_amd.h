@@ -1256,6 +1256,36 @@ SLK_API int slk_repeat_variants_emit(const uint8_t *genome, long G, const int64_
                                      const int64_t *alt_off, int64_t V, int64_t A, int64_t *var_off, int64_t *var_pos,
                                      int32_t *var_ndel, int64_t *var_alt_off, uint8_t *var_alt, slk_stream_t stream);
 
+/* f10e. Alleles proposed by a pileup and genotype log-likelihoods of proposed variants (csrc/genotype.hip; design/genotypes.md section 1
+ * DEFINES the test a count passes, what a position proposes and in what order, the skipped bits and the three log-likelihoods, and is
+ * not repeated here).  Everything is device data and is not trusted, as in f10d.
+ *   slk_pileup_alleles_count / _emit: counts:[P][8] and ins:[P][max_ins][5] int32, the tables of slk_pileup_count_u8 over the packed
+ *     positions [lo, lo + P); max_ins 1 .. 16, min_depth >= 1, min_count >= 1, permille 1 .. 1000, max_del 1 .. 2^20.  One thread per
+ *     position.  nprop, nalt:[P + 1] int64 with entry 0 zero and entry t + 1 the variants and their alt letters position lo + t
+ *     proposes; skipped:[P] int32 <- SLK_ALLELES_SKIPPED_INS where an insertion has more than SLK_RESCORE_MAX_NEW - kmer_len + 1
+ *     letters, | SLK_ALLELES_SKIPPED_DEL where a deletion run has more than max_del.  Summed in place nprop and nalt are prop_off and
+ *     alt_off, and the emit pass writes the V = prop_off[P] variants and A = alt_off[P] letters in f10d's list layout, sorted as they
+ *     come.  Offsets that are not a position's own counts are not followed.
+ *   slk_variant_genotypes_f64: score, ll_edit, cand_read, cand_var and order as slk_polish_sum_variant_gains_f64 takes them; scale a
+ *     finite double > 0.  Writes gl:[V][3] float64 (0, log-likelihood of 0/1, of 1/1, each against 0/0) and n:[V] int32 of every
+ *     variant that has a candidate -- a caller zeroes both first --: per candidate in read order, both values finite,
+ *     d = scale * (ll_edit - score[cand_read]), gl1 += max(d, 0) + log1p(exp(-|d|)) - ln 2, gl2 += d, n += 1; a NaN of either value
+ *     makes the three NaN.  One thread walks a variant: no floating-point atomics, no bit depends on the launch.                     */
+#define SLK_ALLELES_SKIPPED_INS 1
+#define SLK_ALLELES_SKIPPED_DEL 2
+SLK_API int slk_pileup_alleles_count(const int32_t *counts, const int32_t *ins, const uint8_t *genome, long G,
+                                     const int64_t *contig_off, int ncontig, int64_t lo, int64_t P, int max_ins, int kmer_len,
+                                     int min_depth, int min_count, int permille, int max_del, int64_t *nprop, int64_t *nalt,
+                                     int32_t *skipped, slk_stream_t stream);
+SLK_API int slk_pileup_alleles_emit(const int32_t *counts, const int32_t *ins, const uint8_t *genome, long G,
+                                    const int64_t *contig_off, int ncontig, int64_t lo, int64_t P, int max_ins, int kmer_len,
+                                    int min_depth, int min_count, int permille, int max_del, const int64_t *prop_off,
+                                    const int64_t *alt_off, int64_t V, int64_t A, int64_t *var_off, int64_t *var_pos,
+                                    int32_t *var_ndel, int64_t *var_alt_off, uint8_t *var_alt, slk_stream_t stream);
+SLK_API int slk_variant_genotypes_f64(const double *score, int nread, const double *ll_edit, const int32_t *cand_read,
+                                      const int32_t *cand_var, const int64_t *order, int64_t ncand, int64_t V, double scale, double *gl,
+                                      int32_t *n, slk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

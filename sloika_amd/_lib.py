@@ -205,6 +205,10 @@ PROTOTYPES = {
     "slk_repeat_variants_count": (_i, [_vp, _l, _vp, _i, C.c_int64, C.c_int64, _i, _i, _i, _i, _vp, _vp, _vp]),
     "slk_repeat_variants_emit": (_i, [_vp, _l, _vp, _i, C.c_int64, C.c_int64, _i, _i, _i, _i, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp,
                                       _vp, _vp, _vp, _vp]),
+    "slk_pileup_alleles_count": (_i, [_vp, _vp, _vp, _l, _vp, _i, C.c_int64, C.c_int64, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "slk_pileup_alleles_emit": (_i, [_vp, _vp, _vp, _l, _vp, _i, C.c_int64, C.c_int64, _i, _i, _i, _i, _i, _i, _vp, _vp, C.c_int64,
+                                     C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "slk_variant_genotypes_f64": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _d, _vp, _vp, _vp]),
 }
 
 _lib = None

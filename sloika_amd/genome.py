@@ -631,6 +631,46 @@ class Pileup(object):
                                                  nlet.data_ptr(), flags.data_ptr(), D.stream_ptr()), "pileup_call")
         return Consensus(self, letters[:self.P], nlet[:self.P], flags[:self.P], int(min_depth))
 
+    def alleles(self, kmer_len, min_count=2, min_fraction=0.2, min_depth=3, max_del=8):
+        """The variants the pileup's own disagreeing reads propose (slk_pileup_alleles_count / _emit; design/genotypes.md 1.1), the
+        minority ones too: at every position whose reference letter is one of A C G T, the insertion in front of it, the
+        substitutions and the deletion run that starts there whose counts n pass n >= min_count, 1000 n >= permille x depth and
+        depth >= min_depth (permille = round(1000 min_fraction); depth the position's own, an insertion's the `span` of the
+        position in front).  An insertion of more than polish.max_alt(kmer_len) letters and a deletion run of more than max_del
+        are not proposed and counted in `skipped`.  Runs and insertions are cut at the Pileup's span.  Each variant stands against
+        the reference alone; overlapping alleles are separate variants.
+        -> polish.VariantSet, sorted as it comes, with `skipped` = {'insertion': positions, 'deletion': runs} and `skipped_dev`,
+        int32 [P] on the device (bit 1: the insertion in front, bit 2: the run that starts there)."""
+        import torch
+        from . import device as D, polish
+        permille = int(round(1000.0 * float(min_fraction)))
+        if min(int(min_count), int(min_depth), int(max_del)) < 1 or not 1 <= permille <= 1000 or int(max_del) > 1 << 20:
+            raise ValueError("genome: alleles needs min_count, min_depth >= 1, max_del 1 .. 2^20 and min_fraction in (0, 1], not %r"
+                             % ((min_count, min_depth, max_del, min_fraction),))
+        polish._check_kmer_len(kmer_len)
+        ix, P = self.index, self.P
+        dev = self.counts_dev.device
+        coff = polish._contig_offsets(ix, dev)
+        L, st = _lib.lib(), D.stream_ptr()
+        head = (self.counts_dev.data_ptr(), self.ins_dev.data_ptr(), ix.genome.data_ptr(), int(ix.G), coff.data_ptr(), len(ix.names),
+                self.lo, P, self.S, int(kmer_len), int(min_depth), int(min_count), permille, int(max_del))
+        offs = torch.zeros((2, P + 1), dtype=torch.int64, device=dev)
+        skipped = torch.zeros(max(P, 1), dtype=torch.int32, device=dev)
+        _lib.check(L.slk_pileup_alleles_count(*head, offs[0].data_ptr(), offs[1].data_ptr(), skipped.data_ptr(), st),
+                   "pileup_alleles_count")
+        offs = torch.cumsum(offs, 1)
+        V, A = (int(v) for v in offs[:, -1].cpu().numpy())
+        var_off = torch.zeros(V, dtype=torch.int64, device=dev)
+        var_pos, var_ndel = torch.zeros_like(var_off), torch.zeros(V, dtype=torch.int32, device=dev)
+        var_alt_off, var_alt = torch.zeros(V + 1, dtype=torch.int64, device=dev), torch.zeros(A, dtype=torch.uint8, device=dev)
+        _lib.check(L.slk_pileup_alleles_emit(*head, offs[0].data_ptr(), offs[1].data_ptr(), V, A, var_off.data_ptr(), var_pos.data_ptr(),
+                                             var_ndel.data_ptr(), var_alt_off.data_ptr(), var_alt.data_ptr(), st), "pileup_alleles_emit")
+        out = polish.VariantSet(ix, var_off, var_pos, var_ndel, var_alt_off, var_alt, coff)
+        out.skipped_dev = skipped[:P]
+        out.prop_off, out.alt_off = offs[0], offs[1]
+        out.skipped = {'insertion': int((out.skipped_dev & 1).ne(0).sum()), 'deletion': int((out.skipped_dev & 2).ne(0).sum())}
+        return out
+
 
 class Consensus(object):
     """The calls of a Pileup.  letters_dev:[P, 1 + max_ins] uint8, nlet_dev:[P], flags_dev:[P] on the device; `flags` the host copy
@@ -844,3 +884,55 @@ def pileup(index, res, strand, info, ops, region=None, max_ins=4, keep=None, nor
                weights=weights)
     p.add(res, strand, info, ops, keep=keep, normalise=normalise, qual=qual)
     return p, p.consensus(min_depth=min_depth)
+
+
+# ---- VCF text (design/genotypes.md 1.4) ----------------------------------------------------------------------------------------------
+
+VCF_FORMAT = "GT:GQ:DP:AD:PL"
+
+
+def vcf_record(contig, pos, ndel, alt):
+    """(POS, REF, ALT) of replacing contig[pos:pos + ndel] by alt.  ndel == len(alt) == 1: a SNV at pos + 1; both sides non-empty:
+    POS = pos + 1, REF the replaced letters; a pure insertion or deletion takes the base in front (POS = pos), at pos 0 the base
+    behind (POS = 1, REF = contig[0:ndel + 1], ALT = alt + contig[ndel])."""
+    pos, ndel = int(pos), int(ndel)
+    if pos < 0 or ndel < 0 or pos + ndel > len(contig) or ndel + len(alt) < 1:
+        raise ValueError("genome: (%d, %d, %r) is no variant of a contig of %d letters" % (pos, ndel, alt, len(contig)))
+    if ndel and alt:
+        return pos + 1, contig[pos:pos + ndel], alt
+    if pos > 0:
+        return pos, contig[pos - 1:pos + ndel], contig[pos - 1] + alt
+    if ndel >= len(contig):
+        raise ValueError("genome: VCF has no anchor for a variant that deletes or fills a whole contig")
+    return 1, contig[0:ndel + 1], alt + contig[ndel]
+
+
+def vcf_text(index, rows, sample='sample', min_gq=20):
+    """VCFv4.2 text of called variants.  rows: polish.VariantCall (contig, pos, ndel, alt, gt, gq, dp, ad, pl, qual), as
+    polish.VariantCalls.rows() gives them.  The header names every contig of `index` in its order; the records come in contig
+    order, then by POS, and as they were given beyond that; FILTER is PASS, or LowGQ below min_gq; one sample column,
+    GT:GQ:DP:AD:PL with DP the reads that scored the variant and AD those that do not prefer it and those that do."""
+    names = list(index.names)
+    host = index.genome.cpu().numpy().tobytes().decode('ascii')
+    text = dict((n, host[int(a):int(b)]) for n, a, b in zip(names, index.offsets[:-1], index.offsets[1:]))
+    head = ["##fileformat=VCFv4.2", "##source=sloika_amd"]
+    head += ["##contig=<ID=%s,length=%d>" % (n, len(text[n])) for n in names]
+    head += ['##FILTER=<ID=LowGQ,Description="Genotype quality below %d">' % int(min_gq),
+             '##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">',
+             '##FORMAT=<ID=GQ,Number=1,Type=Integer,Description="Genotype quality">',
+             '##FORMAT=<ID=DP,Number=1,Type=Integer,Description="Reads whose signal scored the variant">',
+             '##FORMAT=<ID=AD,Number=R,Type=Integer,Description="Reads whose signal prefers the reference, the variant">',
+             '##FORMAT=<ID=PL,Number=G,Type=Integer,Description="Phred-scaled genotype likelihoods, not calibrated">',
+             "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s" % sample]
+    recs = []
+    for row in rows:
+        name = row[0] if not isinstance(row[0], (int, np.integer)) else names[int(row[0])]
+        if name not in text:
+            raise ValueError("genome: a call names the contig %r, which the index does not hold" % (row[0],))
+        pos, ref, alt = vcf_record(text[name], row[1], row[2], row[3])
+        gt, gq, dp, ad, pl, qual = row[4:10]
+        call = "%s:%d:%d:%d,%d:%d,%d,%d" % ("./." if gt < 0 else ("0/0", "0/1", "1/1")[gt], gq, dp, ad[0], ad[1], pl[0], pl[1], pl[2])
+        recs.append((names.index(name), pos, "\t".join([name, str(pos), ".", ref, alt, "%.1f" % qual, "PASS" if gq >= min_gq else "LowGQ",
+                                                         ".", VCF_FORMAT, call])))
+    recs.sort(key=lambda r: r[:2])                                   # (stable)
+    return "\n".join(head + [r[2] for r in recs]) + "\n"

@@ -560,6 +560,26 @@ class Basecaller(object):
                                            width=width, margin=margin, keep=mask, blank=0, min_prob=self.min_prob,
                                            workspace_limit=workspace_limit)
 
+    def call_variants(self, signals, index, min_count=2, min_fraction=0.2, min_depth=3, max_del=8, max_ins=4, het=1e-3, prior=None,
+                      scale=1.0, variants=None, region=None, keep=None, width=512, margin=None, trim=(0, 0), open_pore_fraction=0.0,
+                      scaling=None, workspace_limit=None, **map_kwargs):
+        """Call the variants of a sample against a reference from whole reads (design/genotypes.md): one network pass and decode, one
+        mapping (genome.Index.map_paths(ops=True, **map_kwargs)), a pileup of the kept reads, the alleles it proposes -- the minority
+        ones too -- with `variants` (rows, a polish.VariantSet or 'repeats') added, each put to the reads' signal on the same mapping
+        (polish.rescore_variants) and genotyped (polish.genotypes; het, prior, scale).  keep as rescore_genome.  The likelihood ratios
+        are the network's own and are not calibrated: what `scale` should be on real reads has not been measured.
+        -> polish.VariantCalls (rows(), vcf())."""
+        from . import polish
+        with self._scope():
+            post, steps, paths, lens, move_row = self._genome_reads(signals, trim, open_pore_fraction, scaling, "call_variants")
+            got = index.map_paths(paths, lens, self.kmer_len, ops=True, **map_kwargs)
+            res, strand, info, ops = got[0], got[1], got[2], got[4]
+            mask = keep(res, strand, info) if callable(keep) else keep
+            return polish.call_variants(post, steps, paths, lens, move_row, index, res, strand, info, ops, self.kmer_len,
+                                        min_count=min_count, min_fraction=min_fraction, min_depth=min_depth, max_del=max_del,
+                                        max_ins=max_ins, het=het, prior=prior, scale=scale, variants=variants, region=region, width=width,
+                                        margin=margin, keep=mask, blank=0, min_prob=self.min_prob, workspace_limit=workspace_limit)
+
     def polish_genome(self, signals, index, width=512, margin=None, kinds=('sub', 'del', 'ins'), keep=None, min_gain=0.0,
                       min_support=2, max_rounds=4, trim=(0, 0), open_pore_fraction=0.0, scaling=None, workspace_limit=None,
                       proposals=None, **map_kwargs):

@@ -897,3 +897,164 @@ def accept_genome_variants(cells, variants, text, kmer_len):
             taken.append(it[6])
             spans.append((it[1], first, last))
     return taken
+
+
+# ---- genotypes of proposed variants (csrc/genotype.hip, design/genotypes.md) -----------------------------------------------------------
+
+GENOTYPES = ("0/0", "0/1", "1/1")
+GQ_CAP, PL_CAP, QUAL_CAP = 99, 999, 999.0
+
+#: one called variant: the variant, gt -1 (./.) or an index of GENOTYPES, gq, dp (the reads that scored it), ad (reads that do not
+#: prefer it, reads that do), pl (three values) and qual
+VariantCall = collections.namedtuple("VariantCall", "contig pos ndel alt gt gq dp ad pl qual")
+
+
+def variant_genotype_likelihoods(score, ll_edit, cand_read, cand_var, V, scale=1.0):
+    """The genotype log-likelihoods of V variants from their candidates (slk_variant_genotypes_f64; design/genotypes.md 1.2): score
+    float64 per read, ll_edit float64, cand_read and cand_var int32 per candidate, as sum_variant_gains takes them, sorted the same
+    way.  Per variant, over its candidates in read order with both values finite, d = scale * (ll_edit - score[read]):
+    gl = (0, sum of log(1/2 + 1/2 e^d), sum of d), the log-likelihoods of 0/0, 0/1 and 1/1 against 0/0, and n their number.  A NaN
+    of either value makes the three NaN.  -> (gl float64 [V, 3], n int32 [V]) on the device."""
+    import torch
+    from . import _lib, device as D
+    dev = score.device
+    V, ncand, scale = int(V), int(ll_edit.numel()), float(scale)
+    if not scale > 0.0 or scale in (float('inf'),):
+        raise ValueError("genotype likelihoods: scale = %r is no positive finite number" % (scale,))
+    if cand_read.numel() != ncand or cand_var.numel() != ncand or cand_read.dtype != torch.int32 or cand_var.dtype != torch.int32 or \
+            score.dtype != torch.float64 or ll_edit.dtype != torch.float64:
+        raise ValueError("genotype likelihoods need one int32 read, one int32 variant and one float64 value per candidate, and a "
+                         "float64 score per read")
+    gl = torch.zeros((V, 3), dtype=torch.float64, device=dev)
+    n = torch.zeros(V, dtype=torch.int32, device=dev)
+    if ncand and V:
+        by_read = torch.sort(cand_read, stable=True).indices
+        order = by_read[torch.sort(cand_var[by_read], stable=True).indices].contiguous()
+        _lib.check(_lib.lib().slk_variant_genotypes_f64(
+            score.contiguous().data_ptr(), int(score.numel()), ll_edit.contiguous().data_ptr(), cand_read.contiguous().data_ptr(),
+            cand_var.contiguous().data_ptr(), order.data_ptr(), ncand, V, scale, gl.data_ptr(), n.data_ptr(), D.stream_ptr()),
+            "variant_genotypes")
+    return gl, n
+
+
+def genotype_likelihoods(rescored, scale=1.0):
+    """variant_genotype_likelihoods of a GenomeVariantsRescored: -> (gl [V, 3], n [V]) on the device, in the caller's order.  At scale
+    1.0 gl[:, 2] has the bits of rescored.gain and n is rescored.support."""
+    return variant_genotype_likelihoods(rescored.score, rescored.ll_edit, rescored.cand_read, rescored.cand_var, len(rescored.variants),
+                                        scale)
+
+
+def genotype_prior(het=1e-3, prior=None):
+    """(p00, p01, p11): `prior` itself, or (1 - 1.5 het, het, het / 2)."""
+    p = (1.0 - 1.5 * float(het), float(het), float(het) / 2.0) if prior is None else tuple(float(v) for v in prior)
+    if len(p) != 3 or not all(0.0 < v <= 1.0 for v in p):
+        raise ValueError("genotypes: the prior %r is not three probabilities above 0" % (p,))
+    return p
+
+
+def call_genotypes(gl, n, het=1e-3, prior=None):
+    """The host half of `genotypes` (design/genotypes.md 1.3), numpy float64: gl [V, 3] and n [V] -> (gt int [V], gq int [V], pl int
+    [V, 3], qual float [V]).  The log-posteriors are gl + log prior, normalised by a max-shifted log-sum-exp; gt their arg-max (ties
+    to the lower index), -1 where n == 0 or gl is NaN; gq = min(99, floor(10 / ln 10 x (best - second))); pl = round(-10 / ln 10 x
+    (gl - max gl)) capped at 999, from the likelihoods; qual = min(999, -10 log10 P(0/0 | reads)) to one decimal.  An uncalled
+    variant has zeros."""
+    gl = np.asarray(gl, dtype=np.float64).reshape(-1, 3)
+    n = np.asarray(n).reshape(-1)
+    V = gl.shape[0]
+    if n.shape[0] != V:
+        raise ValueError("genotypes: %d rows of likelihoods for %d counts" % (V, n.shape[0]))
+    called = (n > 0) & ~np.isnan(gl).any(axis=1)
+    g = np.where(called[:, None], gl, 0.0)
+    post = g + np.log(np.array(genotype_prior(het, prior), dtype=np.float64))[None, :]
+    mx = post.max(axis=1, keepdims=True)
+    post = post - (mx + np.log(np.exp(post - mx).sum(axis=1, keepdims=True)))
+    gt = np.argmax(post, axis=1)                                     # (the first of equal values)
+    ranked = np.sort(post, axis=1)
+    k = 10.0 / np.log(10.0)
+    gq = np.minimum(np.floor(k * (ranked[:, 2] - ranked[:, 1])), GQ_CAP).astype(np.int64)
+    pl = np.minimum(np.rint(-k * (g - g.max(axis=1, keepdims=True))), PL_CAP).astype(np.int64)
+    qual = np.round(np.minimum(-k * post[:, 0], QUAL_CAP), 1) + 0.0  # (+ 0.0: no negative zero)
+    gt = np.where(called, gt, -1).astype(np.int64)
+    gq[~called] = 0
+    pl[~called] = 0
+    qual[~called] = 0.0
+    return gt, gq, pl, qual
+
+
+class VariantCalls(object):
+    """The genotypes of proposed variants (genotypes; design/genotypes.md).  Every array is in the caller's order of the variants.
+
+    gl float64 [V, 3], n int32 [V]: device tensors (genotype_likelihoods); gt, gq, pl, qual: host arrays (call_genotypes); support, pro,
+    support_strand, pro_strand: host copies of the rescoring's tables; rescored: the GenomeVariantsRescored behind them; variants:
+    its VariantSet.  Each variant is judged against the reference alone (biallelic): overlapping alleles are separate records.
+    The likelihood ratios are the network's own and are not calibrated (design/genotypes.md 1.3): `scale` is the knob."""
+
+    def __init__(self, rescored, gl, n, gt, gq, pl, qual, prior, scale):
+        self.rescored, self.variants, self.index = rescored, rescored.variants, rescored.variants.index
+        self.gl, self.n, self.gt, self.gq, self.pl, self.qual, self.prior, self.scale = gl, n, gt, gq, pl, qual, prior, scale
+        self.support, self.pro = rescored.support.cpu().numpy(), rescored.pro.cpu().numpy()
+        self.support_strand, self.pro_strand = rescored.support_strand.cpu().numpy(), rescored.pro_strand.cpu().numpy()
+        self._n = n.cpu().numpy()
+
+    def __len__(self):
+        return len(self.variants)
+
+    def rows(self, min_gq=0, nonref=True):
+        """[VariantCall] of the variants with gq >= min_gq, in the caller's order; nonref: only those called 0/1 or 1/1."""
+        rows = self.variants.rows()
+        return [VariantCall(*rows[v], gt=int(self.gt[v]), gq=int(self.gq[v]), dp=int(self._n[v]),
+                            ad=(int(self._n[v]) - int(self.pro[v]), int(self.pro[v])), pl=tuple(int(x) for x in self.pl[v]),
+                            qual=float(self.qual[v]))
+                for v in range(len(rows)) if self.gq[v] >= min_gq and (self.gt[v] > 0 or not nonref)]
+
+    def vcf(self, sample='sample', min_gq=20, all_records=False):
+        """VCFv4.2 text (genome.vcf_text): the non-reference calls, LowGQ below min_gq; all_records: 0/0 and ./. as well."""
+        from . import genome as G
+        return G.vcf_text(self.index, self.rows(0, nonref=not all_records), sample, min_gq=min_gq)
+
+
+def genotypes(rescored, het=1e-3, prior=None, scale=1.0):
+    """Genotype every variant of a GenomeVariantsRescored: genotype_likelihoods on the device, call_genotypes on the host.
+    -> VariantCalls."""
+    p = genotype_prior(het, prior)
+    gl, n = genotype_likelihoods(rescored, scale)
+    gt, gq, pl, qual = call_genotypes(gl.cpu().numpy(), n.cpu().numpy(), prior=p)
+    return VariantCalls(rescored, gl, n, gt, gq, pl, qual, p, float(scale))
+
+
+def merged_variants(index, first, more, kmer_len):
+    """The rows of the VariantSet `first` followed by those of `more` (a list of (contig, pos, ndel, alt), a VariantSet or 'repeats')
+    that are not among them already, by content (contig name, pos, ndel, alt).  -> `first` itself when nothing is added, else a new
+    VariantSet (upload_variants)."""
+    if more is None:
+        return first
+    added = _as_variant_set(index, more, kmer_len)
+    if len(first) == 0 and len(set(added.rows())) == len(added):
+        return added
+    extra = added.rows()
+    rows = first.rows()
+    seen = set(rows)
+    for row in extra:
+        if row not in seen:
+            seen.add(row)
+            rows.append(row)
+    return first if len(rows) == len(first) else upload_variants(index, rows, kmer_len)
+
+
+def call_variants(post, steps, paths, lens, move_row, index, res, strand, info, ops, kmer_len, min_count=2, min_fraction=0.2, min_depth=3,
+                  max_del=8, max_ins=4, het=1e-3, prior=None, scale=1.0, variants=None, region=None, width=512, margin=None, keep=None,
+                  blank=0, min_prob=None, workspace_limit=None):
+    """Call the variants of a sample against the genome its reads were mapped to (design/genotypes.md): a genome.Pileup of the kept
+    reads over `region`, its alleles (Pileup.alleles; min_count, min_fraction, min_depth, max_del), with `variants` (a list, a
+    VariantSet or 'repeats') added where they are not among them, put to the reads' signal on the SAME mapping (rescore_variants) and
+    genotyped (genotypes).  Everything else as rescore_variants takes it.  -> VariantCalls."""
+    from . import genome as G
+    pile = G.Pileup(index, region=region, max_ins=max_ins)
+    pile.add(res, strand, info, ops, keep=keep)
+    alleles = pile.alleles(kmer_len, min_count=min_count, min_fraction=min_fraction, min_depth=min_depth, max_del=max_del)
+    asked = merged_variants(index, alleles, variants, kmer_len)
+    got = rescore_variants(post, steps, paths, lens, move_row, index, res, strand, info, ops, kmer_len, asked, width=width, margin=margin,
+                           keep=keep, blank=blank, min_prob=min_prob, workspace_limit=workspace_limit)
+    calls = genotypes(got, het=het, prior=prior, scale=scale)
+    calls.pileup, calls.skipped = pile, alleles.skipped
+    return calls
