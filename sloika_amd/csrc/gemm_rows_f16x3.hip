@@ -12,8 +12,12 @@
 // Range: fp16 overflows at 65504 and loses its lo half below 6e-5, so every row of x (in the kernel) and every row of W (in
 // slk_split_f16x2_f32) is first scaled by a power of two that brings its largest magnitude into [1, 2); the scaling is
 // exact and is undone on the float32 accumulators (one multiply by the product row's inverse scale, one fused
-// multiply-add with the weight row's inverse scale and the bias).  Any finite float32 operand is therefore handled with
-// 22 significand bits relative to its row maximum -- float32-grade.
+// multiply-add with the weight row's inverse scale and the bias).  gh_pow2_scale clamps the scale's exponent, so this holds
+// for row maxima in [2^-100, 2^101): such a row is handled with 22 significand bits relative to its row maximum --
+// float32-grade.  Outside (design/fp16_split.md, tests/test_gpu_projection_edges.py): a smaller maximum is scaled by 2^100
+// only and loses one bit of its lo halves per halving, down to a row of zeros; a larger one is scaled by 2^-100 only, stays
+// float32-grade while the scaled maximum is below 65520 (maxima below 65520 * 2^100) and becomes fp16 infinity from there
+// on -- every product of that row is then non-finite, never a finite wrong number, and no other row or column changes.
 #include "common.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));

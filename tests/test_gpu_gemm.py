@@ -211,7 +211,8 @@ def test_gemm_bias_act_f16x3_vs_float64(K, N, act):
 @pytest.mark.parametrize("xmag,wmag", [(1e-7, 1.0), (1e-3, 1e3), (1e3, 1e-3), (1e5, 1e-5), (1e5, 1.0), (3e7, 1e-6), (1.0, 1e6)])
 def test_f16x3_operands_of_any_magnitude(xmag, wmag):
     """fp16 alone overflows at 65504 and has no lo half below 6e-5.  Rows of x and of W are scaled by powers of two before
-    their split, so the 3-term product stays float32-grade for any finite magnitudes -- also when rows of very different
+    their split, so the 3-term product stays float32-grade for row maxima in [2^-100, 2^101), the range gh_pow2_scale's
+    clamped exponent covers (its ends: tests/test_gpu_projection_edges.py) -- also when rows of very different
     size share a tile and when one row holds an outlier.  Checked against float64, relative to sum |x||w|."""
     torch = need_gpu()
     from sloika_amd import _lib
